@@ -1,7 +1,13 @@
 """bench.py — BASELINE.json's metric on its own config.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up for W frames, times K frames and prints the JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, and the counters of the timed frames); nothing else.  --full adds what needs runs of its own: the live PMC passes, the
+roofline object, the CPU baseline and, at N = 1, the other BASELINE configs (all described below; --no-pmc, --no-cpu-baseline and
+--no-extra-configs drop single legs of it).  --dump-outputs DIR writes the frame the last timed step accumulated to DIR/frame.npy
+(`dump_outputs`): the same arguments give the same inputs on every run, so two builds can be compared output for output.
 
 Workload (config.workload): assets house.toml, 1920x1080, 256 spp, 8 bounces, synthetic 2048x1024
 environment (the reference's HDRIs are missing blobs) — BASELINE.json configs[3], the
@@ -20,16 +26,16 @@ region and every candidate exchange — librsrt's RCCL gather of compact tile bu
 it bit for bit before it is timed (the first that does is used, all ranks switching together: `multi_gpu.pre_flight`); the JSON line says whether
 the last timed frame equals it too (`frame_equals_1gpu`), which exchange really ran, and every rank's trace / exchange milliseconds (`multi_gpu`); the collective bring-up (rsrt_comm_init) and the first exchange run under a watchdog
 thread that, should they not return within RSRT_BENCH_WATCHDOG_S seconds (default 120), prints rank / step / an NCCL_DEBUG hint to stderr
-and ends the process with os._exit(3) — a fresh non-zero exit, never a re-exec.  At N = 1 the line also carries `extra_configs`: the other
+and ends the process with os._exit(3) — a fresh non-zero exit, never a re-exec.  With --full at N = 1 the line also carries `extra_configs`: the other
 BASELINE.json configs (default, cube, suzanne, the 15 k-triangle grid, sixteen back-to-back single-sample calls), 3 frames each AFTER the
 timed region, with the oracle-counted roofline fraction of each.
 
-roofline: the kernel's scene is LDS-resident and its environment MALL-resident, so HBM is not the
+roofline (--full): the kernel's scene is LDS-resident and its environment MALL-resident, so HBM is not the
 roof it is under; FP32 VALU issue is.  `frac` = ALGORITHMIC lane-operations per second (the f32 / u32 operations the
 reference's integrator executes per path, counted by the oracle's counting build, x paths / launch time) / 78.64 T/s;
 `utilisation` = the kernel's own retired VALU lane-instructions per SIMD-cycle / 32 (a SIMD retires at most one
 wave64 VALU instruction per 2 cycles = 32 lanes per cycle), from rocprofv3 PMC counters collected
-LIVE by this run: before the GPU is touched, rank 0 (N = 1) starts `rocprofv3 --kernel-trace --pmc ... -- python3
+LIVE by a --full run: before the GPU is touched, rank 0 (N = 1) starts `rocprofv3 --kernel-trace --pmc ... -- python3
 bench.py --pmc-child` four times (separate passes: SQ + GRBM, FETCH_SIZE + LDS, WRITE_SIZE + TCC hit / miss, read
 requests by size), each rendering one frame of the same workload with the same library.  If rocprofv3 cannot run, the committed counters of
 profiles/pmc_house_1080p_8b.json are used — but only when they were taken on the same kernel sources
@@ -180,6 +186,46 @@ def cpu_leg(scene, env, width, height, bounces, log):
 def scene_path(name):
     """--scene: a name under tests/golden/assets/scenes/ or the path of a .toml (tools/make_big_scene.py)."""
     return name if name.endswith(".toml") else os.path.join(ROOT, "tests", "golden", "assets", "scenes", name + ".toml")
+
+
+def use_built_libraries(log):
+    """The package checks for a rebuild of librsrt_host.so / librsrt.so under a lock file in its own directory.  A user who may not
+    write that file (a tree that build() prepared as another user, or a read-only one) could not even load the libraries; such a
+    run loads what build() left instead (RSRT_HOST_LIB / RSRT_LIB, unless already set).  Returns the variables it set."""
+    pkg = os.path.join(ROOT, "rsoderh-raytracing_amd")
+    lock = os.path.join(pkg, ".build.lock")
+    if os.access(lock, os.W_OK) if os.path.exists(lock) else os.access(pkg, os.W_OK):
+        return []
+    set_vars = []
+    for var, name in (("RSRT_HOST_LIB", "librsrt_host.so"), ("RSRT_LIB", "librsrt.so")):
+        path = os.path.join(pkg, name)
+        if os.path.exists(path) and not os.environ.get(var):
+            os.environ[var] = path
+            set_vars.append(var)
+    if set_vars:
+        log("the package directory is not writable by this user: using the libraries build() left (%s)" % ", ".join(set_vars))
+    return set_vars
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_PIXELS = 1 << 20
+
+
+def dump_outputs(out_dir, frame, seed=0):
+    """--dump-outputs: what the timed path hands its caller, from the LAST timed step — the accumulator ([H, W, 4] float32: per-pixel
+    sums of the frame's samples, alpha 1 where rendered) — as <out_dir>/frame.npy.  A frame above 64 MiB is written as a fixed sample
+    instead: frame_sample.npy ([K, 4] float32, K = 2^20 pixels drawn without replacement by a generator seeded with `seed`) and
+    frame_sample_pixels.npy (their flat indices y * W + x, ascending, float64).  Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    if frame.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "frame.npy"), frame)
+        return ["frame"]
+    pixels = frame.reshape(-1, frame.shape[-1])
+    idx = np.sort(np.random.default_rng(seed).choice(len(pixels), size=min(DUMP_SAMPLE_PIXELS, len(pixels)), replace=False))
+    np.save(os.path.join(out_dir, "frame_sample.npy"), pixels[idx])
+    np.save(os.path.join(out_dir, "frame_sample_pixels.npy"), idx.astype(np.float64))
+    return ["frame_sample", "frame_sample_pixels"]
 
 
 # ---------------------------------------------------------------------------------------------- PMC (rocprofv3)
@@ -467,11 +513,12 @@ def extra_configs(env, device_index, log, frames=3):
     import rsoderh_raytracing_amd as R
     out = []
     peak = N_SIMD * LANES_PER_SIMD_CYCLE * MAX_CLOCK_HZ / 1e12
+    scene_dir = tempfile.mkdtemp(prefix="rsrt_scenes_")  # the generated grid scene: this run's own directory, removed at the end
     for label, scene, w, h, spp, mb, calls in EXTRA_CONFIGS:
         try:
             if scene.startswith("grid"):
                 import make_big_scene
-                path = make_big_scene.make(int(scene[4:]))
+                path = make_big_scene.make(int(scene[4:]), scene_dir)
             else:
                 path = scene_path(scene)
             sc = R.Scene.load_toml(path)
@@ -511,6 +558,7 @@ def extra_configs(env, device_index, log, frames=3):
         except Exception as e:  # noqa: BLE001  (a config that cannot run must not cost the headline line)
             out.append({"workload": label, "error": str(e).splitlines()[0][:200]})
             log("extra config %s failed: %s" % (label, e))
+    shutil.rmtree(scene_dir, ignore_errors=True)
     return out
 
 
@@ -524,17 +572,24 @@ def main():
     ap.add_argument("--spp", type=int, default=256)
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--scene", default="house")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="do not start rocprofv3 (the committed counters are used if they match the library)")
-    ap.add_argument("--no-extra-configs", action="store_true", help="N = 1: do not time the other BASELINE configs after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what needs runs of its own: live PMC passes, the roofline object, the CPU baseline, the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the frame of the last timed step to DIR/frame.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not start rocprofv3 (the committed counters are used if they match the library)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="--full, N = 1: do not time the other BASELINE configs after the timed region")
     ap.add_argument("--collective", default="rccl", choices=["rccl", "torch-nccl", "gloo"],
                     help="rccl: rsrt_comm_reduce inside librsrt (the product path); torch-nccl: torch.distributed's reduce; "
                          "gloo: host reduce (rehearsal of N > 1 on one GPU)")
-    ap.add_argument("--write-profile", action="store_true", help="store the PMC counters + algorithmic counts under profiles/")
+    ap.add_argument("--write-profile", action="store_true", help="--full: store the PMC counters + algorithmic counts under profiles/")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.pmc_child:
         return pmc_child(args)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.write_profile and not args.full:
+        ap.error("--write-profile needs --full (the live PMC passes)")
 
     # stdout is for the ONE JSON line: libraries that write to fd 1 (RCCL prints a version banner when a communicator
     # comes up) are sent to stderr for the whole run, the line goes to the saved descriptor at the end
@@ -555,10 +610,11 @@ def main():
         if rank == 0:
             print("[bench] " + msg, file=sys.stderr, flush=True)
 
-    std_cfg = (args.scene, args.width, args.height, args.bounces, args.spp) == ("house", 1920, 1080, 8, 256)
+    use_built_libraries(log)  # (before the PMC children start: they inherit the environment)
+    std_cfg =(args.scene, args.width, args.height, args.bounces, args.spp) == ("house", 1920, 1080, 8, 256)
     # PMC passes first: this process has not touched the GPU yet, the children come and go one at a time
     pmc = None
-    if world == 1 and not args.no_pmc:
+    if args.full and world == 1 and not args.no_pmc:
         pmc = collect_pmc(args, log)
 
     import torch
@@ -737,41 +793,45 @@ def main():
             proof = frame_proof(frame, alone_frame)
             log("N = %d frame equals the 1-GPU frame bit for bit: %s" % (world, proof["frame_equals_1gpu"]))
         value = rays_total / elapsed / 1e6
-        launches_trace = args.steps * max(1, (s["launches"] // 2) // args.steps)
-        trace_ms_per_launch = s["trace_kernel_ms"] / launches_trace
-        cpu_base, per_path, counts = None, None, None
-        if world == 1 and not args.no_cpu_baseline:
-            cpu_base, per_path, counts = cpu_leg(scene, env, W, H, args.bounces, log)
-        committed = None
-        if std_cfg and os.path.exists(PMC_FILE):
-            with open(PMC_FILE) as f:
-                committed = json.load(f)
-        if per_path is None and committed is not None:
-            per_path = committed.get("algorithmic_bytes_per_path")
-        if counts is None and committed is not None and (committed.get("algorithmic_counts_1spp") or {}).get("f32_ops"):
-            counts = committed["algorithmic_counts_1spp"]  # (a property of the workload and of the reference's algorithm, not of the kernel)
-        if pmc is not None and pmc["build_id"] != build_id:
-            log("pmc: the child ran build %s, this process %s: counters dropped" % (pmc["build_id"], build_id))
-            pmc = None
-        if pmc is None and world == 1 and committed is not None:
-            if committed.get("build_id") == build_id:
-                pmc = {k: committed[k] for k in ("counters", "resolve", "kernel", "build_id", "launch_ms_under_pmc")}
-                pmc["source"] = "committed: profiles/pmc_house_1080p_8b.json (same rsrt_build_id as this library)"
-            else:
-                log("pmc: profiles/pmc_house_1080p_8b.json was taken on build %s, this library is %s: not attached" % (committed.get("build_id"), build_id))
-        paths_per_launch = s["paths"] / launches_trace  # this rank's kernel
-        owned_pixels = int(partition.owned_mask(W, H, rank, world).sum())
-        roofline = roofline_object(pmc if world == 1 else None, build_id, trace_ms_per_launch, paths_per_launch, per_path, owned_pixels, spp,
-                                   counts)
-        if world > 1:
-            roofline["note"] = "per-kernel counters are collected at N = 1 only; this object carries the launch time and the algorithmic bytes of rank 0's share"
-        if args.write_profile and std_cfg and world == 1 and pmc is not None and str(pmc.get("source", "")).startswith("live"):
-            os.makedirs(os.path.dirname(PMC_FILE), exist_ok=True)
-            with open(PMC_FILE, "w") as f:
-                json.dump({"workload": "house.toml 1920x1080 256 spp 8 bounces, one frame per PMC pass", "build_id": build_id, "kernel": pmc["kernel"],
-                           "launch_ms_under_pmc": pmc["launch_ms_under_pmc"], "counters": pmc["counters"], "resolve": pmc["resolve"],
-                           "algorithmic_bytes_per_path": per_path, "algorithmic_counts_1spp": counts,
-                           "passes": PMC_PASSES, "source": "bench.py --write-profile (rocprofv3 --kernel-trace --pmc, separate passes)"}, f, indent=1)
+        if args.dump_outputs:
+            log("outputs of the last timed step: %s" % ", ".join(n + ".npy" for n in dump_outputs(args.dump_outputs, frame)))
+        cpu_base, roofline = None, None
+        if args.full:  # the legs that need runs of their own: roofline (live counters), CPU baseline
+            launches_trace = args.steps * max(1, (s["launches"] // 2) // args.steps)
+            trace_ms_per_launch = s["trace_kernel_ms"] / launches_trace
+            per_path, counts = None, None
+            if world == 1 and not args.no_cpu_baseline:
+                cpu_base, per_path, counts = cpu_leg(scene, env, W, H, args.bounces, log)
+            committed = None
+            if std_cfg and os.path.exists(PMC_FILE):
+                with open(PMC_FILE) as f:
+                    committed = json.load(f)
+            if per_path is None and committed is not None:
+                per_path = committed.get("algorithmic_bytes_per_path")
+            if counts is None and committed is not None and (committed.get("algorithmic_counts_1spp") or {}).get("f32_ops"):
+                counts = committed["algorithmic_counts_1spp"]  # (a property of the workload and of the reference's algorithm, not of the kernel)
+            if pmc is not None and pmc["build_id"] != build_id:
+                log("pmc: the child ran build %s, this process %s: counters dropped" % (pmc["build_id"], build_id))
+                pmc = None
+            if pmc is None and world == 1 and committed is not None:
+                if committed.get("build_id") == build_id:
+                    pmc = {k: committed[k] for k in ("counters", "resolve", "kernel", "build_id", "launch_ms_under_pmc")}
+                    pmc["source"] = "committed: profiles/pmc_house_1080p_8b.json (same rsrt_build_id as this library)"
+                else:
+                    log("pmc: profiles/pmc_house_1080p_8b.json was taken on build %s, this library is %s: not attached" % (committed.get("build_id"), build_id))
+            paths_per_launch = s["paths"] / launches_trace  # this rank's kernel
+            owned_pixels = int(partition.owned_mask(W, H, rank, world).sum())
+            roofline = roofline_object(pmc if world == 1 else None, build_id, trace_ms_per_launch, paths_per_launch, per_path, owned_pixels, spp,
+                                       counts)
+            if world > 1:
+                roofline["note"] = "per-kernel counters are collected at N = 1 only; this object carries the launch time and the algorithmic bytes of rank 0's share"
+            if args.write_profile and std_cfg and world == 1 and pmc is not None and str(pmc.get("source", "")).startswith("live"):
+                os.makedirs(os.path.dirname(PMC_FILE), exist_ok=True)
+                with open(PMC_FILE, "w") as f:
+                    json.dump({"workload": "house.toml 1920x1080 256 spp 8 bounces, one frame per PMC pass", "build_id": build_id, "kernel": pmc["kernel"],
+                               "launch_ms_under_pmc": pmc["launch_ms_under_pmc"], "counters": pmc["counters"], "resolve": pmc["resolve"],
+                               "algorithmic_bytes_per_path": per_path, "algorithmic_counts_1spp": counts,
+                               "passes": PMC_PASSES, "source": "bench.py --write-profile (rocprofv3 --kernel-trace --pmc, separate passes)"}, f, indent=1)
         metric = "Mrays/s, house.toml 1920x1080 256spp 8-bounce" if std_cfg else \
             "Mrays/s, %s %dx%d %dspp %d-bounce" % (os.path.basename(args.scene), W, H, spp, args.bounces)
         result = {"metric": metric, "value": value, "unit": "Mrays/s",
@@ -783,8 +843,9 @@ def main():
                              "rays_per_frame": rays_total / args.steps, "paths_per_frame": paths_total / args.steps},
                   "ms_per_frame": elapsed / args.steps * 1e3,
                   "kernel_ms_per_frame": {"trace": float(tmax[1].item()) / args.steps, "resolve": s["resolve_kernel_ms"] / args.steps,
-                                          "reduce": float(tmax[2].item()) / args.steps},
-                  "roofline": roofline, "cpu_baseline": cpu_base}
+                                          "reduce": float(tmax[2].item()) / args.steps}}
+        if args.full:
+            result.update({"roofline": roofline, "cpu_baseline": cpu_base})
         if world > 1:
             result["frame_equals_1gpu"] = proof["frame_equals_1gpu"]
             result["multi_gpu"] = {"collective": collective, "exchange": exchange_used, "pre_flight": exchange_log, "collective_note": {"rccl": "librsrt rsrt_comm_reduce: grouped ncclSend / ncclRecv gather of compact tile buffers (RSRT_COMM_MODE=reduce: dense ncclReduce)",
@@ -793,7 +854,7 @@ def main():
                                    "comm_mode_env": os.environ.get("RSRT_COMM_MODE", ""), "per_rank": per_rank, "proof": proof,
                                    "proof_how": "rank 0 rendered the whole frame alone (partition 0 of 1, second buffer) before the timed region; every candidate exchange "
                                                 "had to reproduce it (pre_flight), the last timed frame is compared again; uint32 views"}
-        elif std_cfg and not args.no_extra_configs:
+        elif args.full and std_cfg and not args.no_extra_configs:
             result["extra_configs"] = extra_configs(env, device_index, log)
     state.close()
     if world > 1:

@@ -50,6 +50,8 @@ def _run(cmd):
 
 def build_host(force=False):
     srcs = [os.path.join(CSRC, s) for s in HOST_SOURCES if os.path.exists(os.path.join(CSRC, s))]
+    if not force and not _newer(HOST_LIB, _deps("host")):
+        return HOST_LIB  # up to date: no lock (a user who cannot write the lock file still loads what build() made)
     with _locked():
         if force or _newer(HOST_LIB, _deps("host")):
             tmp = HOST_LIB + ".tmp%d" % os.getpid()
@@ -100,6 +102,8 @@ def build_hip(force=False, extra_flags=(), instrument=False):
         target = target.replace(".so", "_exp_%s.so" % hashlib.sha256(" ".join(knobs).encode()).hexdigest()[:10])
     sid = source_id() + ("+" + "+".join(k[2:] if k.startswith("-D") else k.lstrip("-") for k in knobs) if knobs else "") + ("+instr" if instrument else "")
     flags.append('-DRSRT_BUILD_ID="%s"' % sid)
+    if not force and not _newer(target, _deps("hip")):
+        return target  # up to date: no lock (libraries are replaced atomically, so reading one needs none)
     with _locked():
         if force or _newer(target, _deps("hip")):
             tmp = target + ".tmp%d" % os.getpid()

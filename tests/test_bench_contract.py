@@ -166,3 +166,25 @@ def test_overhead_ledger_adds_up_to_the_counters():
     assert a["product"]["lane_instructions_per_ray"] > a["b93b1a04be"]["lane_instructions_per_ray"] > a["402bff4434"]["lane_instructions_per_ray"]
     ro = bench.roofline_object(None, "0123456789abcdef", 98.0, 1920 * 1080 * 256, 3450.0, 1920 * 1080, 256, house_counts())
     assert abs(sum(ro["overhead_ledger"]["share"].values()) - 1.0) < 1e-9 and "declared done" in ro["overhead_ledger"]["reading"]
+
+
+def test_dump_outputs_writes_the_last_frame_or_a_fixed_sample_of_it(tmp_path, monkeypatch):
+    """--dump-outputs DIR: the frame as float32 DIR/frame.npy; above the size limit a sample of its pixels drawn by a seeded generator, so
+    that two runs (two builds) write the same pixels."""
+    import numpy as np
+    frame = np.arange(3 * 5 * 4, dtype=np.float32).reshape(3, 5, 4)
+    assert bench.dump_outputs(str(tmp_path / "whole"), frame) == ["frame"]
+    back = np.load(tmp_path / "whole" / "frame.npy")
+    assert back.dtype == np.float32 and np.array_equal(back, frame)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_PIXELS", 6)
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("sample%d" % k)
+        assert bench.dump_outputs(str(d), frame) == ["frame_sample", "frame_sample_pixels"]
+        vals, idx = np.load(d / "frame_sample.npy"), np.load(d / "frame_sample_pixels.npy")
+        assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == (6, 4)
+        assert np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < 15
+        assert np.array_equal(vals, frame.reshape(-1, 4)[idx.astype(np.int64)])
+        runs.append(idx)
+    assert np.array_equal(runs[0], runs[1])

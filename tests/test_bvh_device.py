@@ -4,7 +4,6 @@
 same depth.  The CPU part checks the closed form of the reference's unstable two-pointer partition that the device
 builder rests on."""
 import random
-import sys
 
 import numpy as np
 import pytest
@@ -65,12 +64,10 @@ def same_tree(a, b):
 
 
 @pytest.mark.gpu
-def test_device_builder_equals_the_host_builder_node_for_node():
-    sys.path.insert(0, util.ROOT + "/tools")
-    import make_big_scene
+def test_device_builder_equals_the_host_builder_node_for_node(tmp_path):
     st = R.State.new(R.Scene.load_toml(util.scene_path("default")), util.small_env(), 16, 16)
     report = []
-    for name in ["house", "default", "cube", "spheres_only", "suzanne", make_big_scene.make(4)]:
+    for name in ["house", "default", "cube", "spheres_only", "suzanne", util.big_scene(tmp_path, 4)]:
         sc = R.Scene.load_toml(name if name.endswith(".toml") else util.scene_path(name))
         ref = host.build_bvh(sc.spheres, sc.plane_descs, sc.vertices, sc.triangles)
         assert util.fields_equal(ref[0], sc.primitives) and util.fields_equal(ref[1], sc.bvh_nodes)

@@ -680,13 +680,10 @@ def test_mid_size_scene_with_nodes_in_lds_or_in_global_memory(hybrid, traversal,
     assert (st["ext_rays"], st["shadow_rays"]) == (ost["ext_rays"], ost["shadow_rays"])
 
 
-def test_big_scene_all_global_is_bit_exact(big_env):
+def test_big_scene_all_global_is_bit_exact(big_env, tmp_path):
     """The builder-authored suzanne grid (tools/make_big_scene.py: 15,488 triangles, ~8.7 k nodes): nothing of it fits
     the LDS budget, so the fixed-order walk reads nodes and records from global memory.  Reduced size, bit for bit."""
-    import sys
-    sys.path.insert(0, util.ROOT + "/tools")
-    import make_big_scene
-    sc = R.Scene.load_toml(make_big_scene.make(4))
+    sc = R.Scene.load_toml(util.big_scene(tmp_path, 4))
     assert len(sc.triangles) == 15488 and len(sc.bvh_nodes) > 8000
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 200, 112, 0, 3, 10, fast=True)
     img, st = gpu_render(sc, big_env, 200, 112, 0, 3, 10)
@@ -742,22 +739,19 @@ def test_wide_walk_stack_overflow_on_a_chain_tree(levels, budget, hybrid, kernel
 
 
 @pytest.mark.parametrize("budget", ["", "1", "coop"])
-def test_scene_with_a_deep_tree_takes_the_wide_walk(budget, big_env, monkeypatch):
+def test_scene_with_a_deep_tree_takes_the_wide_walk(budget, big_env, monkeypatch, tmp_path):
     """suzanne on an 8 x 8 grid (61,952 triangles, binary depth 19): the wide tree has eleven levels, more than the walk's eight stack
     registers can always serve, so the scene runs the kernel variant whose stack may overflow into memory (TRAV 5) — on THIS scene no
     ray ever holds more than eight words (the chain tree above is the test of the overflow itself); what is checked here is that a
     scene of this size takes the wide walk at all (a third of the fixed-order walk's steps), bit for bit against the oracle, also with
     one round per TRACE call (RSRT_TRACE_BUDGET=1), and through the probe, in global memory and with the top of the tree staged in LDS."""
-    import sys
-    sys.path.insert(0, util.ROOT + "/tools")
-    import make_big_scene
     if budget == "coop":  # (the product's choice for this scene since round 4: the cooperative walk, which needs no stack variant)
         monkeypatch.setenv("RSRT_TRAVERSAL", "6")
     else:
         monkeypatch.setenv("RSRT_TRAVERSAL", "5")
         if budget:
             monkeypatch.setenv("RSRT_TRACE_BUDGET", budget)
-    sc = R.Scene.load_toml(make_big_scene.make(8))
+    sc = R.Scene.load_toml(util.big_scene(tmp_path, 8))
     assert len(sc.triangles) == 61952 and sc.bvh_depth >= 18
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 160, 90, 0, 2, 10, fast=True)
     img, st = gpu_render(sc, big_env, 160, 90, 0, 2, 10)
@@ -782,23 +776,20 @@ def test_scene_with_a_deep_tree_takes_the_wide_walk(budget, big_env, monkeypatch
 
 
 @pytest.mark.parametrize("lds_cap,lifo_at,narrow_at", [("320", "", ""), ("320", "3072", ""), ("320", "64", "40"), ("", "", "0"), ("", "0", "")])
-def test_cooperative_walk_spills_and_narrow_trips_do_not_change_the_image(lds_cap, lifo_at, narrow_at, big_env, monkeypatch):
+def test_cooperative_walk_spills_and_narrow_trips_do_not_change_the_image(lds_cap, lifo_at, narrow_at, big_env, monkeypatch, tmp_path):
     """The cooperative walk's node queue (rt_coop.h): with its LDS ring capped at the minimum (RSRT_COOP_LDS_CAP=320) a batch of up to 256 rays
     spills its newest items to the wave's arena block and takes them back — all the more when the wave never turns to newest-first
     (RSRT_COOP_LIFO_AT=3072; 0: it always pops newest first, the first version of the walk); with RSRT_COOP_NARROW_AT small a wave pops ONE
     item a trip whenever more than that many items are outstanding (0: always — a plain depth-first walk of the whole batch).  Which items
     travel together, and in which order, must be invisible: suzanne and the 15 k-triangle grid, reduced frames, bit for bit against the oracle,
     and the probe."""
-    import sys
-    sys.path.insert(0, util.ROOT + "/tools")
-    import make_big_scene
     if lds_cap:
         monkeypatch.setenv("RSRT_COOP_LDS_CAP", lds_cap)
     if lifo_at:
         monkeypatch.setenv("RSRT_COOP_LIFO_AT", lifo_at)
     if narrow_at:
         monkeypatch.setenv("RSRT_COOP_NARROW_AT", narrow_at)
-    for sc, w, h, spp in [(R.Scene.load_toml(util.scene_path("suzanne")), 96, 64, 3), (R.Scene.load_toml(make_big_scene.make(4)), 120, 68, 2)]:
+    for sc, w, h, spp in [(R.Scene.load_toml(util.scene_path("suzanne")), 96, 64, 3), (R.Scene.load_toml(util.big_scene(tmp_path, 4)), 120, 68, 2)]:
         ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), w, h, 0, spp, 10, fast=True)
         img, st = gpu_render(sc, big_env, w, h, 0, spp, 10)
         assert np.array_equal(util.bits(img), util.bits(ref))

@@ -1,5 +1,6 @@
 """Shared helpers of the test-suite: product <-> oracle array views, small environments, metrics."""
 import os
+import sys
 
 import numpy as np
 
@@ -12,6 +13,14 @@ ASSETS = os.path.join(ROOT, "tests", "golden", "assets")
 
 def scene_path(name):
     return os.path.join(ASSETS, "scenes", name + ".toml")
+
+
+def big_scene(out_dir, n=4):
+    """tools/make_big_scene.py's suzanne grid (n x n instances), written into `out_dir` — a test's own tmp_path, never a fixed
+    shared directory that another user or another run may hold."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import make_big_scene
+    return make_big_scene.make(n, str(out_dir))
 
 
 def oracle_scene(scene):

@@ -12,7 +12,7 @@ grid = make_big_scene.make(4)
 rows = []
 for label, scene, w, h, spp, mb in [("suzanne 1280x720 128 spp 10 bounces", "suzanne", 1280, 720, 128, 10),
                                     ("suzanne grid 4x4 (15,488 triangles) 1280x720 32 spp 10 bounces", grid, 1280, 720, 32, 10)]:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--scene", scene,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "3", "--warmup", "1", "--scene", scene,
                         "--width", str(w), "--height", str(h), "--spp", str(spp), "--bounces", str(mb)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:

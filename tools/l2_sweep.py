@@ -48,7 +48,7 @@ if "--build-only" in sys.argv:
 out = []
 for label, flags, renv in ROWS:
     env = dict(os.environ, RSRT_LIB=libs[flags], **renv)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "3", "--warmup", "1"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "3", "--warmup", "1"], env=env,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if r.returncode != 0 or not line:

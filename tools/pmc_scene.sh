@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 case "$7" in *TA_*|*TD_*) echo "pmc_scene.sh: TA_* / TD_* counters hang rocprofv3 on this pool: not run"; exit 2;; esac
 TAG=$1; SCENE=$2; W=$3; H=$4; SPP=$5; MB=$6; EXTRA=$7
 mkdir -p $R/gpurun_out
-RSRT_PMC_EXTRA="$EXTRA" python3 $R/bench.py --no-cpu-baseline --steps 3 --warmup 1 --scene $SCENE --width $W --height $H --spp $SPP --bounces $MB \
+RSRT_PMC_EXTRA="$EXTRA" python3 $R/bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --scene $SCENE --width $W --height $H --spp $SPP --bounces $MB \
   > $R/gpurun_out/pmc_scene_$TAG.json 2> $R/gpurun_out/pmc_scene_$TAG.err || tail -5 $R/gpurun_out/pmc_scene_$TAG.err
 python3 - <<PY
 import json
