@@ -299,6 +299,13 @@ rsrt_status rsrt_get_debug_counters(rsrt_context *ctx, uint64_t out[32]);
 /* ... and the lanes that passed each region mark (rt_math.h RT_MARK; tools/ledger.py sets them against the regions' instruction counts).
  * Read and reset; all zero in the product build. */
 rsrt_status rsrt_get_region_counters(rsrt_context *ctx, uint64_t out[32]);
+/* What the cooperative wide walk (TRAV 6) did, cumulative since context creation, in the product build: out[0] node trips,
+ * [1] leaf trips, [2] 64-item blocks of node items spilled to a wave's arena block, [3] blocks taken back, [4] node trips that
+ * popped the newest items, [5] one-item node trips, [6] batches abandoned to the exact walk because the node ring could not take
+ * a trip's items (the arena block was full), [7] the most node items one wave held outstanding (a maximum, not a sum).  The probe
+ * (rsrt_cast_rays, traversal 6) counts all eight; a render counts only [6] (the counting would cost the render kernel registers it has
+ * not got).  The first min(n, 8) words are written, any beyond are zeroed. */
+rsrt_status rsrt_get_walk_counters(rsrt_context *ctx, uint64_t *out, uint32_t n);
 
 /* Exhaustive device self-test of the numeric contract's one shortcut: the 3-instruction reciprocal used for
  * 1/x (rt_math.h, rt_rcp) against the compiler's correctly rounded division, over all 2^32 f32 bit patterns

@@ -29,7 +29,7 @@
 #include "rt_device.h"
 
 #define RT_BLOCK 256
-#define RT_STATS_WORDS 40 // paths, ext, shadow, traversal steps + 32 diagnostic words (zero in the product build)
+#define RT_STATS_WORDS 48 // paths, ext, shadow, traversal steps + 32 diagnostic words (zero in the product build), 4 spare, the cooperative walk's 8 (rt_coop.h CoopCount)
 #define RT_WAVE 64
 #ifndef RT_WALK_POOL
 #define RT_WALK_POOL 192u // path slots per wave of the 1024-thread walk kernels (hybrid scene view): measured 128 / 160 / 192 (profiles/r03_wide_walk.txt): the
@@ -55,6 +55,7 @@ struct RenderParams {
     uint32_t n_slots; // n_owned_tiles * tile_w * tile_h
     uint32_t trace_budget, descend_quorum, flat_quorum, stop_quorum;
     uint32_t coop_lds_cap, coop_lifo_at, coop_narrow_at; // cooperative walk (rt_coop.h): node-queue entries kept in LDS, outstanding items at which a wave pops newest first / one item a trip
+    uint32_t coop_gcap; // ... node items a wave may spill to its arena block (<= RT_COOP_GCAP)
     uint32_t *cold_state; // wave-pool kernel: global arena of the cold path-state columns
     float *sample_buf;
     unsigned int *work_counter;
@@ -424,7 +425,8 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_kernel(DevScene sc, uin
 template <int SV>
 __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_coop_kernel(DevScene sc, uint32_t n, const float *origins, const float *dirs,
                                                                      uint32_t mode, uint32_t flags, uint32_t repeat, rsrt_hit *out, uint32_t *gstack,
-                                                                     uint32_t lds_cap, uint32_t lifo_at, uint32_t narrow_at)
+                                                                     uint32_t lds_cap, uint32_t lifo_at, uint32_t narrow_at, uint32_t gcap,
+                                                                     unsigned long long *stats)
 {
     if (SV != 0) stage_scene_lds(sc);
     const typename PoolView<SV>::type S = PoolView<SV>::make(sc);
@@ -443,6 +445,8 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_coop_kernel(DevScene sc
     Hit h;
     h.t = RT_INFINITY; h.ref = 0; h.src = SRC_BVH; h.u = h.v = 0.0f;
     uint32_t work = 0;
+    CoopCount cc;
+    cc.zero();
     for (uint32_t k = 0; k < repeat; k++) { // (RSRT_PROBE_REPEAT: the same queries again; the result does not change)
         W[C::O + lane] = as_u(o.x); W[C::O + kPool + lane] = as_u(o.y); W[C::O + 2u * kPool + lane] = as_u(o.z);
         W[C::E + lane] = as_u(d.x); W[C::E + kPool + lane] = as_u(d.y); W[C::E + 2u * kPool + lane] = as_u(d.z);
@@ -453,10 +457,11 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_coop_kernel(DevScene sc
         cs.ls = W + C::DWORDS; cs.ns = cs.ls + RT_COOP_LCAP; cs.map = reinterpret_cast<uint16_t *>(cs.ns + RT_COOP_NCAP);
         cs.gs = gstack + (size_t)(blockIdx.x * (RT_BLOCK / RT_WAVE) + wave) * RT_COOP_GCAP;
         cs.ns_h = cs.ns_n = cs.ls_n = cs.gs_n = 0u;
-        cs.lds_cap = lds_cap; cs.lifo_at = lifo_at; cs.narrow_at = narrow_at;
-        coop_push_rays<kPool>(W, cs, valid, lane, W[C::CT + lane], (uint32_t)F_EXT, (uint32_t)F_SHADOW);
-        coop_trace<kPool>(DBG_ARG S, W, cs, false, lane, work);
+        cs.lds_cap = lds_cap; cs.lifo_at = lifo_at; cs.narrow_at = narrow_at; cs.gcap = gcap;
+        coop_push_rays<kPool>(W, cs, cc, valid, lane, W[C::CT + lane], (uint32_t)F_EXT, (uint32_t)F_SHADOW);
+        coop_trace<kPool>(DBG_ARG S, W, cs, cc, false, lane, work);
         RT_WAVE_HANDOVER();
+        if (cs.overflowed() && valid) coop_abandon<kPool>(W, lane, (uint32_t)F_EXT, (uint32_t)F_SHADOW);
         const bool mine[1] = {valid};
         const uint32_t slots[1] = {lane};
         coop_slow_rays<kPool, 1u>(DBG_ARG S, sc, W, mine, slots, false, work);
@@ -464,6 +469,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_coop_kernel(DevScene sc
         h.ref = W[C::BEST + 2u * lane];
         RT_WAVE_HANDOVER();
     }
+    cc.flush(stats, lane);
     if (!valid) return; // (nothing wave-wide from here on)
     if (h.did_hit()) hit_barycentrics(S, h, o, d); // as SHADE does: the traversals do not carry u, v
     if ((mode & 1u) == 0 && !h.did_hit()) { // cast_ray's brute-force fallback (the MISS stage)
@@ -718,6 +724,7 @@ struct rsrt_context {
     int kernel_variant = 4; // index into kVariantPool
     int max_traversal = 6; // most specialised traversal to use where the scene allows it (rt_wavepool.h, TRAV)
     uint32_t coop_lds_cap = RT_COOP_NCAP, coop_lifo_at = RT_COOP_LIFO_AT, coop_narrow_at = RT_COOP_NARROW_AT; // RSRT_COOP_LDS_CAP / _LIFO_AT / _NARROW_AT (tests: force the node queue's spill / newest-first / one-item trips)
+    uint32_t coop_gcap = RT_COOP_GCAP; // RSRT_COOP_GCAP (tests: a small arena block forces the overflow guard, rt_coop.h coop_overflow)
     bool allow_flat = true;
     bool allow_hybrid = true;
     uint32_t trace_budget = 0; // traversal steps per TRACE invocation before a ray is re-queued (0: 6 for the fixed-order walk, 12 for the tree walks)
@@ -1066,6 +1073,7 @@ rsrt_status collect_stats(rsrt_context *ctx)
     memcpy(ctx->debug_words, c + 4, sizeof ctx->debug_words);
     return RSRT_OK;
 }
+static_assert(RT_COOP_STATS + RT_COOP_NSTATS == RT_STATS_WORDS, "the cooperative walk's counters are the last stats words");
 
 
 // Mid-size and big scenes (no whole image in LDS): what the chosen traversal keeps in LDS beside the pools (SceneViewHybrid) — the wide walk
@@ -1274,6 +1282,7 @@ rsrt_status rsrt_context_create(int device_index, rsrt_context **out)
     if (const char *cl = getenv("RSRT_COOP_LDS_CAP")) { int v = atoi(cl); if (v >= (int)RT_COOP_MIN_LDS_CAP && v <= (int)RT_COOP_NCAP) ctx->coop_lds_cap = (uint32_t)v; }
     if (const char *cf = getenv("RSRT_COOP_LIFO_AT")) { int v = atoi(cf); if (v >= 0 && v <= (int)RT_COOP_NARROW_AT) ctx->coop_lifo_at = (uint32_t)v; }
     if (const char *cn = getenv("RSRT_COOP_NARROW_AT")) { int v = atoi(cn); if (v >= 0 && v <= (int)RT_COOP_NARROW_AT) ctx->coop_narrow_at = (uint32_t)v; }
+    if (const char *cg = getenv("RSRT_COOP_GCAP")) { int v = atoi(cg); if (v >= 64 && v <= (int)RT_COOP_GCAP && v % 64 == 0) ctx->coop_gcap = (uint32_t)v; }
     if (const char *cm = getenv("RSRT_COMM_MODE")) ctx->comm_dense_mode = strcmp(cm, "reduce") == 0;
     if (const char *hq = getenv("GPU_MAX_HW_QUEUES")) { int v = atoi(hq); if (v > 0) ctx->hw_queues = v; }
     for (int m = 0; m < 21; m++) (void)hipFuncSetAttribute(probe_function(m / 7, m % 7), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -2128,6 +2137,7 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
     P.coop_lds_cap = ctx->coop_lds_cap;
     P.coop_lifo_at = ctx->coop_lifo_at;
     P.coop_narrow_at = ctx->coop_narrow_at;
+    P.coop_gcap = ctx->coop_gcap;
     // a small job behind a kernel that is still running: the 256-thread form, one workgroup per CU, on one of four lanes (see Lane)
     bool pipelined = false;
     if (ctx->overlap && kv == 4 && sv == 1 && trav != 6 && (uint64_t)P.n_slots * sample_count <= ctx->small_paths && sample_count <= pass_samples)
@@ -2272,6 +2282,20 @@ rsrt_status rsrt_get_debug_counters(rsrt_context *ctx, uint64_t out[32])
     return RSRT_OK;
 }
 
+// The cooperative walk's counters (rt_coop.h CoopCount), cumulative since the context was created; read on their own, so that the
+// rsrt_get_stats window is not touched.
+rsrt_status rsrt_get_walk_counters(rsrt_context *ctx, uint64_t *out, uint32_t n)
+{
+    if (!ctx || (!out && n != 0)) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    unsigned long long c[RT_COOP_NSTATS];
+    HIP_TRY(ctx, hipMemcpy(c, ctx->dev_stats + RT_COOP_STATS, sizeof c, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < n && i < RT_COOP_NSTATS; i++) out[i] = c[i];
+    for (uint32_t i = RT_COOP_NSTATS; i < n; i++) out[i] = 0;
+    return RSRT_OK;
+}
+
 rsrt_status rsrt_get_region_counters(rsrt_context *ctx, uint64_t out[32])
 {
     if (!ctx || !out) return RSRT_ERR_INVALID_ARGUMENT;
@@ -2337,7 +2361,8 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
         const size_t smem = (size_t)sc.lds_float4s * sizeof(float4) + (trav == 4 ? (size_t)sc.stack_entries * RT_BLOCK * sizeof(uint32_t) : 0u) + coop_lds; // (only the stack walk has a stack)
         if (smem > 160 * 1024) { (void)hipFree(d_o); (void)hipFree(d_d); (void)hipFree(d_h); (void)hipFree(d_g); return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "cast_rays: needs %zu bytes of LDS", smem); }
         uint32_t repeat = ctx->probe_repeat;
-        void *kargs[] = {&sc, &n, &d_o, &d_d, &mode, &flags, &repeat, &d_h, &d_g, &ctx->coop_lds_cap, &ctx->coop_lifo_at, &ctx->coop_narrow_at}; // (the last three: the cooperative walk's probe only)
+        void *kargs[] = {&sc, &n, &d_o, &d_d, &mode, &flags, &repeat, &d_h, &d_g, &ctx->coop_lds_cap, &ctx->coop_lifo_at, &ctx->coop_narrow_at, &ctx->coop_gcap,
+                         &ctx->dev_stats}; // (from d_g on: the cooperative walk's probe only)
         e = hipLaunchKernel(probe_function(sv, trav), dim3(n_blocks), dim3(RT_BLOCK), kargs, smem, ctx->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);

@@ -32,15 +32,33 @@
 // wave pops the NEWEST 64 instead of the oldest (depth first: the frontier stops growing with the breadth of the tree); what still does not fit
 // the ring is spilled to the wave's arena block, newest 64 items at a time, and comes back when the ring runs low; and should even that block
 // fill up (coop_narrow_at), the wave pops ONE newest item a trip — a plain depth-first walk, which adds at most three items a level — until it
-// has room again (tests/test_gpu_parity.py forces all three).
+// has room again (tests/test_gpu_parity.py forces all three, and checks with the walk's counters that they happened).
+//
+// The bound.  The argument above reads "3 x wide levels" as if the walk were one depth-first stack; it is not: a spill moves the ring's newest
+// 64 items out, the newest-first and one-item trips then pop the newest of what is LEFT, and the spilled items come back only when the ring runs
+// below 64.  So the arena's fill is not bounded by the tree's depth alone, and nothing proves it stays below RT_COOP_GCAP.  Instead of resting on
+// an argument, the two push sites check the PHYSICAL ring: when the new items would not fit RT_COOP_NCAP even after coop_make_room (the arena
+// block is full), nothing is written, the three lists are emptied and the wave abandons the batch (CoopStacks::overflow): the caller flags
+// every ray of it for coop_slow_rays, which walks it again exactly (any CF_OCCLUDED the walk already set was a real hit).  Counted, like the
+// spills, refills, newest-first and one-item trips and the peak of outstanding node items, in CoopCount (rsrt_get_walk_counters).
+// tests/coop_lists.py restates the lists exactly (the probe's counters must equal it, tests/test_gpu_parity.py).  Swept over the knobs
+// (lds_cap 64 / 128 / 320 x lifo_at 0 / 64 / 512 / 3072 x narrow_at 0 / 40 / 3072) on a chain tree of the 25 wide levels build_wide_tree
+// allows, a fan whose every box every ray meets, suzanne and the 4 x 4 grid, for 64-ray probe batches and 128-slot pool batches with both
+// rays, it finds no overflow at the default RT_COOP_GCAP: at most 1719 node items outstanding (the chain, a pool batch, oldest first up to
+// 3072), 1152 with the product's knobs (the fan).  The tests hold the walk to 2048 = RT_COOP_GCAP / 2 outstanding items on those trees and
+// on probe batches of the 62 k-triangle grid; RSRT_COOP_GCAP=128 forces the guard.  The guard sits inside the spill branch (only a spill
+// that could not happen leaves the ring short), so the product's trips pay nothing for it.
 #pragma once
 #include "rt_device.h"
 
 #define RT_COOP_NCAP 320u   // node-queue entries in LDS (a ring): 63 may wait, one node trip adds at most 4 x 64
 #define RT_COOP_MAP 64u     // dwords of the leaf trip's map: 128 records x 16 bits
 #define RT_COOP_LCAP 320u   // leaf-stack entries in LDS: 63 may wait, one node trip adds at most 4 x 64; the pool kernel's compaction list lives here too
-#define RT_COOP_GCAP 4096u  // node items a wave may spill to its arena block
-#define RT_COOP_MIN_LDS_CAP 320u // (run-time cap of the LDS part, tests: 63 + 256 must fit after the spills)
+#define RT_COOP_GCAP 4096u  // node items a wave may spill to its arena block (the allocation; RSRT_COOP_GCAP caps the use below it, tests)
+// The run-time cap of the ring's LDS part (RSRT_COOP_LDS_CAP, tests) may be as low as one block: coop_make_room spills 64 newest items at a time
+// while the new ones would not fit the cap and 64 are there to spill, so after it either the items fit lds_cap <= RT_COOP_NCAP, or ns_n <= 63
+// and 63 + 256 <= RT_COOP_NCAP, or the arena block is full — the one case the ring could overflow, which the push sites catch (coop_overflow)
+#define RT_COOP_MIN_LDS_CAP 64u
 #define RT_COOP_NARROW_AT 3072u  // outstanding node items beyond which a wave pops one item a trip: GCAP - 3072 - 256 - 64 >= 3 x (wide levels <= 25)
 #define RT_COOP_LIFO_AT 512u     // ... beyond which it pops the newest 64 instead of the oldest (0: always — the first version, A/B)
 #ifndef RT_COOP_SLOT_BITS
@@ -88,7 +106,9 @@ struct CoopStacks {
     uint16_t *map;          // the leaf trip's map (LDS, 128 entries): which item, which of its records, each test slot takes
     uint32_t ns_h, ns_n;    // the ring's head (oldest item) and fill
     uint32_t ls_n, gs_n;
-    uint32_t lds_cap, lifo_at, narrow_at;
+    uint32_t lds_cap, lifo_at, narrow_at, gcap; // gcap: node items this wave may spill (a multiple of 64, <= RT_COOP_GCAP)
+    // (ns_h == RT_COOP_NCAP, a head no trip sets, flags an abandoned batch: coop_overflow; ring() stays in range with it)
+    RT_DEV bool overflowed() const { return ns_h == RT_COOP_NCAP; }
     RT_DEV uint32_t ring(uint32_t i) const // the ring's i-th entry, counted from the head (i < 2 * RT_COOP_NCAP - head)
     {
         const uint32_t k = ns_h + i;
@@ -101,26 +121,90 @@ struct CoopStacks {
     }
 };
 
+// What the walk did (rsrt_get_walk_counters): node trips, leaf trips, 64-item blocks spilled to the arena / taken back, node trips that
+// popped the newest items, one-item trips, batches abandoned (coop_overflow), and the most node items outstanding (ring + arena) at the start
+// of a node trip — which is the most after any push, since only a node trip takes node items.  The probe (rt_cast_rays_coop_kernel) counts
+// all of them, wave-uniform in scalar registers, and flushes them once per wave into the stats words from RT_COOP_STATS on.  The render
+// kernel counts only the abandoned batches (CoopNoCount; its TRACE stage adds them): it already spills scalar registers into VGPR lanes,
+// and eight counters live through the trip loop cost it 6 % on suzanne and the grid.
+#define RT_COOP_STATS 40u // first stats word (rsrt_api.hip RT_STATS_WORDS: paths, ext, shadow, steps, 32 diagnostic words, 4 spare)
+#define RT_COOP_NSTATS 8u
+struct CoopCount {
+    uint32_t node_trips, leaf_trips, spills, refills, lifo_trips, narrow_trips, overflows, peak;
+    RT_DEV void zero() { node_trips = leaf_trips = spills = refills = lifo_trips = narrow_trips = overflows = peak = 0u; }
+    RT_DEV void leaf_trip() { leaf_trips++; }
+    RT_DEV void spill() { spills++; }
+    RT_DEV void refill() { refills++; }
+    RT_DEV void overflow() { overflows++; }
+    RT_DEV void node_trip(bool newest, bool narrow, uint32_t n_out)
+    {
+        node_trips++;
+        lifo_trips += newest ? 1u : 0u;
+        narrow_trips += narrow ? 1u : 0u;
+        peak = max(peak, n_out);
+    }
+    RT_DEV void flush(unsigned long long *stats, uint32_t lane) const
+    {
+        if (lane != 0u) return;
+        atomicAdd(&stats[RT_COOP_STATS + 0u], (unsigned long long)node_trips);
+        atomicAdd(&stats[RT_COOP_STATS + 1u], (unsigned long long)leaf_trips);
+        atomicAdd(&stats[RT_COOP_STATS + 2u], (unsigned long long)spills);
+        atomicAdd(&stats[RT_COOP_STATS + 3u], (unsigned long long)refills);
+        atomicAdd(&stats[RT_COOP_STATS + 4u], (unsigned long long)lifo_trips);
+        atomicAdd(&stats[RT_COOP_STATS + 5u], (unsigned long long)narrow_trips);
+        atomicAdd(&stats[RT_COOP_STATS + 6u], (unsigned long long)overflows);
+        atomicMax(&stats[RT_COOP_STATS + 7u], (unsigned long long)peak);
+    }
+};
+struct CoopNoCount { // (the render kernel: nothing in the trip loop)
+    RT_DEV void leaf_trip() {}
+    RT_DEV void spill() {}
+    RT_DEV void refill() {}
+    RT_DEV void overflow() {}
+    RT_DEV void node_trip(bool, bool, uint32_t) {}
+};
+
 // Room for `n_new` (<= 256) more node items in the ring: the newest go to the arena, 64 items at a time.
-RT_DEV void coop_make_room(CoopStacks &st, uint32_t n_new, uint32_t lane)
+template <class Cnt>
+RT_DEV void coop_make_room(CoopStacks &st, Cnt &cc, uint32_t n_new, uint32_t lane)
 {
-    while (st.ns_n + n_new > st.lds_cap && st.ns_n >= 64u && st.gs_n + 64u <= RT_COOP_GCAP) { // (wave-uniform)
+    while (st.ns_n + n_new > st.lds_cap && st.ns_n >= 64u && st.gs_n + 64u <= st.gcap) { // (wave-uniform)
         st.ns_n -= 64u;
         st.gs[st.gs_n + lane] = st.ns[st.ring(st.ns_n + lane)];
         st.gs_n += 64u;
+        cc.spill();
     }
+}
+
+// The ring cannot take the new items (the arena block is full): write nothing, drop every list and give the batch up — the caller sends
+// every ray of it to coop_slow_rays (coop_abandon).  The walk then ends: with the lists empty coop_trace's loop finds nothing to do.
+template <class Cnt>
+RT_DEV void coop_overflow(CoopStacks &st, Cnt &cc)
+{
+    st.ns_h = RT_COOP_NCAP;
+    st.ns_n = st.gs_n = st.ls_n = 0u;
+    cc.overflow();
+}
+
+// After an abandoned batch: the slot's rays that were asked for go to the exact walk (the result cell and the flags are rewritten there).
+template <uint32_t POOL>
+RT_DEV void coop_abandon(uint32_t *W, uint32_t slot, uint32_t f_ext, uint32_t f_shadow)
+{
+    typedef CoopCols<POOL> C;
+    const uint32_t ct = W[C::CT + slot];
+    W[C::CT + slot] = ct | ((ct & f_ext) != 0u ? (uint32_t)CF_SLOW_E : 0u) | ((ct & f_shadow) != 0u ? (uint32_t)CF_SLOW_S : 0u);
 }
 
 // Root items for up to 64 slots (one per lane; `valid` lanes name a slot whose tag word `ct` says which rays to trace: F_EXT 16, F_SHADOW 8).
 // Sets up the result cell and the walk's flags; a ray the walk cannot take is flagged for coop_slow_rays instead of being pushed.
-template <uint32_t POOL>
-RT_DEV void coop_push_rays(uint32_t *W, CoopStacks &st, bool valid, uint32_t slot, uint32_t ct, uint32_t f_ext, uint32_t f_shadow)
+template <uint32_t POOL, class Cnt>
+RT_DEV void coop_push_rays(uint32_t *W, CoopStacks &st, Cnt &cc, bool valid, uint32_t slot, uint32_t ct, uint32_t f_ext, uint32_t f_shadow)
 {
     typedef CoopCols<POOL> C;
     const V3 o = v3(as_f(W[C::O + slot]), as_f(W[C::O + POOL + slot]), as_f(W[C::O + 2u * POOL + slot]));
     const V3 de = v3(as_f(W[C::E + slot]), as_f(W[C::E + POOL + slot]), as_f(W[C::E + 2u * POOL + slot]));
     const V3 ds = v3(as_f(W[C::S + slot]), as_f(W[C::S + POOL + slot]), as_f(W[C::S + 2u * POOL + slot]));
-    if (st.ns_n + 128u > st.lds_cap) coop_make_room(st, 128u, coop_lanes_below(~0ull)); // (pools of more than 128 slots: a third chunk of root items may not fit the ring)
+    if (st.ns_n + 128u > st.lds_cap) coop_make_room(st, cc, 128u, coop_lanes_below(~0ull)); // (pools of more than 128 slots: a third chunk of root items may not fit the ring)
     const bool want_e = valid & ((ct & f_ext) != 0u), want_s = valid & ((ct & f_shadow) != 0u);
     const bool push_e = want_e & coop_ray_ok(o, de), push_s = want_s & coop_ray_ok(o, ds);
     if (valid) {
@@ -131,6 +215,8 @@ RT_DEV void coop_push_rays(uint32_t *W, CoopStacks &st, bool valid, uint32_t slo
         if (want_e) { W[C::BEST + 2u * slot] = 0u; W[C::BEST + 2u * slot + 1u] = as_u(RT_INFINITY); }
     }
     const unsigned long long be = __ballot(push_e), bs = __ballot(push_s);
+    if (st.overflowed()) return; // (an earlier chunk of the batch did not fit: the whole batch goes to the exact walk)
+    if (st.ns_n + 128u > st.lds_cap && st.ns_n + (uint32_t)__popcll(be) + (uint32_t)__popcll(bs) > RT_COOP_NCAP) { coop_overflow(st, cc); return; }
     if (push_e) st.ns[st.ring_new(be)] = slot << RT_COOP_SLOT_SHIFT;
     st.ns_n += (uint32_t)__popcll(be);
     if (push_s) st.ns[st.ring_new(bs)] = (slot << RT_COOP_SLOT_SHIFT) | RT_COOP_KIND;
@@ -196,8 +282,8 @@ RT_DEV void coop_test_records(DBG_DECL const View &S, uint32_t *W, const CoopSta
 }
 
 // Runs the stacks dry.  W: the wave's hot columns (CoopCols<POOL>); `work` += node items + records tested by this lane.
-template <uint32_t POOL, class View>
-RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, bool anyhit_shadow, uint32_t lane, uint32_t &work)
+template <uint32_t POOL, class View, class Cnt>
+RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, Cnt &cc, bool anyhit_shadow, uint32_t lane, uint32_t &work)
 {
     typedef CoopCols<POOL> C;
 #ifdef RT_INSTRUMENT // (diagnostic build: wave time of the node trips / of the leaf trips, counters 25 / 26)
@@ -219,6 +305,7 @@ RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, bool
             // place in a dense sequence of records, the items whose records end within the first 128 are taken — a run from the top of the
             // stack, the rest stays — and each writes "record j of the item lane i popped" into the map at its places.  Then lane p tests
             // record p (and p + 64): whichever item it belongs to, whichever ray.
+            cc.leaf_trip();
             DBG_WAVE_TICK(14); // (diagnostic build: 14 / 28 leaf trips and their items, 12 / 13 test passes and records, 10 / 11 node trips and items)
             const uint32_t n_take = min(st.ls_n, 64u), top = st.ls_n - 1u;
             const bool act0 = lane < n_take;
@@ -257,6 +344,7 @@ RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, bool
             st.gs_n -= 64u;
             st.ns[st.ring(st.ns_n + lane)] = st.gs[st.gs_n + lane];
             st.ns_n += 64u;
+            cc.refill();
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -264,10 +352,12 @@ RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, bool
         if (st.ns_n == 0u) break; // both stacks empty, nothing spilled: every ray of the batch is done
         DBG_WAVE_TICK(10);
         const uint32_t n_out = st.ns_n + st.gs_n;
-        const uint32_t n_take = n_out > st.narrow_at ? 1u : min(st.ns_n, 64u);
+        const bool narrow = n_out > st.narrow_at, newest = narrow | (n_out > st.lifo_at); // (one-item trips are depth first too: the newest item)
+        const uint32_t n_take = narrow ? 1u : min(st.ns_n, 64u);
         const bool act0 = lane < n_take;
+        cc.node_trip(newest, narrow, n_out);
         uint32_t item;
-        if (n_out > st.lifo_at) { // (wave-uniform) the newest: depth first
+        if (newest) { // (wave-uniform) the newest: depth first
             item = st.ns[st.ring(act0 ? st.ns_n - 1u - lane : 0u)];
         } else { // the oldest
             item = st.ns[st.ring(act0 ? lane : 0u)];
@@ -310,7 +400,13 @@ RT_DEV void coop_trace(DBG_DECL const View &S, uint32_t *W, CoopStacks &st, bool
             bi[k] = __ballot(((im >> k) & 1u) != 0u);
             n_new += (uint32_t)__popcll(bi[k]);
         }
-        if (st.ns_n + n_new > st.lds_cap) coop_make_room(st, n_new, lane);
+        if (st.ns_n + n_new > st.lds_cap) {
+            coop_make_room(st, cc, n_new, lane);
+            if (st.ns_n + n_new > RT_COOP_NCAP) { // the ring cannot take them (the arena block is full): the batch goes to the exact walk
+                coop_overflow(st, cc);
+                continue;
+            }
+        }
         // (each slot's push behind a wave-uniform test: near the root no lane has a leaf in any slot, near the leaves few have interior
         // children in the later slots — the slot's prefix count, item and address are then never formed)
 #pragma unroll

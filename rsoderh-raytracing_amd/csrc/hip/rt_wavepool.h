@@ -367,19 +367,25 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 cs.ns = list + L::kListDwords; cs.ls = list; cs.gs = G + L::kColdColumns * POOL;
                 cs.map = reinterpret_cast<uint16_t *>(cs.ns + RT_COOP_NCAP);
                 cs.ns_h = cs.ns_n = cs.ls_n = cs.gs_n = 0u;
-                cs.lds_cap = P.coop_lds_cap; cs.lifo_at = P.coop_lifo_at; cs.narrow_at = P.coop_narrow_at;
+                cs.lds_cap = P.coop_lds_cap; cs.lifo_at = P.coop_lifo_at; cs.narrow_at = P.coop_narrow_at; cs.gcap = P.coop_gcap;
+                CoopNoCount coop_cc; // (the render kernel counts only abandoned batches, below: rt_coop.h CoopCount)
                 for (uint32_t i0 = 0; i0 < best_n; i0 += 64u) { // (the list is read to the end before the first leaf item lands in the same words)
                     const bool valid = i0 + lane < best_n;
                     const uint32_t s = list[valid ? i0 + lane : 0u];
-                    coop_push_rays<POOL>(W, cs, valid, s, CT_OF(s), (uint32_t)F_EXT, (uint32_t)F_SHADOW);
+                    coop_push_rays<POOL>(W, cs, coop_cc, valid, s, CT_OF(s), (uint32_t)F_EXT, (uint32_t)F_SHADOW);
                 }
-                coop_trace<POOL>(DBG_ARG S, W, cs, anyhit_shadow, lane, n_work);
+                coop_trace<POOL>(DBG_ARG S, W, cs, coop_cc, anyhit_shadow, lane, n_work);
                 RT_WAVE_HANDOVER();
                 // what each slot is left as (the census's tags are still good: nothing else ran).  First the rays the walk handed to the exact
-                // fixed-order walk: a non-finite 1/d, two records at the same closest t (next to none)
+                // fixed-order walk: a non-finite 1/d, two records at the same closest t (next to none), every ray of an abandoned batch
                 uint32_t my_slot[L::kSlotsPerLane];
                 bool mine[L::kSlotsPerLane];
                 for (uint32_t k = 0; k < L::kSlotsPerLane; k++) { my_slot[k] = lane + 64u * k; mine[k] = tags[k] == (uint32_t)TAG_TRACE; }
+                if (cs.overflowed()) {
+                    if (lane == 0u) atomicAdd(&P.stats[RT_COOP_STATS + 6u], 1ull);
+                    for (uint32_t k = 0; k < L::kSlotsPerLane; k++)
+                        if (mine[k]) coop_abandon<POOL>(W, my_slot[k], (uint32_t)F_EXT, (uint32_t)F_SHADOW);
+                }
                 coop_slow_rays<POOL, L::kSlotsPerLane>(DBG_ARG S, sc, W, mine, my_slot, anyhit_shadow, n_work);
                 for (uint32_t k = 0; k < L::kSlotsPerLane; k++) {
                     if (!mine[k]) continue;

@@ -17,12 +17,14 @@ import numpy as np
 from . import _build, types as T
 
 FLAG_REFERENCE_TRAVERSAL = 1  # shadow query runs to the end too (literal shader.wgsl:1249)
+# rsrt_get_walk_counters, in order (rt_coop.h CoopCount)
+WALK_COUNTERS = ("node_trips", "leaf_trips", "spills", "refills", "lifo_trips", "narrow_trips", "overflows", "peak")
 FLAG_PRUNE = 2                # opt-in t-pruning; NOT exactly result-preserving (include/rsrt.h)
 
 _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "rsrt_upload_scene",
             "rsrt_upload_environment", "rsrt_set_partition", "rsrt_accumulator_resize", "rsrt_accumulator_bind",
             "rsrt_accumulator_clear", "rsrt_accumulator_download", "rsrt_resolve_mean_f16", "rsrt_debug_view_f16", "rsrt_render",
-            "rsrt_synchronize", "rsrt_get_stats", "rsrt_cast_rays", "rsrt_describe", "rsrt_get_debug_counters", "rsrt_get_region_counters", "rsrt_display_srgb8",
+            "rsrt_synchronize", "rsrt_get_stats", "rsrt_cast_rays", "rsrt_describe", "rsrt_get_debug_counters", "rsrt_get_region_counters", "rsrt_get_walk_counters", "rsrt_display_srgb8",
             "rsrt_selftest_numerics", "rsrt_build_id", "rsrt_wide_tree_build", "rsrt_build_bvh_device",
             "rsrt_partition_owner", "rsrt_partition_mask", "rsrt_partition_tiles", "rsrt_comm_available", "rsrt_comm_unique_id", "rsrt_comm_init", "rsrt_comm_reduce", "rsrt_comm_set_mode", "rsrt_comm_destroy",
             "rsrt_multi_create", "rsrt_multi_destroy", "rsrt_multi_last_error", "rsrt_multi_size", "rsrt_multi_context",
@@ -87,6 +89,7 @@ def lib():
         L.rsrt_get_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_get_debug_counters.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_get_region_counters.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsrt_get_walk_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rsrt_selftest_numerics.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_cast_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_partition_owner.restype = C.c_uint32
@@ -319,6 +322,13 @@ class State:
         out = np.zeros(32, np.uint64)
         self._check(self._L.rsrt_get_region_counters(self._ctx, _p(out)), "rsrt_get_region_counters")
         return out
+
+    def walk_counters(self):
+        """The cooperative walk's counters since the context was created (rsrt_get_walk_counters): a dict of WALK_COUNTERS; 'peak' is a
+        maximum, the others are sums.  The probe (cast_rays, traversal 6) counts all of them, a render only 'overflows'."""
+        out = np.zeros(len(WALK_COUNTERS), np.uint64)
+        self._check(self._L.rsrt_get_walk_counters(self._ctx, _p(out), len(out)), "rsrt_get_walk_counters")
+        return {k: int(v) for k, v in zip(WALK_COUNTERS, out)}
 
     def selftest_numerics(self):
         """Exhaustive device check of the short reciprocal (all 2^32 inputs): dict of the four words of rsrt_selftest_numerics."""

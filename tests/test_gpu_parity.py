@@ -8,6 +8,7 @@ import os
 import numpy as np
 import pytest
 
+import coop_lists as M
 import oracle
 import util
 import rsoderh_raytracing_amd as R
@@ -31,6 +32,17 @@ def golden_env():
 @pytest.fixture(scope="module")
 def big_env():
     return R.Environment.synthetic(2048, 1024)
+
+
+def gpu_render_walk(scene, env, w, h, begin, count, mb):
+    """gpu_render, and the cooperative walk's counters of the render (a fresh context: its counters start at zero; a render counts only the
+    batches it abandoned to the exact walk, rt_coop.h CoopCount — the probe counts everything)."""
+    st = R.State.new(scene, env, w, h)
+    st.max_bounces = mb
+    st.render_range(begin, count)
+    img, stats, walk = st.download(), st.stats(), st.walk_counters()
+    st.close()
+    return img, stats, walk
 
 
 def gpu_render(scene, env, w, h, begin, count, mb, flags=0, partition_args=None):
@@ -754,7 +766,9 @@ def test_scene_with_a_deep_tree_takes_the_wide_walk(budget, big_env, monkeypatch
     sc = R.Scene.load_toml(util.big_scene(tmp_path, 8))
     assert len(sc.triangles) == 61952 and sc.bvh_depth >= 18
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 160, 90, 0, 2, 10, fast=True)
-    img, st = gpu_render(sc, big_env, 160, 90, 0, 2, 10)
+    img, st, walk = gpu_render_walk(sc, big_env, 160, 90, 0, 2, 10)
+    if budget == "coop":  # the real scene's batches never overflow the ring
+        assert walk["overflows"] == 0, walk
     assert np.array_equal(util.bits(img), util.bits(ref))
     assert (st["ext_rays"], st["shadow_rays"]) == (ost["ext_rays"], ost["shadow_rays"])
     wide_steps = st["traversal_steps"] / (st["ext_rays"] + st["shadow_rays"])
@@ -772,17 +786,23 @@ def test_scene_with_a_deep_tree_takes_the_wide_walk(budget, big_env, monkeypatch
         for mode in (4 << 1, 5 << 1, (5 << 1) | 16, 6 << 1, (6 << 1) | 16):
             got = s2.cast_rays(o, d, mode, 0)
             assert np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1, 9), hits.view(np.uint32).reshape(-1, 9)), mode
+        walk = s2.walk_counters()
         s2.close()
+        if budget == "coop":  # the probe's batches of this scene: no overflow, and the peak within the bound rt_coop.h states
+            print("62 k-triangle grid, probe through the cooperative walk:", walk)
+            assert walk["node_trips"] > 0 and walk["overflows"] == 0 and walk["peak"] <= M.PEAK_BOUND, walk
 
 
-@pytest.mark.parametrize("lds_cap,lifo_at,narrow_at", [("320", "", ""), ("320", "3072", ""), ("320", "64", "40"), ("", "", "0"), ("", "0", "")])
+@pytest.mark.parametrize("lds_cap,lifo_at,narrow_at", [("320", "", ""), ("320", "3072", ""), ("320", "64", "40"), ("", "", "0"), ("", "0", ""),
+                                                      ("64", "", ""), ("320", "3072", "0")])
 def test_cooperative_walk_spills_and_narrow_trips_do_not_change_the_image(lds_cap, lifo_at, narrow_at, big_env, monkeypatch, tmp_path):
     """The cooperative walk's node queue (rt_coop.h): with its LDS ring capped at the minimum (RSRT_COOP_LDS_CAP=320) a batch of up to 256 rays
     spills its newest items to the wave's arena block and takes them back — all the more when the wave never turns to newest-first
     (RSRT_COOP_LIFO_AT=3072; 0: it always pops newest first, the first version of the walk); with RSRT_COOP_NARROW_AT small a wave pops ONE
     item a trip whenever more than that many items are outstanding (0: always — a plain depth-first walk of the whole batch).  Which items
     travel together, and in which order, must be invisible: suzanne and the 15 k-triangle grid, reduced frames, bit for bit against the oracle,
-    and the probe."""
+    and the probe.  RSRT_COOP_LDS_CAP=64 caps the ring at one block (320 is the default).  No render abandons a batch; and the walk's counters
+    (rsrt_get_walk_counters) of the fan's probe batches — equal to tests/coop_lists.py's — prove that each case does what it names."""
     if lds_cap:
         monkeypatch.setenv("RSRT_COOP_LDS_CAP", lds_cap)
     if lifo_at:
@@ -791,9 +811,10 @@ def test_cooperative_walk_spills_and_narrow_trips_do_not_change_the_image(lds_ca
         monkeypatch.setenv("RSRT_COOP_NARROW_AT", narrow_at)
     for sc, w, h, spp in [(R.Scene.load_toml(util.scene_path("suzanne")), 96, 64, 3), (R.Scene.load_toml(util.big_scene(tmp_path, 4)), 120, 68, 2)]:
         ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), w, h, 0, spp, 10, fast=True)
-        img, st = gpu_render(sc, big_env, w, h, 0, spp, 10)
+        img, st, walk = gpu_render_walk(sc, big_env, w, h, 0, spp, 10)
         assert np.array_equal(util.bits(img), util.bits(ref))
         assert (st["ext_rays"], st["shadow_rays"]) == (ost["ext_rays"], ost["shadow_rays"])
+        assert walk["overflows"] == 0, walk
         rng = np.random.default_rng(8)
         o = rng.uniform(-6, 6, (2048, 3)).astype(np.float32) + np.float32([0, 2, 2])
         d = rng.normal(size=(2048, 3)).astype(np.float32)
@@ -804,6 +825,33 @@ def test_cooperative_walk_spills_and_narrow_trips_do_not_change_the_image(lds_ca
             got = s2.cast_rays(o, d, mode, 0)
             assert np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1, 9), hits.view(np.uint32).reshape(-1, 9)), mode
         s2.close()
+    # the fan (util.fan_scene): every probe ray meets every box, so each mechanism has work to do
+    from test_wide_tree import wide_tree
+    sc = util.fan_scene(M.FAN_QUADS)
+    wn, _ = wide_tree(sc)
+    o, d = M.batch_rays("along", wn, 192, 11)
+    knobs = {k: int(v) for k, v in (("lds_cap", lds_cap), ("lifo_at", lifo_at), ("narrow_at", narrow_at)) if v}
+    want, _ = M.probe(M.Tree(wn), o, d, **knobs)
+    s2 = R.State.new(sc, util.small_env(), 16, 16)
+    got = s2.cast_rays(o, d, 6 << 1, 0)
+    walk = s2.walk_counters()
+    s2.close()
+    assert np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1, 9), oracle.cast_rays(util.oracle_scene(sc), o, d, 0, 0).view(np.uint32).reshape(-1, 9))
+    print("fan probe,", (lds_cap, lifo_at, narrow_at), walk)
+    assert walk == want, (walk, want)
+    assert walk["node_trips"] > 0 and walk["overflows"] == 0 and walk["spills"] == walk["refills"], walk
+    if narrow_at == "":
+        assert walk["spills"] > 0, walk  # (the fan's batches outgrow the ring: spilled and taken back)
+    if narrow_at == "0":  # one item a trip, always, and always the newest (also with RSRT_COOP_LIFO_AT=3072)
+        assert walk["narrow_trips"] == walk["lifo_trips"] == walk["node_trips"], walk
+    if narrow_at == "40":
+        assert 0 < walk["narrow_trips"] <= walk["lifo_trips"], walk
+    if lifo_at == "0":
+        assert walk["lifo_trips"] == walk["node_trips"], walk
+    if lifo_at == "3072" and narrow_at == "":  # oldest first throughout: nothing outgrows the threshold
+        assert walk["lifo_trips"] == 0, walk
+    if lds_cap == "" and lifo_at == "" and narrow_at == "" or (lds_cap, lifo_at, narrow_at) == ("320", "", ""):
+        assert walk["lifo_trips"] > 0 and walk["narrow_trips"] == 0, walk  # the product's knobs: newest first beyond 512, never one-item trips
 
 
 def _merge_sibling_leaves(nodes, limit=8):
@@ -896,3 +944,84 @@ def test_two_pipelines_that_share_only_the_asset_files(name, w, h, spp, mb):
     st.close()
     assert np.array_equal(util.bits(img), util.bits(ref))
     assert (g["paths"], g["ext_rays"], g["shadow_rays"]) == (ost["paths"], ost["ext_rays"], ost["shadow_rays"])
+
+
+PROBE_KNOBS = [{}, dict(lds_cap=64, lifo_at=3072, narrow_at=3072), dict(lds_cap=320, lifo_at=64, narrow_at=40), dict(lds_cap=128, lifo_at=0, narrow_at=0),
+               dict(lds_cap=64, lifo_at=3072, narrow_at=40)]
+
+
+def _coop_scene(name, tmp_path):
+    if name == "deck":
+        return util.deck_scene(M.DECK_LEVELS), "along"
+    if name == "fan":
+        return util.fan_scene(M.FAN_QUADS), "along"
+    if name == "grid":
+        return R.Scene.load_toml(util.big_scene(tmp_path, 4)), "aim"
+    return R.Scene.load_toml(util.scene_path(name)), "aim"
+
+
+def _knob_env(monkeypatch, knobs):
+    for key, env in (("lds_cap", "RSRT_COOP_LDS_CAP"), ("lifo_at", "RSRT_COOP_LIFO_AT"), ("narrow_at", "RSRT_COOP_NARROW_AT"), ("gcap", "RSRT_COOP_GCAP")):
+        if key in knobs:
+            monkeypatch.setenv(env, str(knobs[key]))
+        else:
+            monkeypatch.delenv(env, raising=False)
+
+
+@pytest.mark.parametrize("name", ["deck", "fan", "suzanne", "grid"])
+def test_probe_walk_counters_equal_the_lists_model(name, monkeypatch, tmp_path):
+    """The cooperative walk's bookkeeping, observed: the probe (rsrt_cast_rays, traversal 6) runs fixed batches — 64 rays a wave, by index —
+    so its counters (node and leaf trips, spills, refills, newest-first and one-item trips, overflows, the peak of outstanding node items)
+    must equal those of tests/coop_lists.py's exact restatement of rt_coop.h, for the deepest chain, the fan, suzanne and the grid, under the
+    default knobs and four forced ones.  A slip in the list discipline that the images cannot see (the wrong block spilled, a lost refill, an
+    off-by-one in the ring) changes these counts.  The hits are the oracle's, bit for bit."""
+    monkeypatch.delenv("RSRT_PROBE_REPEAT", raising=False)
+    sc, kind = _coop_scene(name, tmp_path)
+    from test_wide_tree import wide_tree
+    wn, _ = wide_tree(sc)
+    tree = M.Tree(wn)
+    o, d = M.batch_rays(kind, wn, 192, 11)
+    hits = oracle.cast_rays(util.oracle_scene(sc), o, d, 0, 0)
+    for knobs in PROBE_KNOBS:
+        _knob_env(monkeypatch, knobs)
+        want, _ = M.probe(tree, o, d, **knobs)
+        for mode in (6 << 1,) + (((6 << 1) | 16,) if kind == "aim" else ()):  # (suzanne, the grid: also with the scene read from LDS)
+            s2 = R.State.new(sc, util.small_env(), 16, 16)  # (a fresh context: counters from zero, the peak included)
+            got = s2.cast_rays(o, d, mode, 0)
+            walk = s2.walk_counters()
+            s2.close()
+            assert np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1, 9), hits.view(np.uint32).reshape(-1, 9)), (knobs, mode)
+            assert walk == want, (name, knobs, mode, walk, want)
+            assert walk["overflows"] == 0
+
+
+@pytest.mark.parametrize("name", ["deck", "fan"])
+def test_forced_overflow_is_exact(name, big_env, monkeypatch, tmp_path):
+    """RSRT_COOP_GCAP=128: the wave's arena block takes two spills, the fan's and the chain's batches outgrow the ring, and the overflow
+    guard (rt_coop.h coop_overflow) abandons them to the exact walk — the image and the probe's hits stay the oracle's bit for bit, the ray
+    counts too, and the counters show the guard at work (the probe's equal the model's)."""
+    monkeypatch.setenv("RSRT_TRAVERSAL", "6")
+    monkeypatch.setenv("RSRT_FLAT", "0")
+    _knob_env(monkeypatch, dict(gcap=128))
+    monkeypatch.delenv("RSRT_PROBE_REPEAT", raising=False)
+    sc, kind = _coop_scene(name, tmp_path)
+    ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
+    img, st, walk = gpu_render_walk(sc, big_env, 96, 64, 0, 4, 10)
+    assert np.array_equal(util.bits(img), util.bits(ref))
+    assert (st["ext_rays"], st["shadow_rays"]) == (ost["ext_rays"], ost["shadow_rays"])
+    print(name, "render with RSRT_COOP_GCAP=128:", walk)
+    if name == "fan":  # (the chain's render batches stay small enough; its probe batches below do not)
+        assert walk["overflows"] > 0, walk
+    from test_wide_tree import wide_tree
+    wn, _ = wide_tree(sc)
+    o, d = M.batch_rays(kind, wn, 192, 11)
+    hits = oracle.cast_rays(util.oracle_scene(sc), o, d, 0, 0)
+    want, _ = M.probe(M.Tree(wn), o, d, gcap=128)
+    assert want["overflows"] > 0
+    for mode in (6 << 1,):
+        s2 = R.State.new(sc, util.small_env(), 16, 16)
+        got = s2.cast_rays(o, d, mode, 0)
+        walk = s2.walk_counters()
+        s2.close()
+        assert np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1, 9), hits.view(np.uint32).reshape(-1, 9)), mode
+        assert walk == want, (mode, walk, want)

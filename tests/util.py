@@ -117,3 +117,51 @@ def deck_scene(levels=14):
     cam["pos"], cam["yaw"], cam["pitch"], cam["fov_y"] = (0.15, 0.1, 3.0), 0.03, -0.02, 0.9  # (radians) looking down the deck
     return R.Scene(base.materials, np.zeros(0, T.SPHERE), np.zeros(0, T.PLANE_DESC), vertices, normals, triangles, cam,
                    planes=np.zeros(0, T.PLANE), primitives=prims, bvh_nodes=nodes, bvh_depth=levels + 1)
+
+
+def fan_scene(quads=256):
+    """A hand-built scene whose rays along -z hit EVERY box of the tree: `quads` large squares (two triangles each, one leaf each), all
+    facing the camera at distinct z, under a balanced binary BVH over them in z order — so every box spans the whole square and a ray
+    seen head-on meets every node.  Its wide tree is short and broad: a batch of rays fans out to every node of a level at once, the case
+    that fills the cooperative walk's node queue (tests/coop_lists.py, rt_coop.h).  Boxes nest, records are distinct: it qualifies."""
+    from rsoderh_raytracing_amd import types as T
+    base = R.Scene.load_toml(scene_path("default"))
+    verts, tris = [], []
+    for q in range(quads):
+        z, s = -0.02 * q, 4.0 + 0.001 * q
+        v0 = len(verts)
+        verts += [(-s, -s, z), (s, -s, z), (s, s, z), (-s, s, z)]
+        tris += [(v0, v0 + 1, v0 + 2), (v0, v0 + 2, v0 + 3)]
+    vertices = np.zeros(len(verts), T.VEC3)
+    vertices["v"] = np.asarray(verts, np.float32)
+    normals = np.zeros(1, T.VEC3)
+    normals["v"][0] = (0.0, 0.0, 1.0)
+    triangles = np.zeros(len(tris), T.TRIANGLE)
+    for i, (a, b, c) in enumerate(tris):
+        triangles[i] = (a, b, c, 0, 0, 0, (i // 2) % max(1, len(base.materials)))
+    prims = np.zeros(len(tris), T.PRIMITIVE_INFO)
+    prims["primitive_type"], prims["index"] = 2, np.arange(len(tris))
+    v = vertices["v"]
+    lo_q = np.minimum.reduce([v[0::4], v[1::4], v[2::4], v[3::4]])
+    hi_q = np.maximum.reduce([v[0::4], v[1::4], v[2::4], v[3::4]])
+    nodes = np.zeros(2 * quads - 1, T.BVH_NODE)
+    at = [0]
+
+    def build(a, b):  # quads a..b-1, pre-order: the first child follows its parent, the second's index is stored
+        i = at[0]
+        at[0] += 1
+        nodes[i]["bounds_min"], nodes[i]["bounds_max"] = lo_q[a:b].min(axis=0), hi_q[a:b].max(axis=0)
+        if b - a == 1:
+            nodes[i]["primitives_or_second_child_index"], nodes[i]["primitives_len"] = 2 * a, 2
+            return
+        m = (a + b) // 2
+        build(a, m)
+        nodes[i]["primitives_or_second_child_index"], nodes[i]["primitives_len"], nodes[i]["split_axis"] = at[0], 0, 2
+        build(m, b)
+
+    build(0, quads)
+    assert at[0] == len(nodes)
+    cam = np.zeros(1, T.CAMERA_DESC)
+    cam["pos"], cam["yaw"], cam["pitch"], cam["fov_y"] = (0.15, 0.1, 3.0), 0.03, -0.02, 0.9
+    return R.Scene(base.materials, np.zeros(0, T.SPHERE), np.zeros(0, T.PLANE_DESC), vertices, normals, triangles, cam,
+                   planes=np.zeros(0, T.PLANE), primitives=prims, bvh_nodes=nodes, bvh_depth=int(np.ceil(np.log2(quads))) + 1)
