@@ -260,6 +260,51 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
 rsrt_status rsrt_synchronize(rsrt_context *ctx);
 rsrt_status rsrt_get_stats(rsrt_context *ctx, rsrt_stats *out);
 
+/* -- denoiser: first-hit AOV buffers and an edge-aware a-trous filter (no reference counterpart) --
+ * The reference shows a 1-16 spp image (one sample per displayed frame); these passes turn such an image into a usable picture.
+ * Whole frame only: a context with a partition of world_size > 1 gets RSRT_ERR_INVALID_ARGUMENT.  Nothing here touches the
+ * accumulator or what rsrt_render computes.
+ *
+ * AOV pass.  For every pixel and every sample k in [sample_begin, sample_begin + sample_count) it casts the camera ray that
+ * rsrt_render casts for (pixel, k) — seed (pixel_index, k), unit-disc jitter — takes that ray's closest hit as rsrt_cast_rays
+ * mode 0 does (BVH, then the brute-force fallback) and adds, in increasing k and in f32, to the pixel's 8-float record:
+ *   [0..2] the hit material's color, [3] 1 (hits), [4..6] the hit normal (flipped towards the ray, as the shader uses it),
+ *   [7] the hit distance.  A miss adds nothing, so split calls give the bits of one call.
+ * The record buffer is width*height*8 f32 on the device: library-owned, sized to the accumulator (allocated and zeroed on
+ * first use or when the size changes), or caller-owned through rsrt_aov_bind (16-byte aligned; NULL goes back to the
+ * library's).  flags must be 0. */
+rsrt_status rsrt_aov_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin,
+                            uint32_t sample_count, uint32_t flags, void *hip_stream);
+rsrt_status rsrt_aov_bind(rsrt_context *ctx, void *device_f32x8, uint32_t width, uint32_t height);
+rsrt_status rsrt_aov_clear(rsrt_context *ctx);
+rsrt_status rsrt_aov_download(rsrt_context *ctx, float *host_f32x8, size_t n_floats);
+
+/* Filter pass: an edge-aware a-trous wavelet filter (Dammertz et al. 2010) of the mean sum / sample_total, guided by the AOV
+ * records of aov_sample_total samples.  The arithmetic is published in include/rsrt_denoise.h: demodulation by the mean
+ * first-hit albedo, `iterations` levels of the 5x5 B3 spline with step 2^i and rational colour / normal / relative-depth weights,
+ * remodulation.  Defaults (what a zero-initialised caller should fill in; the Python and C++ State use them):
+ *   iterations 5 (0..8; 0 returns the mean exactly), sigma_color 2.0, sigma_normal 0.5, sigma_depth 0.3
+ *   (each in [1e-6, 1e6]), flags RSRT_DENOISE_DEMODULATE. */
+enum { RSRT_DENOISE_DEMODULATE = 1u };
+typedef struct rsrt_denoise_params {
+    uint32_t iterations;
+    uint32_t flags;
+    float sigma_color;  /* of the demodulated colour; level i uses sigma_color / 2^i */
+    float sigma_normal; /* of the mean normal */
+    float sigma_depth;  /* of the mean distance, relative to the centre pixel's */
+} rsrt_denoise_params;
+/* Writes W*H RGBA32F (alpha 1) to device_out_rgba32f (a device buffer of the accumulator's size, 16-byte aligned) or, when it is
+ * NULL, to a library-owned buffer.  Scratch (two W*H float4 ping-pong buffers and the packed features) is allocated on first
+ * use and freed on resize and destroy.  RSRT_ERR_NOT_READY: no accumulator or no AOV buffer; RSRT_ERR_INVALID_ARGUMENT: a bad
+ * parameter, sample_total or aov_sample_total 0, an AOV buffer of another size than the accumulator, world_size > 1.
+ * Asynchronous on hip_stream (NULL = the context's stream). */
+rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_sample_total, const rsrt_denoise_params *params,
+                         void *device_out_rgba32f, void *hip_stream);
+/* the last rsrt_denoise output (wherever it was written), to the host: W*H*4 floats */
+rsrt_status rsrt_denoised_download(rsrt_context *ctx, float *host_rgba, size_t n_floats);
+/* ... through the display pass: rsrt_display_pixel(denoised, 1.0f) per pixel (include/rsrt_tonemap.h), RGBA8, alpha 255 */
+rsrt_status rsrt_denoised_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -128,18 +128,59 @@ public:
 
     // State::render (src/state.rs:760-833): one more sample per pixel; restart when the scene hash changed
     void render() { render_samples(1); }
-    void render_samples(uint32_t n)
+    // aov = true: the denoiser's AOV pass over the same samples too (one device only, see render_aov)
+    void render_samples(uint32_t n, bool aov = false)
     {
         const size_t h = scene_hash();
         if (!have_hash_ || h != last_hash_) { // src/state.rs:778-786
             last_hash_ = h; have_hash_ = true;
             check(rsrt_multi_clear(m_));
             sample_count_ = 0;
+            if (have_aov_) clear_aov();
         }
         rsrt_camera cam;
         rsrt_camera_uniform(&camera_, &cam);
         check(rsrt_multi_render(m_, &cam, width_, height_, sample_count_, n, max_bounces, environment_index, flags));
+        if (aov) render_aov(sample_count_, n);
         sample_count_ += n;
+    }
+
+    // -- the denoiser (rsrt.h "denoiser"): whole frame, so a State over one device -------------------------
+    // rsrt_aov_render of samples [sample_begin, sample_begin + n) into device 0's AOV buffer (raw: no hash check)
+    void render_aov(uint32_t sample_begin, uint32_t n)
+    {
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        check_ctx(rsrt_aov_render(context(0), &cam, width_, height_, sample_begin, n, 0, nullptr));
+        have_aov_ = true;
+        aov_sample_count_ += n;
+    }
+    void clear_aov()
+    {
+        check_ctx(rsrt_aov_clear(context(0)));
+        aov_sample_count_ = 0;
+    }
+    uint32_t aov_sample_count() const { return aov_sample_count_; }
+    std::vector<float> download_aov() // W*H*8: albedo sum xyz, hits, normal sum xyz, distance sum
+    {
+        std::vector<float> out((size_t)width_ * height_ * 8);
+        check_ctx(rsrt_aov_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    static rsrt_denoise_params denoise_defaults() { return rsrt_denoise_params{5u, RSRT_DENOISE_DEMODULATE, 2.0f, 0.5f, 0.3f}; }
+    // rsrt_denoise of the mean of sample_count() samples, guided by aov_sample_count() AOV samples: W*H*4 f32 (alpha 1)
+    std::vector<float> denoise(const rsrt_denoise_params &p = denoise_defaults())
+    {
+        check_ctx(rsrt_denoise(context(0), sample_count_, aov_sample_count_, &p, nullptr, nullptr));
+        std::vector<float> out((size_t)width_ * height_ * 4);
+        check_ctx(rsrt_denoised_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    std::vector<uint8_t> denoised_display() // the last denoise() through the display pass
+    {
+        std::vector<uint8_t> out((size_t)width_ * height_ * 4);
+        check_ctx(rsrt_denoised_display_srgb8(context(0), out.data(), out.size()));
+        return out;
     }
     std::vector<float> download() // cumulative_light_texture, all devices' tiles
     {
@@ -175,6 +216,10 @@ private:
     {
         if (st != RSRT_OK) throw Error(rsrt_multi_last_error(m_));
     }
+    void check_ctx(rsrt_status st)
+    {
+        if (st != RSRT_OK) throw Error(rsrt_last_error(context(0)));
+    }
     size_t scene_hash() const // SceneState: camera bits + environment index (src/scene.rs:255-262, src/camera.rs:92-100)
     {
         std::string bytes(reinterpret_cast<const char *>(&camera_), sizeof camera_);
@@ -183,7 +228,8 @@ private:
     }
     rsrt_multi *m_ = nullptr;
     rsrt_camera_desc camera_{};
-    uint32_t width_ = 0, height_ = 0, sample_count_ = 0;
+    uint32_t width_ = 0, height_ = 0, sample_count_ = 0, aov_sample_count_ = 0;
+    bool have_aov_ = false;
     size_t last_hash_ = 0;
     bool have_hash_ = false;
 };

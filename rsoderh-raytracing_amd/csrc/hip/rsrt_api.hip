@@ -744,6 +744,14 @@ struct rsrt_context {
     int hw_queues = 4;
     bool hw_queue_warned = false;
     unsigned long long debug_words[32] = {0};
+    // denoiser (rt_denoise.h): the AOV records (bound or owned, 2 float4 a pixel), the filter's scratch (freed when the accumulator's size
+    // changes) and where the last rsrt_denoise wrote
+    float4 *aov = nullptr;
+    float4 *aov_owned = nullptr;
+    uint32_t aov_w = 0, aov_h = 0;
+    void *dn_scratch = nullptr;
+    uint32_t dn_w = 0, dn_h = 0;
+    float4 *dn_last = nullptr;
 };
 
 namespace {
@@ -954,6 +962,14 @@ void fill_wide_nodes(const std::vector<WideNode> &wide, const rsrt_bvh_node *nod
     }
 }
 
+void free_denoise_scratch(rsrt_context *ctx)
+{
+    (void)hipFree(ctx->dn_scratch);
+    ctx->dn_scratch = nullptr;
+    ctx->dn_w = ctx->dn_h = 0;
+    ctx->dn_last = nullptr;
+}
+
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
     if (ctx->accum && ctx->acc_w == w && ctx->acc_h == h) return RSRT_OK;
@@ -961,6 +977,7 @@ rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bound accumulator is %ux%u but %ux%u was requested", ctx->acc_w, ctx->acc_h, w, h);
     if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; ctx->accum = nullptr; }
     HIP_TRY(ctx, hipDeviceSynchronize());
+    free_denoise_scratch(ctx);
     HIP_TRY(ctx, hipMalloc(&ctx->accum_owned, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipMemset(ctx->accum_owned, 0, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -1308,6 +1325,8 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->scene_blob);
     for (auto &e : ctx->envs) { (void)hipFree(e.rgba); (void)hipFree(e.alias); }
     (void)hipFree(ctx->accum_owned);
+    (void)hipFree(ctx->aov_owned);
+    (void)hipFree(ctx->dn_scratch);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -1987,6 +2006,7 @@ rsrt_status rsrt_accumulator_bind(rsrt_context *ctx, void *device_rgba32f, uint3
     if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
     if ((uintptr_t)device_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "accumulator pointer must be 16-byte aligned");
     if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; }
+    if (width != ctx->acc_w || height != ctx->acc_h) free_denoise_scratch(ctx);
     ctx->accum = static_cast<float4 *>(device_rgba32f);
     ctx->acc_w = width;
     ctx->acc_h = height;
@@ -2375,3 +2395,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 } // extern "C"
 
 #include "rsrt_comm.h"
+#include "rt_denoise.h"

@@ -29,11 +29,26 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_partition_owner", "rsrt_partition_mask", "rsrt_partition_tiles", "rsrt_comm_available", "rsrt_comm_unique_id", "rsrt_comm_init", "rsrt_comm_reduce", "rsrt_comm_set_mode", "rsrt_comm_destroy",
             "rsrt_multi_create", "rsrt_multi_destroy", "rsrt_multi_last_error", "rsrt_multi_size", "rsrt_multi_context",
             "rsrt_multi_upload_scene", "rsrt_multi_upload_environment", "rsrt_multi_resize", "rsrt_multi_clear", "rsrt_multi_render",
-            "rsrt_multi_synchronize", "rsrt_multi_download", "rsrt_multi_display_srgb8", "rsrt_multi_get_stats", "rsrt_multi_uses_rccl"]
+            "rsrt_multi_synchronize", "rsrt_multi_download", "rsrt_multi_display_srgb8", "rsrt_multi_get_stats", "rsrt_multi_uses_rccl",
+            "rsrt_aov_render", "rsrt_aov_bind", "rsrt_aov_clear", "rsrt_aov_download", "rsrt_denoise", "rsrt_denoised_download",
+            "rsrt_denoised_display_srgb8"]
 
 
 class RsrtError(RuntimeError):
-    pass
+    def __init__(self, msg, status=None):
+        super().__init__(msg)
+        self.status = status  # the rsrt_status of the failing call, where there is one
+
+
+DENOISE_DEMODULATE = 1  # rsrt_denoise_params.flags: filter colour / albedo, then multiply the albedo back
+# rsrt_denoise_params defaults (include/rsrt.h)
+DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 2.0, "sigma_normal": 0.5, "sigma_depth": 0.3, "demodulate": True}
+AOV_FLOATS = 8  # per pixel: albedo sum xyz, hits, normal sum xyz, distance sum
+
+
+class DenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
 
 
 def build_id():
@@ -121,6 +136,13 @@ def lib():
         L.rsrt_multi_display_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
         L.rsrt_multi_get_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_multi_uses_rccl.argtypes = [C.c_void_p]
+        L.rsrt_aov_render.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p]
+        L.rsrt_aov_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.rsrt_aov_clear.argtypes = [C.c_void_p]
+        L.rsrt_aov_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsrt_denoised_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_denoised_display_srgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -143,6 +165,8 @@ class State:
         self.camera = None
         self._last_hash = None
         self.flags = 0
+        self.aov_sample_count = 0      # samples in the AOV buffer (render_samples(aov=True) / render_aov)
+        self._has_aov = False
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -157,7 +181,7 @@ class State:
 
     def _check(self, rc, what):
         if rc != 0:
-            raise RsrtError("%s failed (%d): %s" % (what, rc, self._L.rsrt_last_error(self._ctx).decode()))
+            raise RsrtError("%s failed (%d): %s" % (what, rc, self._L.rsrt_last_error(self._ctx).decode()), rc)
 
     def close(self):
         if self._ctx:
@@ -252,15 +276,20 @@ class State:
         self._check(self._L.rsrt_accumulator_clear(self._ctx), "rsrt_accumulator_clear")
         self.sample_count = 0
 
-    def render_samples(self, n, stream=None):
-        """Adds samples [sample_count, sample_count+n); resets first when camera/environment changed."""
+    def render_samples(self, n, stream=None, aov=False):
+        """Adds samples [sample_count, sample_count+n); resets first when camera/environment changed.  aov=True: the AOV pass
+        (render_aov) over the same sample range too."""
         h = self._scene_hash()
         if h != self._last_hash:  # state.rs:778-786
             self._last_hash = h
             self.clear()
+            if self._has_aov:
+                self.clear_aov()
         self._check(self._L.rsrt_render(self._ctx, _p(self.camera), self.width, self.height, self.sample_count, n,
                                         self.max_bounces, self.environment_index, self.flags,
                                         C.c_void_p(stream) if stream else None), "rsrt_render")
+        if aov:
+            self.render_aov(self.sample_count, n, stream=stream)
         self.sample_count += n
 
     def render(self):
@@ -275,6 +304,55 @@ class State:
 
     def synchronize(self):
         self._check(self._L.rsrt_synchronize(self._ctx), "rsrt_synchronize")
+
+    # -- denoiser (include/rsrt.h "denoiser") -------------------------------------------------------
+    def render_aov(self, sample_begin, sample_count, stream=None):
+        """rsrt_aov_render: adds the first hits of the camera rays of samples [sample_begin, sample_begin + sample_count) to the
+        AOV buffer.  Raw, like render_range: no hash check; aov_sample_count grows by sample_count."""
+        self._check(self._L.rsrt_aov_render(self._ctx, _p(self.camera), self.width, self.height, sample_begin, sample_count, 0,
+                                            C.c_void_p(stream) if stream else None), "rsrt_aov_render")
+        self._has_aov = True
+        self.aov_sample_count += sample_count
+
+    def bind_aov(self, device_ptr, width, height):
+        """Use caller-owned device memory (W*H*8 f32) as the AOV buffer (None: back to the library's)."""
+        self._check(self._L.rsrt_aov_bind(self._ctx, C.c_void_p(device_ptr) if device_ptr else None, width, height), "rsrt_aov_bind")
+        self._has_aov = bool(device_ptr)
+
+    def clear_aov(self):
+        self._check(self._L.rsrt_aov_clear(self._ctx), "rsrt_aov_clear")
+        self.aov_sample_count = 0
+
+    def download_aov(self):
+        """[H, W, 8] float32: albedo sum xyz, hits, normal sum xyz, distance sum."""
+        out = np.empty((self.height, self.width, AOV_FLOATS), np.float32)
+        self._check(self._L.rsrt_aov_download(self._ctx, _p(out), out.size), "rsrt_aov_download")
+        return out
+
+    def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, sample_total=None,
+                aov_sample_total=None, out_ptr=None, stream=None, download=True):
+        """rsrt_denoise of the accumulator's mean, guided by the AOV buffer: [H, W, 4] float32 (alpha 1), or None with download=False
+        (the result stays on the device: denoised_display_srgb8, or out_ptr when given).  Unset arguments take DENOISE_DEFAULTS and
+        the sample counters."""
+        d = DENOISE_DEFAULTS
+        pick = lambda v, k: d[k] if v is None else v  # noqa: E731
+        p = DenoiseParams(pick(iterations, "iterations"), DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0,
+                          pick(sigma_color, "sigma_color"), pick(sigma_normal, "sigma_normal"), pick(sigma_depth, "sigma_depth"))
+        n = self.sample_count if sample_total is None else sample_total
+        na = self.aov_sample_count if aov_sample_total is None else aov_sample_total
+        self._check(self._L.rsrt_denoise(self._ctx, n, na, C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
+                                         C.c_void_p(stream) if stream else None), "rsrt_denoise")
+        if not download:
+            return None
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._L.rsrt_denoised_download(self._ctx, _p(out), out.size), "rsrt_denoised_download")
+        return out
+
+    def denoised_display_srgb8(self):
+        """The last denoise() output through the display pass (rsrt_display_pixel(denoised, 1)): [H, W, 4] uint8."""
+        out = np.empty((self.height, self.width, 4), np.uint8)
+        self._check(self._L.rsrt_denoised_display_srgb8(self._ctx, _p(out), out.size), "rsrt_denoised_display_srgb8")
+        return out
 
     # -- results ---------------------------------------------------------------------------------
     def download(self):
