@@ -305,6 +305,37 @@ rsrt_status rsrt_denoised_download(rsrt_context *ctx, float *host_rgba, size_t n
 /* ... through the display pass: rsrt_display_pixel(denoised, 1.0f) per pixel (include/rsrt_tonemap.h), RGBA8, alpha 255 */
 rsrt_status rsrt_denoised_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes);
 
+/* -- temporal pass: sample history kept across camera moves (no reference counterpart) ---------------------------------------------
+ * An interactive caller shows one new frame of a few samples per display refresh and moves the camera between frames.  This pass
+ * reprojects the previous frames' per-pixel history into the current camera, rejects it where the surface changed (plane-distance and
+ * normal tests against the AOV records' mean first hit) and blends the rest with the new frame, weighted by sample count: the colour
+ * of up to max_history earlier samples at no extra ray cost.  The arithmetic is published in include/rsrt_temporal.h (defaults there:
+ * max_history 32, depth_tolerance 0.05, normal_tolerance 0.9).  Whole frame only, like the denoiser.
+ *
+ * rsrt_temporal_accumulate takes the current frame from the accumulator (sum of sample_total samples) and the AOV buffer (records of
+ * aov_sample_total samples), both of the same size, seen through `camera`.  It writes W*H float4 (colour, sample weight) into a
+ * library-owned history (two history and two feature buffers, 64 B a pixel, allocated on first use and freed on resize and destroy)
+ * and remembers the camera for the next call.  An unchanged camera adds the new samples to each pixel's own history uncapped, so a
+ * camera held still converges like the accumulator.  RSRT_ERR_NOT_READY: no accumulator or no AOV buffer; RSRT_ERR_INVALID_ARGUMENT:
+ * a bad parameter, sample_total or aov_sample_total 0, an AOV buffer of another size than the accumulator, world_size > 1.
+ * History is dropped (the next call acts as a first frame: out = (sum / S, S)) by rsrt_temporal_reset, by an accumulator resize or a
+ * bind of another size, and by rsrt_upload_scene / rsrt_upload_environment.  The pass cannot see the render settings: a caller that
+ * changes environment_index, max_bounces or the render flags calls rsrt_temporal_reset.  Each frame needs fresh sample indices
+ * (a frame that reuses the previous frame's indices repeats its random numbers and adds nothing).  Asynchronous on hip_stream. */
+typedef struct rsrt_temporal_params {
+    uint32_t max_history;   /* cap of the reprojected history's sample weight, 1 .. 2^24 */
+    float depth_tolerance;  /* plane-distance test |n . (Xq - X)| <= depth_tolerance * z, in [1e-6, 1e6] */
+    float normal_tolerance; /* normal test n . nq >= normal_tolerance, in [-1, 1] */
+} rsrt_temporal_params;
+rsrt_status rsrt_temporal_accumulate(rsrt_context *ctx, const rsrt_camera *camera, uint32_t sample_total, uint32_t aov_sample_total,
+                                     const rsrt_temporal_params *params, void *hip_stream);
+rsrt_status rsrt_temporal_reset(rsrt_context *ctx);
+/* the last frame's history to the host: W*H*4 floats (colour, weight); RSRT_ERR_NOT_READY when no frame ran since the last reset */
+rsrt_status rsrt_temporal_download(rsrt_context *ctx, float *host_rgba, size_t n_floats);
+/* rsrt_denoise_params.flags: filter the temporal pass's colour instead of sum / sample_total (sample_total is then ignored;
+ * RSRT_ERR_NOT_READY when no temporal frame ran since the last reset) */
+enum { RSRT_DENOISE_TEMPORAL = 2u };
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -176,6 +176,43 @@ public:
         check_ctx(rsrt_denoised_download(context(0), out.data(), out.size()));
         return out;
     }
+    // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
+    static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
+    // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass
+    // (k only grows until temporal_reset: fresh random numbers every frame) and blend them with the reprojected history.  Resets the
+    // history first when environment_index, max_bounces, flags or the size changed; afterwards sample_count() = aov_sample_count() = n
+    // and a later render_samples starts clean.  denoise() with RSRT_DENOISE_TEMPORAL in the flags filters the result.
+    void render_temporal(uint32_t n = 1, const rsrt_temporal_params &p = temporal_defaults())
+    {
+        const uint32_t key[5] = {environment_index, max_bounces, flags, width_, height_};
+        if (!have_temporal_key_ || std::memcmp(key, temporal_key_, sizeof key) != 0) {
+            temporal_reset();
+            std::memcpy(temporal_key_, key, sizeof key);
+            have_temporal_key_ = true;
+        }
+        check(rsrt_multi_clear(m_));
+        if (have_aov_) clear_aov();
+        const uint32_t k = temporal_sample_count_;
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        check(rsrt_multi_render(m_, &cam, width_, height_, k, n, max_bounces, environment_index, flags));
+        render_aov(k, n);
+        check_ctx(rsrt_temporal_accumulate(context(0), &cam, n, n, &p, nullptr));
+        temporal_sample_count_ = k + n;
+        sample_count_ = n;
+        have_hash_ = false;
+    }
+    void temporal_reset() // the next render_temporal is a first frame, from sample 0
+    {
+        check_ctx(rsrt_temporal_reset(context(0)));
+        temporal_sample_count_ = 0;
+    }
+    std::vector<float> download_temporal() // W*H*4: colour, sample weight
+    {
+        std::vector<float> out((size_t)width_ * height_ * 4);
+        check_ctx(rsrt_temporal_download(context(0), out.data(), out.size()));
+        return out;
+    }
     std::vector<uint8_t> denoised_display() // the last denoise() through the display pass
     {
         std::vector<uint8_t> out((size_t)width_ * height_ * 4);
@@ -230,6 +267,8 @@ private:
     rsrt_camera_desc camera_{};
     uint32_t width_ = 0, height_ = 0, sample_count_ = 0, aov_sample_count_ = 0;
     bool have_aov_ = false;
+    uint32_t temporal_sample_count_ = 0, temporal_key_[5] = {0, 0, 0, 0, 0};
+    bool have_temporal_key_ = false;
     size_t last_hash_ = 0;
     bool have_hash_ = false;
 };

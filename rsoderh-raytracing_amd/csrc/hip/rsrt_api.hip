@@ -752,6 +752,11 @@ struct rsrt_context {
     void *dn_scratch = nullptr;
     uint32_t dn_w = 0, dn_h = 0;
     float4 *dn_last = nullptr;
+    // temporal pass (rt_temporal.h): two history and two feature buffers (float4 each, freed when the accumulator's size changes), which
+    // history holds the last frame, how many frames ran since the last reset (0: the next one is a first frame) and the last camera
+    float4 *tp_buf = nullptr;
+    uint32_t tp_w = 0, tp_h = 0, tp_cur = 0, tp_frames = 0;
+    float tp_cam[13] = {0}; // pos, rot (column-major 3x3), fov_y
 };
 
 namespace {
@@ -970,6 +975,16 @@ void free_denoise_scratch(rsrt_context *ctx)
     ctx->dn_last = nullptr;
 }
 
+void free_temporal(rsrt_context *ctx)
+{
+    (void)hipFree(ctx->tp_buf);
+    ctx->tp_buf = nullptr;
+    ctx->tp_w = ctx->tp_h = ctx->tp_cur = ctx->tp_frames = 0;
+}
+
+// the temporal history of the last frame (valid when tp_frames > 0)
+float4 *temporal_history(rsrt_context *ctx) { return ctx->tp_buf + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
+
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
     if (ctx->accum && ctx->acc_w == w && ctx->acc_h == h) return RSRT_OK;
@@ -978,6 +993,7 @@ rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
     if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; ctx->accum = nullptr; }
     HIP_TRY(ctx, hipDeviceSynchronize());
     free_denoise_scratch(ctx);
+    free_temporal(ctx);
     HIP_TRY(ctx, hipMalloc(&ctx->accum_owned, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipMemset(ctx->accum_owned, 0, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -1327,6 +1343,7 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->accum_owned);
     (void)hipFree(ctx->aov_owned);
     (void)hipFree(ctx->dn_scratch);
+    (void)hipFree(ctx->tp_buf);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -1358,6 +1375,7 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
+    ctx->tp_frames = 0; // the temporal history belongs to the old scene
     const rsrt_primitive_info *primitives = primitives_in; // (re-pointed below at a copy with whole leaves reordered, when the wide walk is built)
     const rsrt_bvh_node *nodes = nodes_in;
     if (n_nodes == 0 || !nodes) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh_nodes is empty");
@@ -1909,6 +1927,7 @@ rsrt_status rsrt_upload_environment(rsrt_context *ctx, uint32_t slot, uint32_t w
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
+    ctx->tp_frames = 0; // the temporal history saw the old environment
     if (!rgba || width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "environment: NULL data or zero size");
     if ((uint64_t)width * height > 0x7fffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "environment too large");
     if (slot > 63) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "environment slot %u > 63", slot);
@@ -2006,7 +2025,7 @@ rsrt_status rsrt_accumulator_bind(rsrt_context *ctx, void *device_rgba32f, uint3
     if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
     if ((uintptr_t)device_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "accumulator pointer must be 16-byte aligned");
     if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; }
-    if (width != ctx->acc_w || height != ctx->acc_h) free_denoise_scratch(ctx);
+    if (width != ctx->acc_w || height != ctx->acc_h) { free_denoise_scratch(ctx); free_temporal(ctx); }
     ctx->accum = static_cast<float4 *>(device_rgba32f);
     ctx->acc_w = width;
     ctx->acc_h = height;
@@ -2396,3 +2415,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 
 #include "rsrt_comm.h"
 #include "rt_denoise.h"
+#include "rt_temporal.h"

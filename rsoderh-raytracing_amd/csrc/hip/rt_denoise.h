@@ -262,11 +262,15 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
     const rsrt_denoise_params &p = *params;
     if (p.iterations > 8u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: iterations %u (at most 8)", p.iterations);
-    if (p.flags & ~(uint32_t)RSRT_DENOISE_DEMODULATE) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: unknown flags 0x%x", p.flags);
+    if (p.flags & ~(uint32_t)(RSRT_DENOISE_DEMODULATE | RSRT_DENOISE_TEMPORAL)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: unknown flags 0x%x", p.flags);
+    const bool temporal = (p.flags & RSRT_DENOISE_TEMPORAL) != 0; // the temporal pass's colour (its weight channel is ignored), sample_total 1
+    if (temporal) sample_total = 1u;
     if (!sigma_ok(p.sigma_color) || !sigma_ok(p.sigma_normal) || !sigma_ok(p.sigma_depth))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: sigmas must lie in [1e-6, 1e6]");
     if (sample_total == 0 || aov_sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: sample_total and aov_sample_total must be > 0");
     if ((uintptr_t)device_out_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: output pointer must be 16-byte aligned");
+    if (temporal && (!ctx->tp_frames || ctx->tp_w != ctx->acc_w || ctx->tp_h != ctx->acc_h))
+        return fail(ctx, RSRT_ERR_NOT_READY, "denoise: no temporal frame since the last reset (rsrt_temporal_accumulate first)");
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
     rsrt_status st = ensure_denoise_scratch(ctx);
     if (st || (st = begin_work(ctx, stream))) return st;
@@ -278,7 +282,7 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
     const float st_f = (float)sample_total, at_f = (float)aov_sample_total;
     const int demod = (p.flags & RSRT_DENOISE_DEMODULATE) ? 1 : 0;
     const uint32_t L = p.iterations;
-    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(ctx->accum, ctx->aov, n, st_f, at_f, demod, L == 0, L == 0 ? out : ping, feat);
+    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(temporal ? temporal_history(ctx) : ctx->accum, ctx->aov, n, st_f, at_f, demod, L == 0, L == 0 ? out : ping, feat);
     const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
     for (uint32_t i = 0; i < L; i++) {
         const float4 *src = (i % 2u == 0u) ? ping : pong;

@@ -1,0 +1,134 @@
+// rt_temporal.h — the temporal pass's kernel and C-ABI (include/rsrt.h "temporal pass").  Included at the end of
+// rsrt_api.hip, after rt_denoise.h.
+//
+//  rt_temporal_kernel  one thread a pixel, 64 x 4 workgroups like rt_dn_level_kernel: a wave is one row of 64 pixels, so its bilinear
+//                      taps fall on about two rows of the previous frame.  It reads the sum (16 B), the AOV record (32 B) and up to 4
+//                      taps of previous history and features (16 + 16 B each, mostly from the caches), and writes history and
+//                      features (32 B): about 112 B of unique traffic a pixel.  No LDS.  The per-pixel arithmetic is
+//                      include/rsrt_temporal.h.
+#include "../../../include/rsrt_temporal.h"
+
+// the previous frame's buffers, as rsrt_tp_pixel reads them
+struct TpPrev {
+    const float4 *c_, *f_;
+    __host__ __device__ void col(unsigned q, float o[4]) const
+    {
+        const float4 v = c_[q];
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+    __host__ __device__ void feat(unsigned q, float o[4]) const
+    {
+        const float4 v = f_[q];
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+};
+
+__global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_temporal_kernel(rsrt_tp_frame fr, const float4 *accum, const float4 *aov, const float4 *prev_col,
+                                                                          const float4 *prev_feat, float4 *out_col, float4 *out_feat)
+{
+    const int x = (int)(blockIdx.x * RT_DN_BX + threadIdx.x), y = (int)(blockIdx.y * RT_DN_BY + threadIdx.y);
+    if (x >= (int)fr.width || y >= (int)fr.height) return;
+    const size_t p = (size_t)y * fr.width + (size_t)x;
+    const float4 s = accum[p];
+    const float sum[3] = {s.x, s.y, s.z};
+    float a[8], o[4], f[4];
+    dn_aov(aov, p, a);
+    rsrt_tp_pixel(&fr, TpPrev{prev_col, prev_feat}, x, y, sum, a, o, f);
+    out_col[p] = make_float4(o[0], o[1], o[2], o[3]);
+    out_feat[p] = make_float4(f[0], f[1], f[2], f[3]);
+}
+
+namespace {
+
+// history 0, history 1, features 0, features 1 (float4 each) for the accumulator's size; a new allocation starts without history
+rsrt_status ensure_temporal(rsrt_context *ctx)
+{
+    if (ctx->tp_buf && ctx->tp_w == ctx->acc_w && ctx->tp_h == ctx->acc_h) return RSRT_OK;
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    free_temporal(ctx);
+    HIP_TRY(ctx, hipMalloc(&ctx->tp_buf, (size_t)ctx->acc_w * ctx->acc_h * 4u * sizeof(float4)));
+    ctx->tp_w = ctx->acc_w;
+    ctx->tp_h = ctx->acc_h;
+    return RSRT_OK;
+}
+
+void tp_camera_of(const float c[13], rsrt_tp_camera *out) { rsrt_tp_camera_init(out, c, c + 3, c[12]); }
+
+} // namespace
+
+extern "C" {
+
+rsrt_status rsrt_temporal_accumulate(rsrt_context *ctx, const rsrt_camera *camera, uint32_t sample_total, uint32_t aov_sample_total,
+                                     const rsrt_temporal_params *params, void *hip_stream)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (!camera) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: camera is NULL");
+    if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: params is NULL");
+    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: whole frame only (partition of %u ranks)", ctx->world);
+    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "temporal: no AOV buffer (rsrt_aov_render or rsrt_aov_bind first)");
+    if (ctx->aov_w != ctx->acc_w || ctx->aov_h != ctx->acc_h)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
+    const rsrt_temporal_params &p = *params;
+    if (p.max_history < 1u || p.max_history > (1u << 24))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: max_history %u (1 .. 2^24)", p.max_history);
+    if (!(p.depth_tolerance >= 1.0e-6f && p.depth_tolerance <= 1.0e6f))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: depth_tolerance must lie in [1e-6, 1e6]");
+    if (!(p.normal_tolerance >= -1.0f && p.normal_tolerance <= 1.0f))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: normal_tolerance must lie in [-1, 1]");
+    if (sample_total == 0 || aov_sample_total == 0)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: sample_total and aov_sample_total must be > 0");
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+    rsrt_status st = ensure_temporal(ctx);
+    if (st || (st = begin_work(ctx, stream))) return st;
+    const uint32_t w = ctx->acc_w, h = ctx->acc_h;
+    const size_t n = (size_t)w * h;
+    float cam[13];
+    memcpy(cam, camera->pos, 12);
+    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) cam[3 + 3 * j + k] = camera->rot_transform[j][k];
+    cam[12] = camera->fov_y;
+    rsrt_tp_frame fr;
+    memset(&fr, 0, sizeof fr);
+    tp_camera_of(cam, &fr.cur);
+    tp_camera_of(ctx->tp_frames ? ctx->tp_cam : cam, &fr.prev);
+    fr.width = w;
+    fr.height = h;
+    fr.sample_total = (float)sample_total;
+    fr.aov_sample_total = (float)aov_sample_total;
+    fr.max_history = (float)p.max_history;
+    fr.depth_tolerance = p.depth_tolerance;
+    fr.normal_tolerance = p.normal_tolerance;
+    fr.aspect = (float)w / (float)h;
+    fr.has_prev = ctx->tp_frames > 0;
+    fr.identity = fr.has_prev && rsrt_tp_same_camera(&fr.cur, &fr.prev); // (a resize frees the buffers, so W and H are the previous frame's)
+    const uint32_t src = ctx->tp_cur, dst = src ^ 1u;
+    float4 *hist = ctx->tp_buf, *feat = ctx->tp_buf + 2u * n;
+    const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
+    rt_temporal_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, hist + dst * n, feat + dst * n);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->tp_cur = dst;
+    ctx->tp_frames++;
+    memcpy(ctx->tp_cam, cam, sizeof cam);
+    return end_work(ctx, stream);
+}
+
+rsrt_status rsrt_temporal_reset(rsrt_context *ctx)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    ctx->tp_frames = 0;
+    return RSRT_OK;
+}
+
+rsrt_status rsrt_temporal_download(rsrt_context *ctx, float *host, size_t n_floats)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (!ctx->tp_buf || !ctx->tp_frames) return fail(ctx, RSRT_ERR_NOT_READY, "no temporal frame since the last reset (rsrt_temporal_accumulate first)");
+    if (!host || n_floats != (size_t)ctx->tp_w * ctx->tp_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal_download: expected %zu floats", (size_t)ctx->tp_w * ctx->tp_h * 4u);
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    HIP_TRY(ctx, hipMemcpy(host, temporal_history(ctx), n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return RSRT_OK;
+}
+
+} // extern "C"

@@ -31,7 +31,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_multi_upload_scene", "rsrt_multi_upload_environment", "rsrt_multi_resize", "rsrt_multi_clear", "rsrt_multi_render",
             "rsrt_multi_synchronize", "rsrt_multi_download", "rsrt_multi_display_srgb8", "rsrt_multi_get_stats", "rsrt_multi_uses_rccl",
             "rsrt_aov_render", "rsrt_aov_bind", "rsrt_aov_clear", "rsrt_aov_download", "rsrt_denoise", "rsrt_denoised_download",
-            "rsrt_denoised_display_srgb8"]
+            "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download"]
 
 
 class RsrtError(RuntimeError):
@@ -44,6 +44,15 @@ DENOISE_DEMODULATE = 1  # rsrt_denoise_params.flags: filter colour / albedo, the
 # rsrt_denoise_params defaults (include/rsrt.h)
 DENOISE_DEFAULTS = {"iterations": 5, "sigma_color": 2.0, "sigma_normal": 0.5, "sigma_depth": 0.3, "demodulate": True}
 AOV_FLOATS = 8  # per pixel: albedo sum xyz, hits, normal sum xyz, distance sum
+
+
+DENOISE_TEMPORAL = 2  # rsrt_denoise_params.flags: filter the temporal pass's colour instead of the accumulator's mean
+# rsrt_temporal_params defaults (include/rsrt_temporal.h)
+TEMPORAL_DEFAULTS = {"max_history": 32, "depth_tolerance": 0.05, "normal_tolerance": 0.9}
+
+
+class TemporalParams(C.Structure):
+    _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float)]
 
 
 class DenoiseParams(C.Structure):
@@ -143,6 +152,9 @@ def lib():
         L.rsrt_denoise.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsrt_denoised_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_denoised_display_srgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_temporal_reset.argtypes = [C.c_void_p]
+        L.rsrt_temporal_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -167,6 +179,8 @@ class State:
         self.flags = 0
         self.aov_sample_count = 0      # samples in the AOV buffer (render_samples(aov=True) / render_aov)
         self._has_aov = False
+        self.temporal_sample_count = 0  # first sample index of the next render_temporal frame (only grows until temporal_reset)
+        self._temporal_key = None       # what the history was rendered under: environment, bounces, flags, size
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -330,14 +344,15 @@ class State:
         return out
 
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, sample_total=None,
-                aov_sample_total=None, out_ptr=None, stream=None, download=True):
+                aov_sample_total=None, out_ptr=None, stream=None, download=True, temporal=False):
         """rsrt_denoise of the accumulator's mean, guided by the AOV buffer: [H, W, 4] float32 (alpha 1), or None with download=False
         (the result stays on the device: denoised_display_srgb8, or out_ptr when given).  Unset arguments take DENOISE_DEFAULTS and
-        the sample counters."""
+        the sample counters.  temporal=True: of the last render_temporal frame's colour instead (RSRT_DENOISE_TEMPORAL)."""
         d = DENOISE_DEFAULTS
         pick = lambda v, k: d[k] if v is None else v  # noqa: E731
-        p = DenoiseParams(pick(iterations, "iterations"), DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0,
-                          pick(sigma_color, "sigma_color"), pick(sigma_normal, "sigma_normal"), pick(sigma_depth, "sigma_depth"))
+        flags = (DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0) | (DENOISE_TEMPORAL if temporal else 0)
+        p = DenoiseParams(pick(iterations, "iterations"), flags, pick(sigma_color, "sigma_color"), pick(sigma_normal, "sigma_normal"),
+                          pick(sigma_depth, "sigma_depth"))
         n = self.sample_count if sample_total is None else sample_total
         na = self.aov_sample_count if aov_sample_total is None else aov_sample_total
         self._check(self._L.rsrt_denoise(self._ctx, n, na, C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
@@ -352,6 +367,44 @@ class State:
         """The last denoise() output through the display pass (rsrt_display_pixel(denoised, 1)): [H, W, 4] uint8."""
         out = np.empty((self.height, self.width, 4), np.uint8)
         self._check(self._L.rsrt_denoised_display_srgb8(self._ctx, _p(out), out.size), "rsrt_denoised_display_srgb8")
+        return out
+
+    # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
+    def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None):
+        """One displayed frame of an interactive view: clears the accumulator and the AOV buffer, renders samples [k, k + n) of the
+        current camera with the AOV pass (k = temporal_sample_count: fresh random numbers every frame) and blends them with the
+        reprojected history (rsrt_temporal_accumulate).  Afterwards sample_count = aov_sample_count = n, and a later render_samples
+        starts clean.  The history is reset first when environment_index, max_bounces, flags or the size changed since the last frame.
+        The result stays on the device: download_temporal, denoise(temporal=True)."""
+        key = (self.environment_index, self.max_bounces, self.flags, self.width, self.height)
+        if key != self._temporal_key:
+            self.temporal_reset()
+            self._temporal_key = key
+        self.clear()
+        if self._has_aov:
+            self.clear_aov()
+        k = self.temporal_sample_count
+        self.render_range(k, n, stream=stream)
+        self.render_aov(k, n, stream=stream)
+        d = TEMPORAL_DEFAULTS
+        p = TemporalParams(d["max_history"] if max_history is None else max_history,
+                           d["depth_tolerance"] if depth_tolerance is None else depth_tolerance,
+                           d["normal_tolerance"] if normal_tolerance is None else normal_tolerance)
+        self._check(self._L.rsrt_temporal_accumulate(self._ctx, _p(self.camera), n, n, C.byref(p), C.c_void_p(stream) if stream else None),
+                    "rsrt_temporal_accumulate")
+        self.temporal_sample_count = k + n
+        self.sample_count = n
+        self._last_hash = None
+
+    def temporal_reset(self):
+        """Drops the history: the next render_temporal frame is a first frame, from sample 0."""
+        self._check(self._L.rsrt_temporal_reset(self._ctx), "rsrt_temporal_reset")
+        self.temporal_sample_count = 0
+
+    def download_temporal(self):
+        """The last temporal frame: [H, W, 4] float32 (colour, sample weight)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._L.rsrt_temporal_download(self._ctx, _p(out), out.size), "rsrt_temporal_download")
         return out
 
     # -- results ---------------------------------------------------------------------------------
