@@ -289,7 +289,7 @@ enum { RSRT_DENOISE_DEMODULATE = 1u };
 typedef struct rsrt_denoise_params {
     uint32_t iterations;
     uint32_t flags;
-    float sigma_color;  /* of the demodulated colour; level i uses sigma_color / 2^i */
+    float sigma_color;  /* of the demodulated colour; level i uses sigma_color / 2^i (under RSRT_DENOISE_VARIANCE: sigma_l, below) */
     float sigma_normal; /* of the mean normal */
     float sigma_depth;  /* of the mean distance, relative to the centre pixel's */
 } rsrt_denoise_params;
@@ -335,6 +335,30 @@ rsrt_status rsrt_temporal_download(rsrt_context *ctx, float *host_rgba, size_t n
 /* rsrt_denoise_params.flags: filter the temporal pass's colour instead of sum / sample_total (sample_total is then ignored;
  * RSRT_ERR_NOT_READY when no temporal frame ran since the last reset) */
 enum { RSRT_DENOISE_TEMPORAL = 2u };
+
+/* -- variance guidance: temporal luminance moments, a variance-guided filter and a firefly clamp (no reference counterpart) ---------
+ * rsrt_temporal_accumulate is rsrt_temporal_accumulate_ex with flags 0.  flags: RSRT_TEMPORAL_MOMENTS also keeps a float4 moment
+ * record (mu1, mu2, frames, scale) per pixel of the luminance l of the frame's demodulated colour, reprojected and blended with the
+ * colour's own taps and weights (include/rsrt_temporal.h, rsrt_tp_moments); scale (mu2 - mu1^2) estimates the variance of the output's
+ * luminance.  The history and features such a frame writes are those of a plain frame, bit for bit.  Two more library-owned buffers
+ * (32 B a pixel) are allocated on the first MOMENTS frame and freed with the history.  A frame whose MOMENTS flag differs from the
+ * previous frame's drops the history (it acts as a first frame).  Unknown flags: RSRT_ERR_INVALID_ARGUMENT. */
+enum { RSRT_TEMPORAL_MOMENTS = 1u };
+rsrt_status rsrt_temporal_accumulate_ex(rsrt_context *ctx, const rsrt_camera *camera, uint32_t sample_total, uint32_t aov_sample_total,
+                                        const rsrt_temporal_params *params, uint32_t flags, void *hip_stream);
+/* the last frame's moment records to the host: W*H*4 floats (mu1, mu2, frames, scale); RSRT_ERR_NOT_READY when the last frame since
+ * the last reset carried none */
+rsrt_status rsrt_temporal_moments_download(rsrt_context *ctx, float *host_f32x4, size_t n_floats);
+/* rsrt_denoise_params.flags (include/rsrt_variance.h; both act only when iterations >= 1, iterations 0 still returns the mean):
+ *   RSRT_DENOISE_CLAMP     firefly clamp of the filter's input: a pixel whose luminance exceeds that of all 8 neighbours (and 0) is
+ *                          scaled down to the brightest neighbour's.
+ *   RSRT_DENOISE_VARIANCE  variance-guided levels (SVGF): the colour term compares luminance against sigma_color^2 times the 3x3 blur
+ *                          of a per-pixel variance, which every level filters along with the colour.  sigma_color is then sigma_l,
+ *                          of luminance in units of its standard deviation: default RSRT_SV_SIGMA_L 4.0 (no 2^i per level).  The
+ *                          variance comes from the temporal moments under RSRT_DENOISE_TEMPORAL (the last temporal frame must have
+ *                          carried them, otherwise RSRT_ERR_NOT_READY), or from the input's luminance itself; below 4 frames of
+ *                          history it is estimated over a 7x7 window.  Requires RSRT_DENOISE_DEMODULATE (RSRT_ERR_INVALID_ARGUMENT). */
+enum { RSRT_DENOISE_VARIANCE = 4u, RSRT_DENOISE_CLAMP = 8u };
 
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are

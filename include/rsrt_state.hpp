@@ -168,6 +168,9 @@ public:
         return out;
     }
     static rsrt_denoise_params denoise_defaults() { return rsrt_denoise_params{5u, RSRT_DENOISE_DEMODULATE, 2.0f, 0.5f, 0.3f}; }
+    // the variance-guided filter (rsrt.h RSRT_DENOISE_VARIANCE): sigma_color is sigma_l, 4.0 (RSRT_SV_SIGMA_L); add RSRT_DENOISE_CLAMP for
+    // the firefly clamp and RSRT_DENOISE_TEMPORAL (after render_temporal(n, p, true)) for the temporal moments
+    static rsrt_denoise_params variance_defaults() { return rsrt_denoise_params{5u, RSRT_DENOISE_DEMODULATE | RSRT_DENOISE_VARIANCE, 4.0f, 0.5f, 0.3f}; }
     // rsrt_denoise of the mean of sample_count() samples, guided by aov_sample_count() AOV samples: W*H*4 f32 (alpha 1)
     std::vector<float> denoise(const rsrt_denoise_params &p = denoise_defaults())
     {
@@ -181,10 +184,11 @@ public:
     // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass
     // (k only grows until temporal_reset: fresh random numbers every frame) and blend them with the reprojected history.  Resets the
     // history first when environment_index, max_bounces, flags or the size changed; afterwards sample_count() = aov_sample_count() = n
-    // and a later render_samples starts clean.  denoise() with RSRT_DENOISE_TEMPORAL in the flags filters the result.
-    void render_temporal(uint32_t n = 1, const rsrt_temporal_params &p = temporal_defaults())
+    // and a later render_samples starts clean.  denoise() with RSRT_DENOISE_TEMPORAL in the flags filters the result.  moments: keep the
+    // luminance moments too (RSRT_TEMPORAL_MOMENTS, download_temporal_moments); toggling it resets the history.
+    void render_temporal(uint32_t n = 1, const rsrt_temporal_params &p = temporal_defaults(), bool moments = false)
     {
-        const uint32_t key[5] = {environment_index, max_bounces, flags, width_, height_};
+        const uint32_t key[6] = {environment_index, max_bounces, flags, width_, height_, moments ? 1u : 0u};
         if (!have_temporal_key_ || std::memcmp(key, temporal_key_, sizeof key) != 0) {
             temporal_reset();
             std::memcpy(temporal_key_, key, sizeof key);
@@ -197,7 +201,7 @@ public:
         rsrt_camera_uniform(&camera_, &cam);
         check(rsrt_multi_render(m_, &cam, width_, height_, k, n, max_bounces, environment_index, flags));
         render_aov(k, n);
-        check_ctx(rsrt_temporal_accumulate(context(0), &cam, n, n, &p, nullptr));
+        check_ctx(rsrt_temporal_accumulate_ex(context(0), &cam, n, n, &p, moments ? RSRT_TEMPORAL_MOMENTS : 0u, nullptr));
         temporal_sample_count_ = k + n;
         sample_count_ = n;
         have_hash_ = false;
@@ -211,6 +215,12 @@ public:
     {
         std::vector<float> out((size_t)width_ * height_ * 4);
         check_ctx(rsrt_temporal_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    std::vector<float> download_temporal_moments() // W*H*4: mu1, mu2, frames, scale (the last frame must have carried moments)
+    {
+        std::vector<float> out((size_t)width_ * height_ * 4);
+        check_ctx(rsrt_temporal_moments_download(context(0), out.data(), out.size()));
         return out;
     }
     std::vector<uint8_t> denoised_display() // the last denoise() through the display pass
@@ -267,7 +277,7 @@ private:
     rsrt_camera_desc camera_{};
     uint32_t width_ = 0, height_ = 0, sample_count_ = 0, aov_sample_count_ = 0;
     bool have_aov_ = false;
-    uint32_t temporal_sample_count_ = 0, temporal_key_[5] = {0, 0, 0, 0, 0};
+    uint32_t temporal_sample_count_ = 0, temporal_key_[6] = {0, 0, 0, 0, 0, 0};
     bool have_temporal_key_ = false;
     size_t last_hash_ = 0;
     bool have_hash_ = false;

@@ -25,6 +25,7 @@
  *   nh = min((sum w Hn(q)) / wsum, max_history).
  *   Blend: out.rgb = (h nh + c S) / (nh + S), out.w = nh + S; without history out = (c, S).
  *   Stored for the next frame: out, and the features (n.xyz, z), or (0, 0, 0, -1) for sky.
+ *   With RSRT_TEMPORAL_MOMENTS the same taps also carry the luminance moments (rsrt_tp_moments, below).
  *
  * Defaults (what a zero-initialised caller should fill in; the Python and C++ State use them):
  *   max_history 32 samples (in [1, 2^24]), depth_tolerance tau_z 0.05 (in [1e-6, 1e6]), normal_tolerance tau_n 0.9 (in [-1, 1]).
@@ -37,6 +38,7 @@
 #define RSRT_TEMPORAL_H
 
 #include "rsrt_detmath.h"
+#include "rsrt_variance.h" /* rsrt_sv_frame_lum: the moments' luminance */
 
 #define RSRT_TP_MIN_WEIGHT 0.01f       /* below this much valid bilinear weight a pixel has no history */
 #define RSRT_TP_MAX_HISTORY 32u        /* defaults of rsrt_temporal_params */
@@ -140,10 +142,21 @@ RSRT_HD int rsrt_tp_current(const rsrt_tp_frame *fr, const float sum[3], const f
     return surface;
 }
 
+/* What rsrt_tp_pixel_m gathers besides the colour: nothing (the plain pass).  A gatherer sees the history exactly where the colour
+ * does: own(q) in the identity case, tap(q, w) for every valid bilinear tap, resolve(wsum) when the taps carry enough weight, and
+ * finally blend(used, nh, S), with used != 0 when the pixel has history and nh its (capped) weight. */
+struct rsrt_tp_no_moments {
+    RSRT_HD void own(unsigned) {}
+    RSRT_HD void tap(unsigned, float) {}
+    RSRT_HD void resolve(float) {}
+    RSRT_HD void blend(int, float, float) {}
+};
+
 /* One pixel.  Prev::col(q, float[4]) and Prev::feat(q, float[4]) load the previous history and features of pixel index q.  Writes the
- * new history (out) and features (f); returns an RSRT_TP_* code. */
-template <class Prev>
-RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int y, const float sum[3], const float aov[8], float out[4], float f[4])
+ * new history (out) and features (f); returns an RSRT_TP_* code.  mom gathers along (rsrt_tp_no_moments, rsrt_tp_moments). */
+template <class Prev, class Mom>
+RSRT_HD int rsrt_tp_pixel_m(const rsrt_tp_frame *fr, const Prev &prev, Mom &mom, int x, int y, const float sum[3], const float aov[8], float out[4],
+                            float f[4])
 {
     const unsigned w = fr->width, hh = fr->height;
     float c[3];
@@ -157,6 +170,7 @@ RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int 
         float hq[4];
         prev.col((unsigned)y * w + (unsigned)x, hq);
         h[0] = hq[0]; h[1] = hq[1]; h[2] = hq[2]; nh = hq[3];
+        mom.own((unsigned)y * w + (unsigned)x);
         code = RSRT_TP_IDENTITY;
     } else {
         float d[3], X[3], e[3], fx = 0.0f, fy = 0.0f;
@@ -196,6 +210,7 @@ RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int 
                 }
                 wsum = wsum + tw[t];
                 for (int i = 0; i < 4; i++) acc[i] = acc[i] + tw[t] * hq[i];
+                mom.tap(q, tw[t]);
             }
             if (wsum < RSRT_TP_MIN_WEIGHT) {
                 code = plane_rej ? RSRT_TP_PLANE_REJECTED : (normal_rej ? RSRT_TP_NORMAL_REJECTED : RSRT_TP_LOW_WEIGHT);
@@ -203,6 +218,7 @@ RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int 
                 for (int i = 0; i < 3; i++) h[i] = acc[i] / wsum;
                 nh = acc[3] / wsum;
                 nh = nh > fr->max_history ? fr->max_history : nh;
+                mom.resolve(wsum);
                 code = surface ? RSRT_TP_REPROJECTED : RSRT_TP_SKY;
             }
         }
@@ -210,10 +226,75 @@ RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int 
     if (code == RSRT_TP_IDENTITY || code == RSRT_TP_REPROJECTED || code == RSRT_TP_SKY) {
         for (int i = 0; i < 3; i++) out[i] = (h[i] * nh + c[i] * S) / (nh + S);
         out[3] = nh + S;
+        mom.blend(1, nh, S);
     } else {
         for (int i = 0; i < 3; i++) out[i] = c[i];
         out[3] = S;
+        mom.blend(0, nh, S);
     }
+    return code;
+}
+
+/* the plain pass (rt_temporal_kernel) */
+template <class Prev>
+RSRT_HD int rsrt_tp_pixel(const rsrt_tp_frame *fr, const Prev &prev, int x, int y, const float sum[3], const float aov[8], float out[4], float f[4])
+{
+    rsrt_tp_no_moments none;
+    return rsrt_tp_pixel_m(fr, prev, none, x, y, sum, aov, out, f);
+}
+
+/* The luminance moments (RSRT_TEMPORAL_MOMENTS, rt_temporal_moments_kernel): a float4 record (mu1, mu2, frames, scale) per pixel.
+ * l = rsrt_sv_lum of the frame's demodulated colour sum / S / max(a, RSRT_DN_ALBEDO_EPS) (rsrt_sv_frame_lum, with the current AOV
+ * record's mean albedo a).  mu1, mu2 and frames are reprojected with the colour's taps, weights and wsum (hm = (sum w m(q)) / wsum;
+ * identity: the pixel's own record) and blended with the colour's weights:
+ *   mu1' = (hm1 nh + l S) / (nh + S),  mu2' = (hm2 nh + (l l) S) / (nh + S),  frames' = hm3 + 1,  scale = S / (nh + S);
+ * without history (l, l l, 1, 1).  scale is the factor by which the spread of the per-frame means shrinks in the blended colour:
+ * scale (mu2 - mu1^2) estimates the variance of the output's luminance, and it goes to 0 as a still camera converges.
+ * Load::mom(q, float[4]) loads the previous record of pixel index q. */
+template <class Load>
+struct rsrt_tp_moments {
+    const Load *load;
+    float l;
+    float h[3];   /* the reprojected mu1, mu2, frames */
+    float out[4]; /* the new record */
+    RSRT_HD void own(unsigned q)
+    {
+        float m[4];
+        load->mom(q, m);
+        for (int i = 0; i < 3; i++) h[i] = m[i];
+    }
+    RSRT_HD void tap(unsigned q, float w)
+    {
+        float m[4];
+        load->mom(q, m);
+        for (int i = 0; i < 3; i++) h[i] = h[i] + w * m[i];
+    }
+    RSRT_HD void resolve(float wsum)
+    {
+        for (int i = 0; i < 3; i++) h[i] = h[i] / wsum;
+    }
+    RSRT_HD void blend(int used, float nh, float S)
+    {
+        const float l2 = l * l;
+        if (used) {
+            out[0] = (h[0] * nh + l * S) / (nh + S);
+            out[1] = (h[1] * nh + l2 * S) / (nh + S);
+            out[2] = h[2] + 1.0f;
+            out[3] = S / (nh + S);
+        } else {
+            out[0] = l; out[1] = l2; out[2] = 1.0f; out[3] = 1.0f;
+        }
+    }
+};
+
+/* one pixel of a MOMENTS frame: rsrt_tp_pixel's history and features, bit for bit, and the moment record (mout) */
+template <class Prev>
+RSRT_HD int rsrt_tp_pixel_moments(const rsrt_tp_frame *fr, const Prev &prev, int x, int y, const float sum[3], const float aov[8], float out[4],
+                                  float f[4], float mout[4])
+{
+    rsrt_tp_moments<Prev> mom = {&prev, rsrt_sv_frame_lum(sum, fr->sample_total, aov, fr->aov_sample_total), {0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+    const int code = rsrt_tp_pixel_m(fr, prev, mom, x, y, sum, aov, out, f);
+    for (int i = 0; i < 4; i++) mout[i] = mom.out[i];
     return code;
 }
 

@@ -757,6 +757,10 @@ struct rsrt_context {
     float4 *tp_buf = nullptr;
     uint32_t tp_w = 0, tp_h = 0, tp_cur = 0, tp_frames = 0;
     float tp_cam[13] = {0}; // pos, rot (column-major 3x3), fov_y
+    // the luminance moments (RSRT_TEMPORAL_MOMENTS): two float4 record buffers (allocated on the first MOMENTS frame, freed with the
+    // history) and whether the last frame carried them
+    float4 *tp_mom = nullptr;
+    uint32_t tp_moments = 0;
 };
 
 namespace {
@@ -978,12 +982,16 @@ void free_denoise_scratch(rsrt_context *ctx)
 void free_temporal(rsrt_context *ctx)
 {
     (void)hipFree(ctx->tp_buf);
+    (void)hipFree(ctx->tp_mom);
     ctx->tp_buf = nullptr;
-    ctx->tp_w = ctx->tp_h = ctx->tp_cur = ctx->tp_frames = 0;
+    ctx->tp_mom = nullptr;
+    ctx->tp_w = ctx->tp_h = ctx->tp_cur = ctx->tp_frames = ctx->tp_moments = 0;
 }
 
 // the temporal history of the last frame (valid when tp_frames > 0)
 float4 *temporal_history(rsrt_context *ctx) { return ctx->tp_buf + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
+// ... and its moment records (valid when tp_moments is set too)
+float4 *temporal_moments(rsrt_context *ctx) { return ctx->tp_mom + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
 
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -1344,6 +1352,7 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->aov_owned);
     (void)hipFree(ctx->dn_scratch);
     (void)hipFree(ctx->tp_buf);
+    (void)hipFree(ctx->tp_mom);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -2416,3 +2425,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rsrt_comm.h"
 #include "rt_denoise.h"
 #include "rt_temporal.h"
+#include "rt_variance.h"

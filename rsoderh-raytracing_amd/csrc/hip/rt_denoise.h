@@ -168,6 +168,10 @@ rsrt_status ensure_denoise_scratch(rsrt_context *ctx)
 
 bool sigma_ok(float s) { return s >= 1.0e-6f && s <= 1.0e6f; }
 
+// the clamp / variance pass and the L >= 1 levels after rt_dn_prepare_kernel wrote ping and feat (rt_variance.h)
+void sv_filter(rsrt_context *ctx, hipStream_t stream, const rsrt_denoise_params &p, bool temporal, float4 *ping, float4 *pong, const ushort4 *feat,
+               float4 *out, uint32_t w, uint32_t h, float aov_total);
+
 } // namespace
 
 extern "C" {
@@ -262,7 +266,10 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
     const rsrt_denoise_params &p = *params;
     if (p.iterations > 8u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: iterations %u (at most 8)", p.iterations);
-    if (p.flags & ~(uint32_t)(RSRT_DENOISE_DEMODULATE | RSRT_DENOISE_TEMPORAL)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: unknown flags 0x%x", p.flags);
+    if (p.flags & ~(uint32_t)(RSRT_DENOISE_DEMODULATE | RSRT_DENOISE_TEMPORAL | RSRT_DENOISE_VARIANCE | RSRT_DENOISE_CLAMP))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: unknown flags 0x%x", p.flags);
+    if ((p.flags & RSRT_DENOISE_VARIANCE) && !(p.flags & RSRT_DENOISE_DEMODULATE))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: RSRT_DENOISE_VARIANCE requires RSRT_DENOISE_DEMODULATE");
     const bool temporal = (p.flags & RSRT_DENOISE_TEMPORAL) != 0; // the temporal pass's colour (its weight channel is ignored), sample_total 1
     if (temporal) sample_total = 1u;
     if (!sigma_ok(p.sigma_color) || !sigma_ok(p.sigma_normal) || !sigma_ok(p.sigma_depth))
@@ -271,6 +278,8 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
     if ((uintptr_t)device_out_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: output pointer must be 16-byte aligned");
     if (temporal && (!ctx->tp_frames || ctx->tp_w != ctx->acc_w || ctx->tp_h != ctx->acc_h))
         return fail(ctx, RSRT_ERR_NOT_READY, "denoise: no temporal frame since the last reset (rsrt_temporal_accumulate first)");
+    if (temporal && (p.flags & RSRT_DENOISE_VARIANCE) && !ctx->tp_moments)
+        return fail(ctx, RSRT_ERR_NOT_READY, "denoise: the last temporal frame carried no moments (RSRT_TEMPORAL_MOMENTS)");
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
     rsrt_status st = ensure_denoise_scratch(ctx);
     if (st || (st = begin_work(ctx, stream))) return st;
@@ -284,13 +293,17 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
     const uint32_t L = p.iterations;
     rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(temporal ? temporal_history(ctx) : ctx->accum, ctx->aov, n, st_f, at_f, demod, L == 0, L == 0 ? out : ping, feat);
     const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
-    for (uint32_t i = 0; i < L; i++) {
-        const float4 *src = (i % 2u == 0u) ? ping : pong;
-        if (i + 1u == L)
-            rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov, out, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, at_f, demod);
-        else
-            rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov, (i % 2u == 0u) ? pong : ping, w, h, i, p.sigma_color, p.sigma_normal,
-                                                                  p.sigma_depth, at_f, demod);
+    if (L > 0 && (p.flags & (RSRT_DENOISE_VARIANCE | RSRT_DENOISE_CLAMP))) {
+        sv_filter(ctx, stream, p, temporal, ping, pong, feat, out, w, h, at_f);
+    } else {
+        for (uint32_t i = 0; i < L; i++) {
+            const float4 *src = (i % 2u == 0u) ? ping : pong;
+            if (i + 1u == L)
+                rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov, out, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, at_f, demod);
+            else
+                rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov, (i % 2u == 0u) ? pong : ping, w, h, i, p.sigma_color,
+                                                                      p.sigma_normal, p.sigma_depth, at_f, demod);
+        }
     }
     HIP_TRY(ctx, hipGetLastError());
     ctx->dn_last = out;

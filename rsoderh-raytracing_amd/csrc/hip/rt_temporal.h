@@ -6,6 +6,8 @@
 //                      taps of previous history and features (16 + 16 B each, mostly from the caches), and writes history and
 //                      features (32 B): about 112 B of unique traffic a pixel.  No LDS.  The per-pixel arithmetic is
 //                      include/rsrt_temporal.h.
+//  rt_temporal_moments_kernel  the same pass with the luminance moments (RSRT_TEMPORAL_MOMENTS): one float4 record more a pixel, read
+//                      through the same taps and written.
 #include "../../../include/rsrt_temporal.h"
 
 // the previous frame's buffers, as rsrt_tp_pixel reads them
@@ -38,7 +40,49 @@ __global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_temporal_kernel(rsrt_t
     out_feat[p] = make_float4(f[0], f[1], f[2], f[3]);
 }
 
+// the previous frame's buffers and moment records, as rsrt_tp_pixel_moments reads them
+struct TpPrevM : TpPrev {
+    const float4 *m_;
+    __host__ __device__ void mom(unsigned q, float o[4]) const
+    {
+        const float4 v = m_[q];
+        o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
+    }
+};
+
+// rt_temporal_kernel plus the luminance moments (RSRT_TEMPORAL_MOMENTS): 16 B more read (the previous record, per valid tap, mostly from
+// the caches) and 16 B more written a pixel.  History and features are the plain kernel's, bit for bit.
+__global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_temporal_moments_kernel(rsrt_tp_frame fr, const float4 *accum, const float4 *aov,
+                                                                                  const float4 *prev_col, const float4 *prev_feat,
+                                                                                  const float4 *prev_mom, float4 *out_col, float4 *out_feat,
+                                                                                  float4 *out_mom)
+{
+    const int x = (int)(blockIdx.x * RT_DN_BX + threadIdx.x), y = (int)(blockIdx.y * RT_DN_BY + threadIdx.y);
+    if (x >= (int)fr.width || y >= (int)fr.height) return;
+    const size_t p = (size_t)y * fr.width + (size_t)x;
+    const float4 s = accum[p];
+    const float sum[3] = {s.x, s.y, s.z};
+    float a[8], o[4], f[4], m[4];
+    dn_aov(aov, p, a);
+    TpPrevM prev;
+    prev.c_ = prev_col;
+    prev.f_ = prev_feat;
+    prev.m_ = prev_mom;
+    rsrt_tp_pixel_moments(&fr, prev, x, y, sum, a, o, f, m);
+    out_col[p] = make_float4(o[0], o[1], o[2], o[3]);
+    out_feat[p] = make_float4(f[0], f[1], f[2], f[3]);
+    out_mom[p] = make_float4(m[0], m[1], m[2], m[3]);
+}
+
 namespace {
+
+// the two moment buffers (float4 each), allocated on the first MOMENTS frame after ensure_temporal and freed with the history
+rsrt_status ensure_moments(rsrt_context *ctx)
+{
+    if (ctx->tp_mom) return RSRT_OK;
+    HIP_TRY(ctx, hipMalloc(&ctx->tp_mom, (size_t)ctx->tp_w * ctx->tp_h * 2u * sizeof(float4)));
+    return RSRT_OK;
+}
 
 // history 0, history 1, features 0, features 1 (float4 each) for the accumulator's size; a new allocation starts without history
 rsrt_status ensure_temporal(rsrt_context *ctx)
@@ -61,8 +105,16 @@ extern "C" {
 rsrt_status rsrt_temporal_accumulate(rsrt_context *ctx, const rsrt_camera *camera, uint32_t sample_total, uint32_t aov_sample_total,
                                      const rsrt_temporal_params *params, void *hip_stream)
 {
+    return rsrt_temporal_accumulate_ex(ctx, camera, sample_total, aov_sample_total, params, 0u, hip_stream);
+}
+
+rsrt_status rsrt_temporal_accumulate_ex(rsrt_context *ctx, const rsrt_camera *camera, uint32_t sample_total, uint32_t aov_sample_total,
+                                        const rsrt_temporal_params *params, uint32_t flags, void *hip_stream)
+{
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
+    if (flags & ~(uint32_t)RSRT_TEMPORAL_MOMENTS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: unknown flags 0x%x", flags);
+    const bool moments = (flags & RSRT_TEMPORAL_MOMENTS) != 0;
     if (!camera) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: camera is NULL");
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: params is NULL");
     if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: whole frame only (partition of %u ranks)", ctx->world);
@@ -81,6 +133,7 @@ rsrt_status rsrt_temporal_accumulate(rsrt_context *ctx, const rsrt_camera *camer
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: sample_total and aov_sample_total must be > 0");
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
     rsrt_status st = ensure_temporal(ctx);
+    if (!st && moments) st = ensure_moments(ctx);
     if (st || (st = begin_work(ctx, stream))) return st;
     const uint32_t w = ctx->acc_w, h = ctx->acc_h;
     const size_t n = (size_t)w * h;
@@ -100,15 +153,20 @@ rsrt_status rsrt_temporal_accumulate(rsrt_context *ctx, const rsrt_camera *camer
     fr.depth_tolerance = p.depth_tolerance;
     fr.normal_tolerance = p.normal_tolerance;
     fr.aspect = (float)w / (float)h;
-    fr.has_prev = ctx->tp_frames > 0;
+    fr.has_prev = ctx->tp_frames > 0 && ctx->tp_moments == (moments ? 1u : 0u); // (a MOMENTS toggle drops the history)
     fr.identity = fr.has_prev && rsrt_tp_same_camera(&fr.cur, &fr.prev); // (a resize frees the buffers, so W and H are the previous frame's)
     const uint32_t src = ctx->tp_cur, dst = src ^ 1u;
     float4 *hist = ctx->tp_buf, *feat = ctx->tp_buf + 2u * n;
     const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
-    rt_temporal_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, hist + dst * n, feat + dst * n);
+    if (moments)
+        rt_temporal_moments_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, ctx->tp_mom + src * n,
+                                                               hist + dst * n, feat + dst * n, ctx->tp_mom + dst * n);
+    else
+        rt_temporal_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, hist + dst * n, feat + dst * n);
     HIP_TRY(ctx, hipGetLastError());
     ctx->tp_cur = dst;
     ctx->tp_frames++;
+    ctx->tp_moments = moments ? 1u : 0u;
     memcpy(ctx->tp_cam, cam, sizeof cam);
     return end_work(ctx, stream);
 }
@@ -128,6 +186,18 @@ rsrt_status rsrt_temporal_download(rsrt_context *ctx, float *host, size_t n_floa
     if (!host || n_floats != (size_t)ctx->tp_w * ctx->tp_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal_download: expected %zu floats", (size_t)ctx->tp_w * ctx->tp_h * 4u);
     { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
     HIP_TRY(ctx, hipMemcpy(host, temporal_history(ctx), n_floats * sizeof(float), hipMemcpyDeviceToHost));
+    return RSRT_OK;
+}
+
+rsrt_status rsrt_temporal_moments_download(rsrt_context *ctx, float *host, size_t n_floats)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (!ctx->tp_buf || !ctx->tp_frames || !ctx->tp_moments || !ctx->tp_mom)
+        return fail(ctx, RSRT_ERR_NOT_READY, "the last temporal frame carried no moments (rsrt_temporal_accumulate_ex with RSRT_TEMPORAL_MOMENTS first)");
+    if (!host || n_floats != (size_t)ctx->tp_w * ctx->tp_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal_moments_download: expected %zu floats", (size_t)ctx->tp_w * ctx->tp_h * 4u);
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    HIP_TRY(ctx, hipMemcpy(host, temporal_moments(ctx), n_floats * sizeof(float), hipMemcpyDeviceToHost));
     return RSRT_OK;
 }
 

@@ -31,7 +31,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_multi_upload_scene", "rsrt_multi_upload_environment", "rsrt_multi_resize", "rsrt_multi_clear", "rsrt_multi_render",
             "rsrt_multi_synchronize", "rsrt_multi_download", "rsrt_multi_display_srgb8", "rsrt_multi_get_stats", "rsrt_multi_uses_rccl",
             "rsrt_aov_render", "rsrt_aov_bind", "rsrt_aov_clear", "rsrt_aov_download", "rsrt_denoise", "rsrt_denoised_download",
-            "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download"]
+            "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download",
+            "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download"]
 
 
 class RsrtError(RuntimeError):
@@ -49,6 +50,10 @@ AOV_FLOATS = 8  # per pixel: albedo sum xyz, hits, normal sum xyz, distance sum
 DENOISE_TEMPORAL = 2  # rsrt_denoise_params.flags: filter the temporal pass's colour instead of the accumulator's mean
 # rsrt_temporal_params defaults (include/rsrt_temporal.h)
 TEMPORAL_DEFAULTS = {"max_history": 32, "depth_tolerance": 0.05, "normal_tolerance": 0.9}
+TEMPORAL_MOMENTS = 1  # rsrt_temporal_accumulate_ex flags: keep the luminance moments too
+DENOISE_VARIANCE = 4  # rsrt_denoise_params.flags: variance-guided levels (include/rsrt_variance.h)
+DENOISE_CLAMP = 8     # ... and the firefly clamp of the filter's input
+VARIANCE_SIGMA_L = 4.0  # sigma_color's default under DENOISE_VARIANCE (RSRT_SV_SIGMA_L: SVGF's sigma_l)
 
 
 class TemporalParams(C.Structure):
@@ -155,6 +160,8 @@ def lib():
         L.rsrt_temporal_accumulate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rsrt_temporal_reset.argtypes = [C.c_void_p]
         L.rsrt_temporal_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_temporal_accumulate_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rsrt_temporal_moments_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -344,13 +351,18 @@ class State:
         return out
 
     def denoise(self, iterations=None, sigma_color=None, sigma_normal=None, sigma_depth=None, demodulate=None, sample_total=None,
-                aov_sample_total=None, out_ptr=None, stream=None, download=True, temporal=False):
+                aov_sample_total=None, out_ptr=None, stream=None, download=True, temporal=False, variance=False, clamp=False):
         """rsrt_denoise of the accumulator's mean, guided by the AOV buffer: [H, W, 4] float32 (alpha 1), or None with download=False
         (the result stays on the device: denoised_display_srgb8, or out_ptr when given).  Unset arguments take DENOISE_DEFAULTS and
-        the sample counters.  temporal=True: of the last render_temporal frame's colour instead (RSRT_DENOISE_TEMPORAL)."""
+        the sample counters.  temporal=True: of the last render_temporal frame's colour instead (RSRT_DENOISE_TEMPORAL).
+        variance=True: variance-guided levels (RSRT_DENOISE_VARIANCE; sigma_color is then sigma_l and defaults to VARIANCE_SIGMA_L; with
+        temporal=True the last frame must have been rendered with moments=True); clamp=True: the firefly clamp (RSRT_DENOISE_CLAMP)."""
         d = DENOISE_DEFAULTS
         pick = lambda v, k: d[k] if v is None else v  # noqa: E731
-        flags = (DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0) | (DENOISE_TEMPORAL if temporal else 0)
+        flags = (DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0) | (DENOISE_TEMPORAL if temporal else 0) \
+            | (DENOISE_VARIANCE if variance else 0) | (DENOISE_CLAMP if clamp else 0)
+        if sigma_color is None and variance:
+            sigma_color = VARIANCE_SIGMA_L
         p = DenoiseParams(pick(iterations, "iterations"), flags, pick(sigma_color, "sigma_color"), pick(sigma_normal, "sigma_normal"),
                           pick(sigma_depth, "sigma_depth"))
         n = self.sample_count if sample_total is None else sample_total
@@ -370,13 +382,14 @@ class State:
         return out
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
-    def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None):
+    def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):
         """One displayed frame of an interactive view: clears the accumulator and the AOV buffer, renders samples [k, k + n) of the
         current camera with the AOV pass (k = temporal_sample_count: fresh random numbers every frame) and blends them with the
         reprojected history (rsrt_temporal_accumulate).  Afterwards sample_count = aov_sample_count = n, and a later render_samples
         starts clean.  The history is reset first when environment_index, max_bounces, flags or the size changed since the last frame.
-        The result stays on the device: download_temporal, denoise(temporal=True)."""
-        key = (self.environment_index, self.max_bounces, self.flags, self.width, self.height)
+        The result stays on the device: download_temporal, denoise(temporal=True).  moments=True keeps the luminance moments too
+        (RSRT_TEMPORAL_MOMENTS: download_temporal_moments, denoise(temporal=True, variance=True)); toggling it resets the history."""
+        key = (self.environment_index, self.max_bounces, self.flags, self.width, self.height, bool(moments))
         if key != self._temporal_key:
             self.temporal_reset()
             self._temporal_key = key
@@ -390,8 +403,8 @@ class State:
         p = TemporalParams(d["max_history"] if max_history is None else max_history,
                            d["depth_tolerance"] if depth_tolerance is None else depth_tolerance,
                            d["normal_tolerance"] if normal_tolerance is None else normal_tolerance)
-        self._check(self._L.rsrt_temporal_accumulate(self._ctx, _p(self.camera), n, n, C.byref(p), C.c_void_p(stream) if stream else None),
-                    "rsrt_temporal_accumulate")
+        self._check(self._L.rsrt_temporal_accumulate_ex(self._ctx, _p(self.camera), n, n, C.byref(p), TEMPORAL_MOMENTS if moments else 0,
+                                                        C.c_void_p(stream) if stream else None), "rsrt_temporal_accumulate_ex")
         self.temporal_sample_count = k + n
         self.sample_count = n
         self._last_hash = None
@@ -405,6 +418,12 @@ class State:
         """The last temporal frame: [H, W, 4] float32 (colour, sample weight)."""
         out = np.empty((self.height, self.width, 4), np.float32)
         self._check(self._L.rsrt_temporal_download(self._ctx, _p(out), out.size), "rsrt_temporal_download")
+        return out
+
+    def download_temporal_moments(self):
+        """The last temporal frame's luminance moments (render_temporal(moments=True)): [H, W, 4] float32 (mu1, mu2, frames, scale)."""
+        out = np.empty((self.height, self.width, 4), np.float32)
+        self._check(self._L.rsrt_temporal_moments_download(self._ctx, _p(out), out.size), "rsrt_temporal_moments_download")
         return out
 
     # -- results ---------------------------------------------------------------------------------
