@@ -93,7 +93,7 @@ __device__ __forceinline__ SceneView<LDS> make_view(const DevScene &sc);
 template <>
 __device__ __forceinline__ SceneView<true> make_view<true>(const DevScene &sc)
 {
-    SceneView<true> v; // image order: nodes | escape links | primitive records | triangle normals | materials | fallback records | flat leaves
+    SceneView<true> v; // image order: nodes | escape links | primitive records | triangle normals | materials | fallback records | flat leaves | oriented leaves
     v.o_nodes = 0;
     v.o_esc = v.o_nodes + 2u * sc.n_nodes;
     v.o_prims = v.o_esc + (8u * sc.n_nodes + 3u) / 4u;
@@ -319,6 +319,8 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_render_kernel(RenderParams P)
 // LDS of the 1024-thread walk kernels (hybrid scene view): sixteen waves' pools and beside them the traversal's part of the scene
 static constexpr size_t kHybridPoolBytes = (size_t)(1024 / RT_WAVE) * 4u * ((size_t)H_COUNT * RT_WALK_POOL + pool_list_dwords(4));
 static constexpr uint32_t kHybridRoomF4 = (uint32_t)((160 * 1024 - kHybridPoolBytes) / sizeof(float4));
+// A small scene's whole image goes to LDS while it stays within this (the room beside the flat kernel's sixteen 192-slot pools)
+static constexpr size_t kSmallImageBytes = 24 * 1024;
 // ... and of the cooperative walk's kernel (TRAV 6): 128-slot pools with their two work stacks
 #ifndef RT_COOP_POOL
 #define RT_COOP_POOL 128u // (build-time A/B: -DRT_COOP_POOL=96u with RSRT_WPS=5 fits a fifth wave per SIMD beside 256-thread workgroups)
@@ -726,6 +728,7 @@ struct rsrt_context {
     uint32_t coop_lds_cap = RT_COOP_NCAP, coop_lifo_at = RT_COOP_LIFO_AT, coop_narrow_at = RT_COOP_NARROW_AT; // RSRT_COOP_LDS_CAP / _LIFO_AT / _NARROW_AT (tests: force the node queue's spill / newest-first / one-item trips)
     uint32_t coop_gcap = RT_COOP_GCAP; // RSRT_COOP_GCAP (tests: a small arena block forces the overflow guard, rt_coop.h coop_overflow)
     bool allow_flat = true;
+    bool flat_oriented = true; // RSRT_FLAT_ORIENTED=0: the flat loop orders each box's slab values itself instead of reading octant tables (A/B)
     bool allow_hybrid = true;
     uint32_t trace_budget = 0; // traversal steps per TRACE invocation before a ray is re-queued (0: 6 for the fixed-order walk, 12 for the tree walks)
     uint32_t descend_quorum = 30; // fixed-order / wide walk: a descending round ends once fewer than this percentage of its lanes are still descending
@@ -1311,6 +1314,7 @@ rsrt_status rsrt_context_create(int device_index, rsrt_context **out)
     if (const char *hy = getenv("RSRT_HYBRID")) ctx->allow_hybrid = atoi(hy) != 0; // 0: mid-size scenes read everything from global memory (A/B)
     if (const char *ty = getenv("RSRT_TRAVERSAL")) ctx->max_traversal = atoi(ty); // cap: 0 generic tree walk, 1 typed leaf loops, 2 + flat small-scene loop, 3 + fixed-order walk (A/B)
     if (const char *fl = getenv("RSRT_FLAT")) ctx->allow_flat = atoi(fl) != 0; // 0: small scenes take the walk a big scene would (A/B)
+    if (const char *fo = getenv("RSRT_FLAT_ORIENTED")) ctx->flat_oriented = atoi(fo) != 0; // 0: no per-octant leaf tables (A/B)
     if (const char *tb = getenv("RSRT_TRACE_BUDGET")) { int v = atoi(tb); if (v > 0) ctx->trace_budget = (uint32_t)v; }
     if (const char *dq = getenv("RSRT_DESCEND_QUORUM")) { int v = atoi(dq); if (v >= 0 && v <= 100) ctx->descend_quorum = (uint32_t)v; }
     if (const char *sq = getenv("RSRT_STOP_QUORUM")) { int v = atoi(sq); if (v >= 0 && v <= 100) ctx->stop_quorum = (uint32_t)v; }
@@ -1525,6 +1529,15 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
         }
     }
     const size_t flat_f4 = flat_ok ? 2 * leaf_nodes.size() : 0, rank_f4 = flat_ok ? 32 : 0;
+    // The leaf boxes once more for each ray-sign octant q (bit 0 x, bit 1 y, bit 2 z, as trace_flat computes it), corners in slab
+    // order: {near.xyz, mask lo}{far.xyz, mask hi}, near = the max corner on the axes whose bit is set.  Tables are 2 x an odd
+    // number of float4s apart, so the eight octants' copies of one leaf lie in eight different 16-byte cells of LDS's 256-byte bank
+    // row (a ds_read_b128 of a wave of mixed octants has no bank conflict).  Only where the image with them still fits beside the
+    // path pools: a scene they would push out of LDS keeps the loop that orders the values itself.
+    const size_t ostride_f4 = 2 * (leaf_nodes.size() | 1);
+    const size_t oflat_f4 = flat_ok && ctx->flat_oriented ? 8 * ostride_f4 : 0;
+    const size_t base_f4 = 2ull * n_nodes + 4ull * n_primitives + 3ull * n_triangles + 4ull * n_materials + 4ull * n_spheres + 4ull * n_planes + esc_f4 + flat_f4;
+    const bool flat_oriented = oflat_f4 != 0 && (base_f4 + oflat_f4) * sizeof(float4) <= kSmallImageBytes;
     // ---- fixed-order traversal (rt_device.h, trace_preorder): per-octant visiting rank of EVERY primitive record — the
     // position at which the reference's near-child-first walk meets it — which decides equal t whatever order the records
     // are really tested in; and the skip links of the pre-order node array (next node once an interior node is missed).
@@ -1626,7 +1639,7 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
     // the wide walks' LDS image: the head of the wide-node array (hottest first), as far as the room beside the launch's pools goes (hybrid_stage)
     const uint32_t wimg_nodes = wide_ok ? (uint32_t)wide.size() : 0u;
     // ---- build the device image: nodes | prims | escape links | tri normals | materials | fb spheres | fb planes
-    const size_t n_f4 = 2ull * n_nodes + 4ull * n_primitives + 3ull * n_triangles + 4ull * n_materials + 4ull * n_spheres + 4ull * n_planes + esc_f4 + flat_f4;
+    const size_t n_f4 = base_f4 + (flat_oriented ? oflat_f4 : 0);
     std::vector<float4> img(n_f4 + rank_f4 + pnode_f4 + prank_f4 + wnode_f4); // what follows the LDS image: flat ranks | pre-order nodes | record ranks | wide nodes
     float4 *p = img.data();
     float4 *p_nodes = p;
@@ -1689,6 +1702,16 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
             p[1] = f4(nd.bounds_max[0], nd.bounds_max[1], nd.bounds_max[2], u2f((uint32_t)(lm >> 32)));
             p += 2;
         }
+        if (flat_oriented) {
+            for (uint32_t q = 0; q < 8; q++)
+                for (size_t k = 0; k < leaf_nodes.size(); k++) {
+                    const float4 lo = p_flat[2 * k], hi = p_flat[2 * k + 1];
+                    float4 *c = p + q * ostride_f4 + 2 * k;
+                    c[0] = f4(q & 1u ? hi.x : lo.x, q & 2u ? hi.y : lo.y, q & 4u ? hi.z : lo.z, lo.w);
+                    c[1] = f4(q & 1u ? lo.x : hi.x, q & 2u ? lo.y : hi.y, q & 4u ? lo.z : hi.z, hi.w);
+                }
+            p += oflat_f4;
+        }
         memcpy(p, flat_rank.data(), flat_rank.size() * sizeof(uint32_t));
     }
     // The cooperative walk (rt_coop.h) folds an extension ray's hits with an atomic minimum and sends a ray that sees two records at the same
@@ -1743,6 +1766,7 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
     sc.fb_planes = ctx->scene_blob + (p_fbp - img.data());
     sc.escape = ctx->scene_blob + (p_esc - img.data());
     sc.flat_leaves = ctx->scene_blob + (p_flat - img.data());
+    sc.flat_ostride = flat_oriented ? (uint32_t)ostride_f4 : 0u;
     sc.flat_rank = reinterpret_cast<const uint32_t *>(ctx->scene_blob + n_f4);
     sc.pnodes = ctx->scene_blob + n_f4 + rank_f4;
     sc.n_pnodes = n_pnodes;
@@ -1794,7 +1818,7 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials,
     sc.typed_leaves = typed_leaves ? 1u : 0u;
     const size_t stack_bytes = (size_t)sc.stack_entries * RT_BLOCK * sizeof(uint32_t);
     if (stack_bytes > 128 * 1024) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh depth %u exceeds the supported traversal stack", depth);
-    sc.lds_float4s = (n_f4 * sizeof(float4) <= 24 * 1024) ? (uint32_t)n_f4 : 0u; // whole image in LDS only while it leaves room for the path pools
+    sc.lds_float4s = (n_f4 * sizeof(float4) <= kSmallImageBytes) ? (uint32_t)n_f4 : 0u; // whole image in LDS only while it leaves room for the path pools
     sc.lds_hybrid = 0;
     sc.lds_src = sc.nodes; // the image starts with the nodes
     ctx->hybrid_head_f4 = ctx->hybrid_pnode_f4 = 0;

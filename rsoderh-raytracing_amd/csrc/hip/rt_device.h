@@ -57,7 +57,8 @@ struct DevScene {
     const float4 *fb_spheres;  // 4 per sphere, scene order (cast_ray's brute-force loop)
     const float4 *fb_planes;   // 4 per plane
     const float4 *escape;      // 8 octants x n_nodes u32 'next node when this subtree is done', packed 4 per float4
-    const float4 *flat_leaves; // 2 per leaf: {min.xyz, record mask lo}{max.xyz, record mask hi} (trace_flat)
+    const float4 *flat_leaves; // 2 per leaf: {min.xyz, record mask lo}{max.xyz, record mask hi} (trace_flat); then, if flat_ostride != 0,
+                               // 8 octant tables flat_ostride float4s apart, leaf k at 2k: {near.xyz, mask lo}{far.xyz, mask hi}
     uint32_t n_nodes, n_prims, n_tris, n_materials, n_spheres, n_planes;
     uint32_t stack_entries;    // per-lane traversal stack entries (tree depth + 1)
     uint32_t lds_float4s;      // float4 count of the LDS image (0 = scene stays in global memory)
@@ -88,6 +89,10 @@ struct DevScene {
     uint32_t coop_ok;   // ... and the cooperative walk (rt_coop.h, TRAV 6) can name every record and node in its 32-bit work items
     // the wide walk's LDS image (lds_hybrid == 3): the first lds_wnodes wide nodes; everything else is read from global memory
     uint32_t lds_wnodes;
+    // flat traversal: 0, or the stride of the per-octant leaf tables after flat_leaves (the boxes' corners in slab order for a ray-sign
+    // octant: no min / max to order the slab values); 0 where the image with them would not fit beside the pools, or RSRT_FLAT_ORIENTED=0
+    // (a member of its own down here: placed next to n_leaves it cost the flat kernels scratch memory, the kernel arguments' SGPRs shifting)
+    uint32_t flat_ostride;
     const float4 *lds_src; // what stage_scene_lds copies (lds_float4s float4s): the image, nodes | escape links, or the pre-order nodes
 };
 
@@ -1140,7 +1145,8 @@ RT_DEV void trace_threaded_typed(DBG_DECL const View &S, uint32_t n_nodes, V3 o,
 // primitive records (all three scenes the reference ships) the walk is replaced by
 //   1. one wave-uniform loop over the leaf boxes — no cursor, no escape links, no per-lane node
 //      fetch: the box is the same for all lanes (an LDS broadcast read), every lane with a ray
-//      is busy in every trip, and min/max replace the compare-and-swap (no NaN can occur);
+//      is busy in every trip, and min/max replace the compare-and-swap (no NaN can occur) — or, with the per-octant leaf
+//      tables, the lane's table already holds each box's corners in slab order;
 //   2. a 64-bit mask of the records to test (OR of the hit leaves' masks), split by type, walked with
 //      ctz in three homogeneous loops as in trace_threaded_typed.
 // Order only matters for equal t: then the record that comes first in this octant's depth-first order
@@ -1178,21 +1184,47 @@ RT_DEV void trace_flat(DBG_DECL const View &S, const DevScene &sc, V3 o, V3 d, V
             if (__ballot(!resumed & !(t_0 > t_1)) != 0ull) active |= sc.cull_mask[g];
         }
     }
+    if (sc.flat_ostride != 0u) { // (wave-uniform)
+        // This lane's octant table holds each box with the corner on the ray's near side first: 1/d is finite here and f32
+        // subtraction and multiplication are monotone, so (near - o) * inv <= (far - o) * inv on every axis, and each value below is
+        // exactly the fminf / fmaxf of the loop after this one (up to the sign of a zero, which the comparison does not see): the
+        // same decision without the six min / max.  A wave of mixed octants reads up to eight addresses a box; the tables' stride
+        // puts them in eight different 16-byte cells of the 256-byte bank row, so the read costs the LDS what a broadcast does.
+        const uint32_t octant = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
+        const uint32_t table = 2u * sc.n_leaves + octant * sc.flat_ostride; // (the tables follow the leaves)
+#pragma unroll 4
+        for (uint32_t L = 0; L < n_leaves; L++) {
+            if (!((active >> L) & 1u)) continue; // (wave-uniform)
+            RT_MARK(5);
+            DBG_WAVE_TICK(10);
+            DBG_ADD(11, 1);
+            const float4 n0 = S.flat(table + 2u * L), n1 = S.flat(table + 2u * L + 1u);
+            const float ax = (n0.x - o.x) * inv.x, bx = (n1.x - o.x) * inv.x;
+            const float ay = (n0.y - o.y) * inv.y, by = (n1.y - o.y) * inv.y;
+            const float az = (n0.z - o.z) * inv.z, bz = (n1.z - o.z) * inv.z;
+            const float t_0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(ax, ay), az), 0.0f);
+            const float t_1 = __builtin_fminf(__builtin_fminf(__builtin_fminf(bx, by), bz), RT_INFINITY); // (not a no-op: a box entered beyond RT_INFINITY is missed)
+            const uint32_t keep = t_0 > t_1 ? 0u : 0xffffffffu;
+            all_lo |= as_u(n0.w) & keep;
+            all_hi |= as_u(n1.w) & keep;
+        }
+    } else {
 #pragma unroll 4 // ( -1.3 % against 1 with the 1024-thread workgroups; it measured the same with 256-thread ones)
-    for (uint32_t L = 0; L < n_leaves; L++) {
-        if (!((active >> L) & 1u)) continue; // (wave-uniform)
-        RT_MARK(5);
-        DBG_WAVE_TICK(10);
-        DBG_ADD(11, 1);
-        const float4 n0 = S.flat(2u * L), n1 = S.flat(2u * L + 1u);
-        const float ax = (n0.x - o.x) * inv.x, bx = (n1.x - o.x) * inv.x;
-        const float ay = (n0.y - o.y) * inv.y, by = (n1.y - o.y) * inv.y;
-        const float az = (n0.z - o.z) * inv.z, bz = (n1.z - o.z) * inv.z;
-        const float t_0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax, bx), __builtin_fminf(ay, by)), __builtin_fminf(az, bz)), 0.0f);
-        const float t_1 = __builtin_fminf(__builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax, bx), __builtin_fmaxf(ay, by)), __builtin_fmaxf(az, bz)), RT_INFINITY);
-        const bool miss = t_0 > t_1;
-        all_lo |= miss ? 0u : as_u(n0.w); // .w: the leaf's records as a 64-bit mask
-        all_hi |= miss ? 0u : as_u(n1.w);
+        for (uint32_t L = 0; L < n_leaves; L++) {
+            if (!((active >> L) & 1u)) continue; // (wave-uniform)
+            RT_MARK(5);
+            DBG_WAVE_TICK(10);
+            DBG_ADD(11, 1);
+            const float4 n0 = S.flat(2u * L), n1 = S.flat(2u * L + 1u);
+            const float ax = (n0.x - o.x) * inv.x, bx = (n1.x - o.x) * inv.x;
+            const float ay = (n0.y - o.y) * inv.y, by = (n1.y - o.y) * inv.y;
+            const float az = (n0.z - o.z) * inv.z, bz = (n1.z - o.z) * inv.z;
+            const float t_0 = __builtin_fmaxf(__builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(ax, bx), __builtin_fminf(ay, by)), __builtin_fminf(az, bz)), 0.0f);
+            const float t_1 = __builtin_fminf(__builtin_fminf(__builtin_fminf(__builtin_fmaxf(ax, bx), __builtin_fmaxf(ay, by)), __builtin_fmaxf(az, bz)), RT_INFINITY);
+            const bool miss = t_0 > t_1;
+            all_lo |= miss ? 0u : as_u(n0.w); // .w: the leaf's records as a 64-bit mask
+            all_hi |= miss ? 0u : as_u(n1.w);
+        }
     }
     RT_MARK(6);
     const unsigned long long all_m = resumed ? rem : (((unsigned long long)all_hi << 32) | all_lo);
