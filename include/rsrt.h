@@ -79,7 +79,7 @@ typedef struct rsrt_stats {
     double total_kernel_ms;
     uint32_t launches;     /* kernel launches since the previous rsrt_get_stats */
     uint32_t _pad;
-    double trace_kernel_ms;   /* part of kernel_ms spent in the path-tracing kernel (rt_render_kernel) */
+    double trace_kernel_ms;   /* part of kernel_ms spent in the path-tracing kernel (rt_render_pool_kernel) */
     double resolve_kernel_ms; /* part spent in the ordered sample resolve (rt_resolve_kernel) */
     double reduce_ms;         /* HIP-event time of rsrt_comm_reduce calls (the RCCL reduce of the accumulators) */
     uint64_t traversal_steps; /* box tests + primitive tests of the BVH walks (0 where the flat small-scene loop runs:

@@ -1,14 +1,12 @@
 // rsrt_api.hip — kernels + C-ABI of librsrt.so (include/rsrt.h).  gfx950 only.
 //
 // Kernel design:
-//  rt_render_kernel   persistent path-tracing kernel.  A workgroup is 4 waves; every WAVE pulls
-//                     chunks (one owned framebuffer tile x a block of sample indices) from one
-//                     global atomic counter.  Lanes own one path each; when a lane's path ends it
-//                     is refilled with the next (pixel, sample) of the wave's chunk — work is
-//                     handed to the idle lanes with a wave64 ballot + prefix popcount, no LDS or
-//                     atomics involved.  Each finished path stores its radiance to the sample
-//                     buffer [sample][pixel slot]; nothing is accumulated in flight, so any lane
-//                     may take any sample and the result cannot depend on scheduling.
+//  rt_render_pool_kernel persistent path-tracing kernel (rt_wavepool.h).  Every WAVE pulls chunks
+//                     (one owned framebuffer tile x a block of sample indices) from one global
+//                     atomic counter into its pool of path slots.  Each finished path stores its
+//                     radiance to the sample buffer [sample][pixel slot]; nothing is accumulated in
+//                     flight, so any lane may take any sample and the result cannot depend on
+//                     scheduling.
 //  rt_resolve_kernel  adds the buffered samples of every owned pixel into the RGBA32F
 //                     accumulator in increasing sample order — the exact f32 sum that
 //                     `sample_count` successive reference frames produce (shader.wgsl:1367-1371).
@@ -36,7 +34,7 @@
                           // bigger pool wins even where it takes LDS from the top block (15 k-triangle scene: 161 instead of 352 wide nodes staged, same time)
 #endif
 #ifndef RT_BIG_POOL
-#define RT_BIG_POOL 192u // RSRT_KERNEL=4: 1024-thread workgroups, this many slots per wave
+#define RT_BIG_POOL 192u // the default form for a scene whose whole image fits LDS: 1024-thread workgroups, this many slots per wave
 #endif
 
 struct RenderParams {
@@ -160,161 +158,6 @@ __device__ __forceinline__ void start_path(const RenderParams &P, uint32_t px, u
     s.bounce = 0;
 }
 
-template <bool LDS>
-__global__ __launch_bounds__(RT_BLOCK) void rt_render_kernel(RenderParams P)
-{
-    const DevScene &sc = P.scene;
-    if (LDS) stage_scene_lds(sc);
-    const SceneView<LDS> S = make_view<LDS>(sc);
-    uint32_t *stack = reinterpret_cast<uint32_t *>(rt_smem + sc.lds_float4s) + threadIdx.x;
-    const uint32_t stride = RT_BLOCK;
-    const uint32_t lane = threadIdx.x & (RT_WAVE - 1);
-    const bool prune = (P.flags & RSRT_FLAG_PRUNE) != 0;
-    const bool anyhit_shadow = !(P.flags & RSRT_FLAG_REFERENCE_TRAVERSAL);
-    const uint32_t tile_px = P.tile_w * P.tile_h;
-
-    // wave-uniform chunk cursor
-    uint32_t chunk_next = 0, chunk_left = 0, chunk_tile_slot0 = 0, chunk_tx0 = 0, chunk_ty0 = 0, chunk_s0 = 0, chunk_p0 = 0;
-    bool exhausted = false;
-
-    PathState ps;
-    bool active = false;
-    unsigned long long n_paths = 0, n_ext = 0, n_shadow = 0;
-
-    for (;;) {
-        // ---------------- refill idle lanes from the wave's chunk (ballot + prefix popcount)
-        while (!exhausted) {
-            unsigned long long need = __ballot(!active);
-            if (need == 0ull) break;
-            if (chunk_left == 0u) {
-                uint32_t c = 0;
-                if (lane == (uint32_t)__builtin_ctzll(need)) c = atomicAdd(P.work_counter, 1u);
-                c = __builtin_amdgcn_readlane((int)c, __builtin_ctzll(need));
-                if (c >= P.n_chunks) { exhausted = true; break; }
-                const uint32_t q = c % P.n_subtiles, cb = c / P.n_subtiles; // sub-tile, then (tile, sample block)
-                uint32_t j = cb / P.n_sblocks, b = cb % P.n_sblocks; // owned-tile ordinal, sample block
-                uint32_t ttx, tty;
-                if (!owned_tile(j, P.rank, P.world, P.skew, P.tiles_x, P.tiles_per_row, ttx, tty)) continue; // padding slot: next chunk
-                chunk_tx0 = ttx * P.tile_w;
-                chunk_ty0 = tty * P.tile_h;
-                chunk_tile_slot0 = j * tile_px;
-                chunk_s0 = b * P.samples_per_chunk;
-                uint32_t ns = min(P.samples_per_chunk, P.sample_count - chunk_s0);
-                chunk_p0 = q * P.chunk_px;
-                chunk_next = 0;
-                chunk_left = ns * P.chunk_px;
-            }
-            uint32_t n_need = (uint32_t)__popcll(need);
-            uint32_t take = min(n_need, chunk_left);
-            uint32_t rank = (uint32_t)__popcll(need & ((1ull << lane) - 1ull));
-            if (!active && rank < take) {
-                uint32_t item = chunk_next + rank;
-                uint32_t k = item / P.chunk_px, p = chunk_p0 + item % P.chunk_px;
-                uint32_t px = chunk_tx0 + p % P.tile_w, py = chunk_ty0 + p / P.tile_w;
-                if (px < P.width && py < P.height) {
-                    uint32_t srel = chunk_s0 + k;
-                    start_path(P, px, py, P.sample_begin + srel, ps);
-                    ps.slot = srel * P.n_slots + chunk_tile_slot0 + p;
-                    active = true;
-                    n_paths++;
-                }
-            }
-            chunk_next += take;
-            chunk_left -= take;
-        }
-        if (__ballot(active) == 0ull) break;
-
-        // ---------------- extension ray: cast_ray (shader.wgsl:1221)
-        Hit hit;
-        hit.t = RT_INFINITY;
-        if (active) {
-            trace_closest(S, sc, ps.o, ps.d, prune, stack, stride, hit);
-            n_ext++;
-        }
-        bool finished = false;
-        bool want_shadow = false;
-        Surface surf;
-        BsdfMaterial mat;
-        EnvironmentSample es;
-        float cos_nee = 0.0f;
-        if (active) {
-            if (!hit.did_hit()) { // escaped: shader.wgsl:1222-1231
-                float u, v;
-                direction_to_equirectangular_uv(ps.d, u, v);
-                V3 sky = sample_env_bilinear(P.env, u, v);
-                float pdf = environment_direction_pdf(P.env, ps.d, u, v);
-                float w = power_heuristic(ps.last_pdf, pdf);
-                ps.light = ps.light + ps.throughput * sky * w;
-                finished = true;
-            } else {
-                surf = resolve_hit(S, hit, ps.o, ps.d);
-                mat = load_material(S, surf.material_id);
-                ps.light = ps.light + ps.throughput * mat.emission; // :1236
-                es = sample_environment(P.env, ps.rng);             // :1240
-                cos_nee = fmax_(0.0f, dot(surf.normal, es.direction));
-                want_shadow = cos_nee > 0.0f && es.pdf > 0.0f;      // :1246-1247
-            }
-        }
-        // ---------------- NEE shadow query: cast_ray_bvh from the hit point (:1249)
-        bool occluded = false;
-        if (active && want_shadow) {
-            Hit sh;
-            if (anyhit_shadow) trace_bvh<true>(S, surf.point, es.direction, prune, stack, stride, sh);
-            else trace_bvh<false>(S, surf.point, es.direction, prune, stack, stride, sh);
-            occluded = sh.did_hit();
-            n_shadow++;
-        }
-        if (active && !finished) {
-            if (want_shadow && !occluded) { // :1251-1265
-                Frame frame = make_frame(surf.normal);
-                V3 wo = to_frame_local(frame, -ps.d);
-                V3 wi = to_frame_local(frame, es.direction);
-                V3 scattering = bsdf_eval_local(wo, wi, mat);
-                float pdf_bsdf = bsdf_pdf_local(wo, wi, mat);
-                float w = power_heuristic(es.pdf, pdf_bsdf);
-                ps.light = ps.light + ps.throughput * w * es.radiance * scattering * cos_nee / es.pdf;
-            }
-            BsdfSample bs = bsdf_sample(ps.d, surf.normal, mat, ps.rng); // :1270
-            if (bs.dir.x == 0.0f && bs.dir.y == 0.0f && bs.dir.z == 0.0f) {
-                ps.light = bs.scattering; // debug colour overwrites, :1274
-                finished = true;
-            } else if (bs.pdf <= 0.0f) {
-                finished = true;
-            } else {
-                float c = fmax_(0.0f, dot(surf.normal, bs.dir));
-                ps.throughput = ps.throughput * (bs.scattering * (c / bs.pdf));
-                if (length(ps.throughput) < 0.001f) finished = true;
-                else {
-                    ps.last_pdf = bs.pdf;
-                    ps.o = surf.point;
-                    ps.d = bs.dir;
-                }
-            }
-            ps.bounce++;
-            if (ps.bounce >= P.max_bounces) finished = true;
-        }
-        if (active && finished) {
-            float *dst = P.sample_buf + (size_t)ps.slot * 3u;
-            dst[0] = ps.light.x;
-            dst[1] = ps.light.y;
-            dst[2] = ps.light.z;
-            active = false;
-        }
-    }
-
-    // per-wave reduction of the counters, one atomic per wave and counter
-    for (int off = 32; off > 0; off >>= 1) {
-        n_paths += __shfl_down(n_paths, off);
-        n_ext += __shfl_down(n_ext, off);
-        n_shadow += __shfl_down(n_shadow, off);
-    }
-    if (lane == 0) {
-        atomicAdd(&P.stats[0], n_paths);
-        atomicAdd(&P.stats[1], n_ext);
-        atomicAdd(&P.stats[2], n_shadow);
-    }
-}
-
 #include "rt_wavepool.h"
 // LDS of the 1024-thread walk kernels (hybrid scene view): sixteen waves' pools and beside them the traversal's part of the scene
 static constexpr size_t kHybridPoolBytes = (size_t)(1024 / RT_WAVE) * 4u * ((size_t)H_COUNT * RT_WALK_POOL + pool_list_dwords(4));
@@ -357,7 +200,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_resolve_kernel(RenderParams P, fl
 }
 
 // The ray-query probe.  SV / TRAV as in rt_render_pool_kernel (where the scene is read from, which traversal
-// runs); TRAV == 4 is the first kernel's stack walk.  mode bit 0: cast_ray_bvh only (no brute-force fallback).
+// runs); TRAV == 4 is the per-lane stack walk (trace_bvh).  mode bit 0: cast_ray_bvh only (no brute-force fallback).
 template <int SV, int TRAV>
 __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_kernel(DevScene sc, uint32_t n, const float *origins, const float *dirs,
                                                                 uint32_t mode, uint32_t flags, uint32_t repeat, rsrt_hit *out)
@@ -372,7 +215,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_kernel(DevScene sc, uin
     const bool prune = (flags & RSRT_FLAG_PRUNE) != 0;
     Hit h;
     h.t = RT_INFINITY; h.ref = 0; h.src = SRC_BVH; h.u = h.v = 0.0f;
-    if (TRAV == 4) { // the stack traversal of the first kernel
+    if (TRAV == 4) { // the per-lane stack traversal
         trace_bvh<false>(S, o, d, prune, stack, RT_BLOCK, h);
     } else { // what the production kernel's TRACE stage runs, resumed until done as the scheduler would
 #ifdef RT_INSTRUMENT
@@ -381,7 +224,7 @@ __global__ __launch_bounds__(RT_BLOCK) void rt_cast_rays_kernel(DevScene sc, uin
         uint32_t cur = 0, work = 0;
         unsigned long long flat_rem = 0ull;
         uint32_t wmem[RT_WSTATE_WORDS]; // (the wide walk parks its stack here between calls, as the pool kernel does in the slot's cold columns)
-        constexpr int T = TRAV; // (probe numbering: 4 is the first kernel's stack walk, handled above; 5 the wide walk — the form whose stack may overflow, which takes any tree)
+        constexpr int T = TRAV; // (probe numbering: 4 is the per-lane stack walk, handled above; 5 the wide walk — the form whose stack may overflow, which takes any tree)
         while (cur != RT_END) trace_dispatch<T>(DBG_ARG S, sc, o, d, prune, false, T >= 4 ? 2u : 12u, 50u, cur, h, nullptr, work, flat_rem, wmem, 1u, 60u);
         // RSRT_PROBE_REPEAT (tools/trace_rate.py): the same query again and again, so that a timing of this kernel is a timing
         // of the traversal and not of staging the scene for 256 rays; the result does not change
@@ -591,12 +434,10 @@ struct Env {
 
 } // namespace
 
-// Kernel variants (RSRT_KERNEL): 0 = lockstep megakernel (first kernel); 1, 2, 3 = stage-scheduled wave-pool kernel
-// with 192 / 160 / 128 path slots per wave in 256-thread workgroups, each with its own LDS copy of a small scene (160: four
-// workgroups per CU fit in LDS); 4 (default) = for a scene whose whole image fits LDS, ONE 1024-thread workgroup per CU — one
-// scene copy instead of four, which is what makes room for 192 slots per wave (-0.8 % on the BASELINE frame); anything else as 2.
-#define RT_N_VARIANTS 5
-static const uint32_t kVariantPool[RT_N_VARIANTS] = {0, 192, 160, 128, RT_BIG_POOL};
+// Render kernel forms.  For a scene whose whole image fits LDS the default form is ONE 1024-thread workgroup per CU — one scene copy
+// instead of four, which is what makes room for 192 slots per wave (-0.8 % on the BASELINE frame); the SMALL form, which pipelined
+// small jobs run (and RSRT_KERNEL=2 forces), has 160 slots per wave in 256-thread workgroups, each with its own LDS copy of the
+// scene (four workgroups per CU fit in LDS).  Other scene views have one form.
 template <int SV, uint32_t BLOCK, uint32_t POOL>
 static const void *pool_function(int trav)
 {
@@ -610,17 +451,14 @@ static const void *pool_function(int trav)
     }
 }
 // sv: 0 scene in global memory, 1 whole image in LDS, 2 hybrid (nodes + escape links in LDS, 1024-thread workgroups)
-static const void *variant_function(int kv, int sv, int trav)
+static const void *variant_function(bool small, int sv, int trav)
 {
-    if (kv == 0) return sv == 1 ? reinterpret_cast<const void *>(&rt_render_kernel<true>) : reinterpret_cast<const void *>(&rt_render_kernel<false>);
     if (trav == 6) // the cooperative walk: 128-slot pools; one 1024-thread workgroup per CU beside the staged node prefix, else 256-thread workgroups
         return sv == 2 ? reinterpret_cast<const void *>(&rt_render_pool_kernel<2, RT_COOP_BLOCK, RT_COOP_POOL, 6>)
                        : (sv == 1 ? reinterpret_cast<const void *>(&rt_render_pool_kernel<1, RT_BLOCK, RT_COOP_POOL, 6>) : reinterpret_cast<const void *>(&rt_render_pool_kernel<0, RT_BLOCK, RT_COOP_POOL, 6>));
     if (sv == 2) return pool_function<2, 1024, RT_WALK_POOL>(trav == 2 ? 1 : trav); // (the flat loop needs the whole image: never asked for here)
-    if (kv == 1) return sv == 1 ? pool_function<1, RT_BLOCK, 192>(trav) : pool_function<0, RT_BLOCK, 192>(trav);
-    if (kv == 3) return sv == 1 ? pool_function<1, RT_BLOCK, 128>(trav) : pool_function<0, RT_BLOCK, 128>(trav);
-    if (kv == 4 && sv == 1) return pool_function<1, 1024, RT_BIG_POOL>(trav);
-    return sv == 1 ? pool_function<1, RT_BLOCK, 160>(trav) : pool_function<0, RT_BLOCK, 160>(trav);
+    if (sv == 1) return small ? pool_function<1, RT_BLOCK, 160>(trav) : pool_function<1, 1024, RT_BIG_POOL>(trav);
+    return pool_function<0, RT_BLOCK, 160>(trav);
 }
 
 template <int SV>
@@ -640,6 +478,14 @@ static const void *probe_function(int sv, int trav)
 {
     return sv == 0 ? probe_function_sv<0>(trav) : (sv == 1 ? probe_function_sv<1>(trav) : probe_function_sv<2>(trav));
 }
+
+// Scheduling of the render passes (see rsrt_context::Lane)
+static constexpr uint32_t kLanes = 4;               // sets of work buffers, each with its own stream
+static constexpr uint64_t kSmallPaths = 4ull << 20; // a call of at most this many paths is a small job
+static constexpr int kPipeBlocks = 1;               // workgroups per CU of a pipelined small job (four such jobs fill a CU)
+static constexpr uint32_t kChunksPerWave = 32;      // work chunks a resident wave should get at least: sets samples per chunk, and sub-tiles for small jobs
+static constexpr uint32_t kDescendQuorum = 30;      // fixed-order / wide walk: a descending round ends once fewer than this percentage of its lanes are still descending
+static constexpr uint32_t kStopQuorum = 40;         // wide walk: a TRACE call ends (the unfinished rays park their stacks) once fewer than this percentage of its lanes are still walking
 
 struct rsrt_context {
     int device = 0;
@@ -664,11 +510,11 @@ struct rsrt_context {
     float4 *accum_owned = nullptr;
     uint32_t acc_w = 0, acc_h = 0;
     // work buffers
-    // Two sets of work buffers ("lanes"), used in turn by successive passes: a pass's path-tracing kernel runs on its lane's own
+    // kLanes sets of work buffers ("lanes"), used in turn by successive passes: a pass's path-tracing kernel runs on its lane's own
     // stream and touches nothing but its lane's buffers, so the kernel of call k + 1 fills the CUs that call k's tail is leaving
     // (a launch ends with ~0.5 ms of pipeline drain: at one sample per call — the reference's interactive mode, src/state.rs:
     // 760-833 — that was half the frame time).  Only the small resolve kernels, which add into the accumulator in sample
-    // order, stay chained on the caller's stream.  RSRT_OVERLAP=0: one lane, everything on the caller's stream (A/B).
+    // order, stay chained one behind the other (enqueue_pass).
     struct Lane {
         hipStream_t stream = nullptr;
         unsigned int *work_counter = nullptr;
@@ -682,17 +528,13 @@ struct rsrt_context {
         bool traced_valid = false;
         hipEvent_t caller_at = nullptr; // where the caller's stream stood when this lane's last pass was enqueued
     };
-    // Ordinary jobs use lane 0.  SMALL jobs (at most `small_paths` paths a call: the reference's one sample per
-    // frame) that arrive while an earlier kernel is still running are PIPELINED: they take turns over all four lanes and run the
-    // 256-thread form of the kernel with one workgroup per CU, so that up to four calls are resident side by side and one call's
+    // Ordinary jobs use lane 0.  SMALL jobs (at most kSmallPaths paths a call: the reference's one sample per
+    // frame) that arrive while an earlier kernel is still running are PIPELINED: they take turns over all kLanes lanes and run the
+    // small form of the kernel with kPipeBlocks workgroups per CU, so that up to four calls are resident side by side and one call's
     // ~0.5 ms of pipeline fill and drain is covered by its neighbours' steady state (a call alone on the GPU keeps the full grid:
     // its latency is what counts then).
-    Lane lanes[8];
-    uint32_t n_lanes = 4;   // lanes in use (RSRT_PIPE_LANES: 2 .. 8)
-    uint32_t pipe_div = 1;  // a pipelined small job's grid is a CU's worth of workgroups / pipe_div (RSRT_PIPE_DIV: with 8 lanes and 2, each of eight resident jobs has half as many waves that each run twice as long)
+    Lane lanes[kLanes];
     uint32_t next_small_lane = 1;
-    bool overlap = true;
-    uint64_t small_paths = 4ull << 20;
     unsigned long long *dev_stats = nullptr;
     // stats
     rsrt_stats stats{};
@@ -722,8 +564,8 @@ struct rsrt_context {
     // scratch for rsrt_resolve_mean_f16 / rsrt_display_srgb8 (grow-only; no per-frame hipMalloc)
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
-    int blocks_per_cu[21][RT_N_VARIANTS] = {}; // [scene view * 7 + traversal][kernel variant]
-    int kernel_variant = 4; // index into kVariantPool
+    int blocks_per_cu[21] = {}; // [scene view * 7 + traversal], of the form small_form selects (a pipelined job has kPipeBlocks)
+    bool small_form = false; // RSRT_KERNEL=2: every job runs the small form (tests reach it this way)
     int max_traversal = 6; // most specialised traversal to use where the scene allows it (rt_wavepool.h, TRAV)
     uint32_t coop_lds_cap = RT_COOP_NCAP, coop_lifo_at = RT_COOP_LIFO_AT, coop_narrow_at = RT_COOP_NARROW_AT; // RSRT_COOP_LDS_CAP / _LIFO_AT / _NARROW_AT (tests: force the node queue's spill / newest-first / one-item trips)
     uint32_t coop_gcap = RT_COOP_GCAP; // RSRT_COOP_GCAP (tests: a small arena block forces the overflow guard, rt_coop.h coop_overflow)
@@ -731,14 +573,9 @@ struct rsrt_context {
     bool flat_oriented = true; // RSRT_FLAT_ORIENTED=0: the flat loop orders each box's slab values itself instead of reading octant tables (A/B)
     bool allow_hybrid = true;
     uint32_t trace_budget = 0; // traversal steps per TRACE invocation before a ray is re-queued (0: 6 for the fixed-order walk, 12 for the tree walks)
-    uint32_t descend_quorum = 30; // fixed-order / wide walk: a descending round ends once fewer than this percentage of its lanes are still descending
-    uint32_t stop_quorum = 40; // wide walk: a TRACE call ends (the unfinished rays park their stacks) once fewer than this percentage of its lanes are still walking
-    uint32_t chunks_per_wave = 32; // work chunks a resident wave should get at least (RSRT_CHUNKS_PER_WAVE): sets samples per chunk, and sub-tiles for small jobs
     uint32_t flat_quorum = 20; // flat traversal: the triangle loop ends once fewer than this percentage of its lanes still hold triangles (0: never)
     // (every RSRT_* environment knob is read ONCE, in rsrt_context_create)
     size_t sample_buffer_budget = 16ull << 30; // RSRT_SAMPLE_BUFFER_MB: bytes of sample buffer per pass
-    int pipe_blocks = 1;     // RSRT_PIPE_BLOCKS: workgroups per CU of a pipelined small job (four such jobs fill a CU)
-    int max_blocks_per_cu = 0; // RSRT_BLOCKS_PER_CU: cap on the occupancy the runtime reports (0: none; experiment knob)
     uint32_t probe_repeat = 1; // RSRT_PROBE_REPEAT: rsrt_cast_rays runs every query this many times (tools/trace_rate.py)
     // Pipelined small jobs want four kernels of one context resident at a time, each from a stream of its own; the HIP runtime maps a
     // process's streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and streams that share one run one after the other —
@@ -1160,11 +997,11 @@ int select_traversal(const rsrt_context *ctx, const DevScene &sc, uint32_t max_b
 
 // One pass of rsrt_render: the path-tracing kernel over P.sample_count samples, then the ordered resolve.
 rsrt_status enqueue_pass(rsrt_context *ctx, RenderParams &P, const rsrt_context::PassEvents &pe, const void *kfn, uint32_t block, int bpc,
-                         size_t smem, size_t per_sample, uint32_t max_bounces, hipStream_t caller_stream, rsrt_context::Lane &lane, uint32_t grid_div = 1)
+                         size_t smem, size_t per_sample, uint32_t max_bounces, hipStream_t caller_stream, rsrt_context::Lane &lane)
 {
     const uint32_t tile_px = P.tile_w * P.tile_h;
     // the path-tracing kernel: on the lane's stream (behind the resolve that last read this lane's sample buffer: same stream)
-    const hipStream_t stream = ctx->overlap ? lane.stream : caller_stream;
+    const hipStream_t stream = lane.stream;
     HIP_TRY(ctx, hipEventRecord(pe.begin, stream));
     if (max_bounces > 0) {
         // chunk = one tile x samples_per_chunk samples.  Up to 8 samples per chunk (2048 paths: the
@@ -1172,8 +1009,8 @@ rsrt_status enqueue_pass(rsrt_context *ctx, RenderParams &P, const rsrt_context:
         // partitioned frame — so that every resident wave still gets >= ~32 chunks and the tail,
         // where waves run out of work at different times, stays a few percent.
         {
-            const uint64_t waves = (uint64_t)ctx->cus * bpc * (block / RT_WAVE) / grid_div;
-            const uint64_t want_chunks = (uint64_t)ctx->chunks_per_wave * waves;
+            const uint64_t waves = (uint64_t)ctx->cus * bpc * (block / RT_WAVE);
+            const uint64_t want_chunks = (uint64_t)kChunksPerWave * waves;
             const uint64_t total_tile_samples = (uint64_t)P.n_owned_tiles * P.sample_count;
             uint64_t spc = total_tile_samples / std::max<uint64_t>(want_chunks, 1);
             spc = std::min<uint64_t>(std::max<uint64_t>(spc, 1), std::max<uint32_t>(1u, 2048u / tile_px));
@@ -1193,7 +1030,7 @@ rsrt_status enqueue_pass(rsrt_context *ctx, RenderParams &P, const rsrt_context:
         HIP_TRY(ctx, hipMemsetAsync(lane.work_counter, 0, sizeof(unsigned int), stream));
         const uint32_t waves_wanted = (uint32_t)std::min<uint64_t>(n_chunks, 0x7fffffffull);
         const uint32_t wpb = block / RT_WAVE;
-        uint32_t grid = std::min<uint32_t>((waves_wanted + wpb - 1) / wpb, std::max<uint32_t>(1u, (uint32_t)(ctx->cus * bpc) / grid_div));
+        uint32_t grid = std::min<uint32_t>((waves_wanted + wpb - 1) / wpb, std::max<uint32_t>(1u, (uint32_t)(ctx->cus * bpc)));
         grid = std::max(grid, 1u);
         void *kargs[] = {&P};
         HIP_TRY(ctx, hipLaunchKernel(kfn, dim3(grid), dim3(block), kargs, smem, stream));
@@ -1202,32 +1039,24 @@ rsrt_status enqueue_pass(rsrt_context *ctx, RenderParams &P, const rsrt_context:
         HIP_TRY(ctx, hipMemsetAsync(lane.sample_buf, 0, per_sample * P.sample_count, stream));
     }
     HIP_TRY(ctx, hipEventRecord(pe.traced, stream));
-    if (ctx->overlap) {
-        HIP_TRY(ctx, hipEventRecord(lane.traced, stream));
-        lane.traced_valid = true;
-    }
+    HIP_TRY(ctx, hipEventRecord(lane.traced, stream));
+    lane.traced_valid = true;
     // The ordered resolve, behind the kernel on the lane's stream.  It adds into the accumulator, so it comes after (a) what the
     // caller's stream holds at this moment (a clear, a caller's own kernel on a bound accumulator) and (b) whatever the context
     // enqueued last on any stream — the previous pass's resolve above all: samples are added in increasing order.  Nothing is
     // put on the caller's stream that could wait there (several streams share a hardware queue: a wait parked in the caller's
     // queue holds up the lane that shares it — measured, 0.81 against 0.60 ms per single-sample call); the caller's stream is
     // ordered behind the resolve by rsrt_render once per call, if the caller named a stream of its own.
-    if (ctx->overlap) {
-        HIP_TRY(ctx, hipEventRecord(lane.caller_at, caller_stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(stream, lane.caller_at, 0));
-        if (ctx->last_valid && ctx->last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->last_event, 0));
-    }
+    HIP_TRY(ctx, hipEventRecord(lane.caller_at, caller_stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(stream, lane.caller_at, 0));
+    if (ctx->last_valid && ctx->last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->last_event, 0));
     hipLaunchKernelGGL(rt_resolve_kernel, dim3((P.n_slots + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, P, ctx->accum);
     HIP_TRY(ctx, hipGetLastError());
     ctx->cum_launches++;
     HIP_TRY(ctx, hipEventRecord(pe.end, stream));
-    if (ctx->overlap) {
-        HIP_TRY(ctx, hipEventRecord(lane.resolved, stream));
-        lane.resolved_valid = true;
-        rsrt_status st = end_work(ctx, stream); // the context's chain now ends on the lane's stream
-        if (st) return st;
-    }
-    return RSRT_OK;
+    HIP_TRY(ctx, hipEventRecord(lane.resolved, stream));
+    lane.resolved_valid = true;
+    return end_work(ctx, stream); // the context's chain now ends on the lane's stream
 }
 
 // the device-only packing of an uploaded environment (rt_alias_device.h, rt_env_pack_*): pmf copies in the texels' alpha and
@@ -1296,33 +1125,22 @@ rsrt_status rsrt_context_create(int device_index, rsrt_context **out)
                    }
                    return r; }()) != hipSuccess ||
         (e = hipMalloc(&ctx->dev_stats, RT_STATS_WORDS * sizeof(unsigned long long))) != hipSuccess ||
-        (e = hipMemset(ctx->dev_stats, 0, RT_STATS_WORDS * sizeof(unsigned long long))) != hipSuccess) {
+        (e = hipMemsetAsync(ctx->dev_stats, 0, RT_STATS_WORDS * sizeof(unsigned long long), ctx->stream)) != hipSuccess || // (not the null stream:
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {                                                             // see ensure_aov)
         fail(nullptr, RSRT_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
         delete ctx;
         return RSRT_ERR_HIP;
     }
-    for (int kv = 0; kv < RT_N_VARIANTS; kv++)
-        for (int m = 0; m < 21; m++) (void)hipFuncSetAttribute(variant_function(kv, m / 7, m % 7), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (const char *kv = getenv("RSRT_KERNEL")) { // see kVariantPool
-        int v = atoi(kv);
-        if (v >= 0 && v < RT_N_VARIANTS) ctx->kernel_variant = v;
-    }
-    if (const char *sp = getenv("RSRT_SMALL_PATHS")) { long long v = atoll(sp); if (v >= 0) ctx->small_paths = (uint64_t)v; } // 0: no pipelining of small jobs (A/B)
-    if (const char *pl = getenv("RSRT_PIPE_LANES")) { int v = atoi(pl); if (v >= 2 && v <= 8) ctx->n_lanes = (uint32_t)v; } // experiment knobs
-    if (const char *pd = getenv("RSRT_PIPE_DIV")) { int v = atoi(pd); if (v >= 1 && v <= 8) ctx->pipe_div = (uint32_t)v; }
-    if (const char *ov = getenv("RSRT_OVERLAP")) ctx->overlap = atoi(ov) != 0; // 0: one set of work buffers, every kernel on the caller's stream (A/B)
+    for (bool small : {false, true})
+        for (int m = 0; m < 21; m++) (void)hipFuncSetAttribute(variant_function(small, m / 7, m % 7), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (const char *kv = getenv("RSRT_KERNEL")) ctx->small_form = atoi(kv) == 2; // 2: the small form for every job; 4 (the default) or anything else: the product's choice
     if (const char *hy = getenv("RSRT_HYBRID")) ctx->allow_hybrid = atoi(hy) != 0; // 0: mid-size scenes read everything from global memory (A/B)
     if (const char *ty = getenv("RSRT_TRAVERSAL")) ctx->max_traversal = atoi(ty); // cap: 0 generic tree walk, 1 typed leaf loops, 2 + flat small-scene loop, 3 + fixed-order walk (A/B)
     if (const char *fl = getenv("RSRT_FLAT")) ctx->allow_flat = atoi(fl) != 0; // 0: small scenes take the walk a big scene would (A/B)
     if (const char *fo = getenv("RSRT_FLAT_ORIENTED")) ctx->flat_oriented = atoi(fo) != 0; // 0: no per-octant leaf tables (A/B)
     if (const char *tb = getenv("RSRT_TRACE_BUDGET")) { int v = atoi(tb); if (v > 0) ctx->trace_budget = (uint32_t)v; }
-    if (const char *dq = getenv("RSRT_DESCEND_QUORUM")) { int v = atoi(dq); if (v >= 0 && v <= 100) ctx->descend_quorum = (uint32_t)v; }
-    if (const char *sq = getenv("RSRT_STOP_QUORUM")) { int v = atoi(sq); if (v >= 0 && v <= 100) ctx->stop_quorum = (uint32_t)v; }
-    if (const char *cw = getenv("RSRT_CHUNKS_PER_WAVE")) { int v = atoi(cw); if (v >= 1 && v <= 4096) ctx->chunks_per_wave = (uint32_t)v; }
     if (const char *fq = getenv("RSRT_FLAT_QUORUM")) { int v = atoi(fq); if (v >= 0 && v <= 100) ctx->flat_quorum = (uint32_t)v; }
     if (const char *e2 = getenv("RSRT_SAMPLE_BUFFER_MB")) { long v = atol(e2); if (v > 0) ctx->sample_buffer_budget = (size_t)v << 20; }
-    if (const char *pb = getenv("RSRT_PIPE_BLOCKS")) { int v = atoi(pb); if (v >= 1 && v <= 4) ctx->pipe_blocks = v; } // experiment knob
-    if (const char *o = getenv("RSRT_BLOCKS_PER_CU")) { int v = atoi(o); if (v > 0) ctx->max_blocks_per_cu = v; } // experiment knob
     if (const char *pr = getenv("RSRT_PROBE_REPEAT")) { int v = atoi(pr); if (v > 1 && v <= 4096) ctx->probe_repeat = (uint32_t)v; }
     if (const char *cl = getenv("RSRT_COOP_LDS_CAP")) { int v = atoi(cl); if (v >= (int)RT_COOP_MIN_LDS_CAP && v <= (int)RT_COOP_NCAP) ctx->coop_lds_cap = (uint32_t)v; }
     if (const char *cf = getenv("RSRT_COOP_LIFO_AT")) { int v = atoi(cf); if (v >= 0 && v <= (int)RT_COOP_NARROW_AT) ctx->coop_lifo_at = (uint32_t)v; }
@@ -2184,9 +2002,9 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
     const uint32_t tile_px = P.tile_w * P.tile_h;
     if ((uint64_t)P.n_owned_tiles * tile_px > 0x7fffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "frame too large");
     P.n_slots = P.n_owned_tiles * tile_px;
-    P.descend_quorum = ctx->descend_quorum;
+    P.descend_quorum = kDescendQuorum;
     P.flat_quorum = ctx->flat_quorum;
-    P.stop_quorum = ctx->stop_quorum;
+    P.stop_quorum = kStopQuorum;
     P.stats = ctx->dev_stats;
     if (P.n_slots == 0) return RSRT_OK;
 
@@ -2197,10 +2015,9 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
     pass_samples = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(pass_samples, 0xffffffffull / P.n_slots)); // slot ids are 32-bit
     const size_t need = per_sample * pass_samples;
 
-    const int kv = ctx->kernel_variant;
     const int trav = select_traversal(ctx, P.scene, max_bounces, flags);
     int sv = P.scene.lds_float4s != 0 ? 1 : 0;
-    if (sv == 0 && kv != 0 && ctx->allow_hybrid) { // mid-size scene: what the chosen traversal's box steps touch, in LDS (the first kernel has no hybrid form)
+    if (sv == 0 && ctx->allow_hybrid) { // mid-size scene: what the chosen traversal's box steps touch, in LDS
         if (hybrid_stage(ctx, P.scene, trav, trav == 6 ? kCoopRoomF4 : kHybridRoomF4)) sv = 2;
     }
     // measured on suzanne and the 15 k-triangle grid (profiles/r02_bvh_knobs.txt): with the quorum vote a round is short, and
@@ -2210,48 +2027,44 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
     P.coop_lifo_at = ctx->coop_lifo_at;
     P.coop_narrow_at = ctx->coop_narrow_at;
     P.coop_gcap = ctx->coop_gcap;
-    // a small job behind a kernel that is still running: the 256-thread form, one workgroup per CU, on one of four lanes (see Lane)
+    // a small job behind a kernel that is still running: the small form, kPipeBlocks workgroups per CU, on one of the lanes (see Lane)
     bool pipelined = false;
-    if (ctx->overlap && kv == 4 && sv == 1 && trav != 6 && (uint64_t)P.n_slots * sample_count <= ctx->small_paths && sample_count <= pass_samples)
+    if (!ctx->small_form && sv == 1 && trav != 6 && (uint64_t)P.n_slots * sample_count <= kSmallPaths && sample_count <= pass_samples)
         for (auto &L : ctx->lanes) pipelined = pipelined || (L.traced_valid && hipEventQuery(L.traced) == hipErrorNotReady);
-    const int kv_eff = pipelined ? 2 : kv;
-    const bool big = kv_eff == 4 && sv == 1 && trav != 6; // one workgroup per CU shares the scene copy
-    const uint32_t pool = trav == 6 ? RT_COOP_POOL : (sv == 2 ? RT_WALK_POOL : ((kv_eff == 4 && !big) ? 160u : kVariantPool[kv_eff]));
+    const bool small = ctx->small_form || pipelined;
+    const bool big = !small && sv == 1 && trav != 6; // one workgroup per CU shares the scene copy
+    const uint32_t pool = trav == 6 ? RT_COOP_POOL : (sv == 2 ? RT_WALK_POOL : (big ? RT_BIG_POOL : 160u));
     const uint32_t block = (sv == 2 && trav == 6) ? (uint32_t)RT_COOP_BLOCK : ((sv == 2 || big) ? 1024u : (uint32_t)RT_BLOCK);
-    const size_t scene_bytes = (size_t)P.scene.lds_float4s * sizeof(float4);
-    const size_t smem = kv == 0 ? scene_bytes + (size_t)P.scene.stack_entries * RT_BLOCK * sizeof(uint32_t)
-                                : scene_bytes + (size_t)(block / RT_WAVE) * 4u * pool_wave_lds_dwords(trav, pool);
+    const size_t smem = (size_t)P.scene.lds_float4s * sizeof(float4) + (size_t)(block / RT_WAVE) * 4u * pool_wave_lds_dwords(trav, pool);
     if (smem > 160 * 1024) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "kernel needs %zu bytes of LDS (> 160 KiB): bvh too deep for this pool size", smem);
-    const void *kfn = variant_function(kv_eff, sv, trav);
-    int pipe_blocks = ctx->pipe_blocks; // workgroups per CU of a pipelined small job: four such jobs fill a CU
-    if (pipelined && !ctx->hw_queue_warned && ctx->hw_queues < (int)ctx->n_lanes + 1) { // (the lanes' streams and the caller's)
+    const void *kfn = variant_function(small, sv, trav);
+    if (pipelined && !ctx->hw_queue_warned && ctx->hw_queues < (int)kLanes + 1) { // (the lanes' streams and the caller's)
         ctx->hw_queue_warned = true;
         fprintf(stderr, "librsrt: pipelining single-sample calls over %u streams on %d hardware queues: set GPU_MAX_HW_QUEUES=8 before the first HIP call (INTEGRATION.md)\n",
-                ctx->n_lanes, ctx->hw_queues);
+                kLanes, ctx->hw_queues);
     }
-    int &bpc = pipelined ? pipe_blocks : ctx->blocks_per_cu[sv * 7 + trav][kv];
+    int pipe_blocks = kPipeBlocks;
+    int &bpc = pipelined ? pipe_blocks : ctx->blocks_per_cu[sv * 7 + trav];
     if (bpc == 0) {
         int nb = 0;
         hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kfn, (int)block, smem);
         if (e != hipSuccess || nb <= 0) nb = 1;
         bpc = std::min(nb, 8);
-        if (ctx->max_blocks_per_cu > 0) bpc = std::min(bpc, ctx->max_blocks_per_cu);
     }
 
-    const size_t need_cold = kv != 0 ? (size_t)ctx->cus * bpc * (block / RT_WAVE) * pool_wave_cold_dwords(trav, pool) * sizeof(uint32_t) : 0; // cold path-state arena: one block of columns per wave that can be resident
-    // the context's buffers are shared by every call: order this stream after whatever ran last (another stream's
-    // render, rsrt_accumulator_clear on the context's own stream, ...) — with lanes, enqueue_pass orders each resolve itself
-    if (!ctx->overlap && (st = begin_work(ctx, stream))) return st;
+    const size_t need_cold = (size_t)ctx->cus * bpc * (block / RT_WAVE) * pool_wave_cold_dwords(trav, pool) * sizeof(uint32_t); // cold path-state arena: one block of columns per wave that can be resident
+    // the context's buffers are shared by every call: enqueue_pass orders each resolve after whatever ran last (another stream's
+    // render, rsrt_accumulator_clear on the context's own stream, ...)
     rsrt_context::Lane *last_lane = nullptr;
     for (uint32_t done = 0; done < sample_count; done += pass_samples) {
         P.sample_begin = sample_begin + done;
         P.sample_count = std::min(pass_samples, sample_count - done);
         uint32_t li = 0; // ordinary jobs: lane 0, one after the other (a frame's kernel time is then its own, not its neighbour's too)
-        if (ctx->overlap && pipelined) { li = ctx->next_small_lane; ctx->next_small_lane = (li + 1u) % ctx->n_lanes; }
+        if (pipelined) { li = ctx->next_small_lane; ctx->next_small_lane = (li + 1u) % kLanes; }
         else ctx->next_small_lane = 1u;
         rsrt_context::Lane &lane = ctx->lanes[li];
         if (need > lane.sample_buf_bytes || need_cold > lane.cold_bytes) { // (grow-only; a reallocation waits for everything in flight)
-            if ((st = sync_all(ctx))) { if (!ctx->overlap) (void)end_work(ctx, stream); return st; }
+            if ((st = sync_all(ctx))) return st;
             if (need > lane.sample_buf_bytes) {
                 if (lane.sample_buf) { (void)hipFree(lane.sample_buf); lane.sample_buf = nullptr; lane.sample_buf_bytes = 0; }
                 HIP_TRY(ctx, hipMalloc(&lane.sample_buf, need));
@@ -2267,18 +2080,16 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
         P.cold_state = lane.cold_state;
         P.work_counter = lane.work_counter;
         rsrt_context::PassEvents pe = {get_event(ctx), get_event(ctx), get_event(ctx)};
-        const rsrt_status pst = enqueue_pass(ctx, P, pe, kfn, block, bpc, smem, per_sample, max_bounces, stream, lane, pipelined ? ctx->pipe_div : 1u);
+        const rsrt_status pst = enqueue_pass(ctx, P, pe, kfn, block, bpc, smem, per_sample, max_bounces, stream, lane);
         if (pst != RSRT_OK) { // nothing of this pass is pending: the three events go back to the pool
             ctx->event_pool.push_back(pe.begin); ctx->event_pool.push_back(pe.traced); ctx->event_pool.push_back(pe.end);
-            // earlier passes may be in flight.  With lanes the chain's end stays where the last successful pass recorded it (its lane's
-            // resolve): recording it on the caller's stream here would drop the dependency on those resolves
-            if (!ctx->overlap) (void)end_work(ctx, stream);
+            // earlier passes may be in flight: the chain's end stays where the last successful pass recorded it (its lane's
+            // resolve); recording it on the caller's stream here would drop the dependency on those resolves
             return pst;
         }
         ctx->pending_events.push_back(pe);
         last_lane = &lane;
     }
-    if (!ctx->overlap) return end_work(ctx, stream);
     // a caller that named a stream of its own gets that stream's semantics: what it enqueues there next comes after this render
     if (hip_stream && last_lane) HIP_TRY(ctx, hipStreamWaitEvent(stream, last_lane->resolved, 0));
     return RSRT_OK;

@@ -146,7 +146,10 @@ rsrt_status ensure_aov(rsrt_context *ctx)
     if (ctx->aov_owned) { (void)hipFree(ctx->aov_owned); ctx->aov_owned = nullptr; ctx->aov = nullptr; ctx->aov_w = ctx->aov_h = 0; }
     const size_t bytes = (size_t)ctx->acc_w * ctx->acc_h * 2u * sizeof(float4);
     HIP_TRY(ctx, hipMalloc(&ctx->aov_owned, bytes));
-    HIP_TRY(ctx, hipMemset(ctx->aov_owned, 0, bytes));
+    // (on the context's stream, and finished before any pass can write the buffer: a plain hipMemset goes to the null stream, which the
+    // context's non-blocking streams are not ordered against, and could land on top of the first AOV pass)
+    HIP_TRY(ctx, hipMemsetAsync(ctx->aov_owned, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->aov = ctx->aov_owned;
     ctx->aov_w = ctx->acc_w;
     ctx->aov_h = ctx->acc_h;

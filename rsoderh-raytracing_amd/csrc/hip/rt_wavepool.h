@@ -1,6 +1,6 @@
 // rt_wavepool.h — the stage-scheduled path-tracing kernel (rt_render_pool_kernel).
 //
-// Why: the first kernel (one lane = one path, all stages in lockstep; rt_render_kernel) keeps only
+// Why: a lockstep kernel (one lane = one path, all stages in lockstep: the project's first kernel) keeps only
 // ~13 of 64 lanes active per VALU instruction (profiles/r01_v1_*): lanes wait for each other across
 // stages of very different length.  Here a WAVE owns a pool of POOL path slots, every slot carries a
 // stage tag, and the wave repeatedly

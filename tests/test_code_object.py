@@ -39,3 +39,16 @@ def test_pool_kernels_keep_four_waves_per_simd_without_scratch():
         m = md[names[0]]
         assert m["vgpr_count"] <= 128, (names[0], m)
         assert m["private_segment_fixed_size"] == 0 and m["vgpr_spill_count"] == 0, (names[0], m)
+
+
+@pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-readelf")), reason="no llvm-readelf")
+def test_code_object_holds_exactly_the_render_kernel_forms():
+    """rsrt_api.hip variant_function: <SV, BLOCK, POOL> for traversals 0-5 — whole image in LDS in the default and the small form, scene
+    in global memory, hybrid — and the cooperative walk (TRAV 6) in each scene view; nothing else is compiled."""
+    forms = [(1, 1024, 192), (1, 256, 160), (0, 256, 160), (2, 1024, 192)]
+    wanted = {"ILi%dELj%dELj%dELi%dEE" % (sv, block, pool, trav) for sv, block, pool in forms for trav in range(6)}
+    wanted |= {"ILi0ELj256ELj128ELi6EE", "ILi1ELj256ELj128ELi6EE", "ILi2ELj1024ELj128ELi6EE"}
+    names = kernel_metadata()
+    got = {re.match(r"_Z21rt_render_pool_kernel(I.*?EE)", n).group(1) for n in names if n.startswith("_Z21rt_render_pool_kernel")}
+    assert got == wanted, (sorted(got - wanted), sorted(wanted - got))
+    assert not [n for n in names if "rt_render_kernel" in n]

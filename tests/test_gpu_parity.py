@@ -129,10 +129,10 @@ def test_matches_oracle_live(name, w, h, spp, mb, big_env):
     assert (st["paths"], st["ext_rays"], st["shadow_rays"]) == (ost["paths"], ost["ext_rays"], ost["shadow_rays"])
 
 
-@pytest.mark.parametrize("variant,traversal", [("4", "6"), ("2", "6"), ("4", "6-noflat"), ("1", "6-noflat"), ("0", "4"), ("1", "4"), ("2", "4"), ("3", "4"), ("4", "4"), ("2", "4-noflat"), ("4", "4-noflat"), ("2", "3"), ("4", "3"), ("2", "3-noflat"), ("4", "3-noflat"), ("2", "1"), ("4", "1"), ("2", "0")])
+@pytest.mark.parametrize("variant,traversal", [("4", "6"), ("2", "6"), ("4", "6-noflat"), ("2", "4"), ("4", "4"), ("2", "4-noflat"), ("4", "4-noflat"), ("2", "3"), ("4", "3"), ("2", "3-noflat"), ("4", "3-noflat"), ("2", "1"), ("4", "1"), ("2", "0")])
 def test_every_kernel_variant_is_bit_exact(variant, traversal, big_env, monkeypatch):
-    """RSRT_KERNEL: 0 = lockstep megakernel, 1/2/3 = stage-scheduled wave-pool kernel (192/160/128 slots per wave), 4 (the
-    default) = one 1024-thread workgroup and one scene copy per CU for scenes that fit LDS, 192 slots per wave;
+    """RSRT_KERNEL: 2 = the small form (256-thread workgroups, 160 slots per wave), 4 (the default) = one 1024-thread
+    workgroup and one scene copy per CU for scenes that fit LDS, 192 slots per wave;
     RSRT_TRAVERSAL caps the traversal: 6 = product (flat loop for small scenes, cooperative wide walk otherwise; with RSRT_FLAT=0 that
     walk for small scenes too), 4 = the one-ray-a-lane wide walk instead, 3 = the fixed-order walk instead of the wide one, 1 tree walk with per-type leaf loops, 0 generic tree walk.
     Scheduling differs, the per-path arithmetic does not: all must give the oracle's bits."""
@@ -714,14 +714,14 @@ def test_big_scene_all_global_is_bit_exact(big_env, tmp_path):
     s2.close()
 
 
-@pytest.mark.parametrize("levels,budget,hybrid,kernel", [(42, "", "1", "4"), (60, "", "1", "4"), (60, "1", "1", "4"), (60, "1", "0", "4"), (60, "1", "0", "1"), (60, "", "0", "3"),
+@pytest.mark.parametrize("levels,budget,hybrid,kernel", [(42, "", "1", "4"), (60, "", "1", "4"), (60, "1", "1", "4"), (60, "1", "0", "4"), (60, "", "0", "4"),
                                                          (42, "coop", "1", "4"), (60, "coop", "1", "4"), (60, "coop", "0", "4")])
 def test_wide_walk_stack_overflow_on_a_chain_tree(levels, budget, hybrid, kernel, big_env, monkeypatch):
     """tests/util.py deck_scene: a hand-built chain tree whose wide form has levels / 3 levels, on which a ray along the deck holds up to
     13 (42 levels) or 19 (60) stack words — more than the walk has registers (test_wide_tree.py shows that on the CPU).  The image, seen
     along the deck, and a batch of probe rays must be the oracle's bit for bit: with the default budget, and with one round per TRACE
     call, so that rays are parked and resumed while words sit in the overflow area.  42 levels: the scene's whole image fits LDS (scene
-    view 1); 60: nodes staged in LDS (view 2) or everything in global memory (RSRT_HYBRID=0, view 0) with 160 / 192 / 128-slot pools."""
+    view 1); 60: nodes staged in LDS (view 2) or everything in global memory (RSRT_HYBRID=0, view 0) with 192 / 160-slot pools."""
     if budget == "coop":  # the same trees through the cooperative walk, which has no per-ray stack to overflow (its work stacks are the wave's)
         monkeypatch.setenv("RSRT_TRAVERSAL", "6")
     else:

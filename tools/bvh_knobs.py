@@ -1,5 +1,5 @@
 """Scratch: run-time knob matrix on the general-BVH scenes (suzanne, suzanne grid) for the library named by RSRT_LIB
-(or the product).  python tools/bvh_knobs.py "RSRT_TRACE_BUDGET=6;RSRT_TRACE_BUDGET=12;RSRT_KERNEL=1,RSRT_TRACE_BUDGET=24" """
+(or the product).  python tools/bvh_knobs.py "RSRT_TRACE_BUDGET=6;RSRT_TRACE_BUDGET=12;RSRT_KERNEL=2,RSRT_TRACE_BUDGET=24" """
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests')); sys.path.insert(0, os.path.join(ROOT, 'tools'))

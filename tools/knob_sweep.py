@@ -1,5 +1,5 @@
 """Scratch: time the house 1080p frame for values of one environment knob.
-python tools/knob_sweep.py RSRT_TRACE_BUDGET 8,12,16,1000 [kernel variant] [spp]"""
+python tools/knob_sweep.py RSRT_TRACE_BUDGET 8,12,16,1000 [kernel variant: 2 or 4] [spp]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))

@@ -15,14 +15,10 @@ ROWS = [  # label, compile-time flags, run-time environment
     ("12 columns, one nt 12-byte store (product)", "", {}),
     ("12 columns, one sc1 12-byte store", "-DRT_SAMPLE_STORE=3", {}),
     ("product + nt environment gathers", "-DRT_ENV_NT=1", {}),
-    ("product, 3 workgroups per CU", "", {"RSRT_BLOCKS_PER_CU": "3"}),
-    ("product, 128 slots per wave", "", {"RSRT_KERNEL": "3"}),
-    ("product, 128 slots, 3 workgroups per CU", "", {"RSRT_KERNEL": "3", "RSRT_BLOCKS_PER_CU": "3"}),
-    ("sc1 store + nt env, 3 workgroups per CU", "-DRT_SAMPLE_STORE=3 -DRT_ENV_NT=1", {"RSRT_BLOCKS_PER_CU": "3"}),
     ("product + nt on the alias-slot gather only", "-DRT_ENV_NT=2", {}),
     ("sc1 store + nt on the alias-slot gather only", "-DRT_SAMPLE_STORE=3 -DRT_ENV_NT=2", {}),
 ]
-if "--only" in sys.argv:  # e.g. --only 3,10,11
+if "--only" in sys.argv:  # e.g. --only 3,6,7
     keep = [int(k) for k in sys.argv[sys.argv.index("--only") + 1].split(",")]
     ROWS = [ROWS[k] for k in keep]
 

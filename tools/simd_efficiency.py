@@ -1,5 +1,5 @@
 """Diagnostic: SIMD efficiency per code region of the wave-pool kernel, from the loop-trip counters of
-the instrumented build (RSRT_INSTRUMENT=1).  python tools/simd_efficiency.py [kernel_variant] [spp] [scene name | path.toml] [w] [h] [bounces]"""
+the instrumented build (RSRT_INSTRUMENT=1).  python tools/simd_efficiency.py [kernel variant: 2 or 4] [spp] [scene name | path.toml] [w] [h] [bounces]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, 'tests'))
