@@ -11,7 +11,9 @@
  *   c_p   = sum_p / S                                      the noisy mean (rsrt_display_srgb8's input)
  *   a_p   = (albedo_sum_p + (T - hits_p)) / T              mean first-hit albedo; a sample that hit nothing counts as 1
  *   n_p   = normal_sum_p / T,  z_p = distance_sum_p / T    mean first-hit normal and distance (a miss counts as 0),
- *                                                          both stored as binary16 (the packed features one tap reads)
+ *                                                          both stored as binary16 (the packed features one tap reads);
+ *                                                          z_p saturates at RSRT_DN_DEPTH_MAX first, so that a far pixel
+ *                                                          packs to a finite depth instead of inf (inf - inf = NaN in dz)
  *   r_p   = c_p / max(a_p, RSRT_DN_ALBEDO_EPS)             demodulated (RSRT_DENOISE_DEMODULATE; otherwise r_p = c_p)
  * Level i = 0 .. L-1, step 2^i, taps q = p + 2^i (dx, dy), dx, dy in -2..2, dy outer, dx inner; taps outside the image
  * are skipped:
@@ -29,6 +31,7 @@
 
 #define RSRT_DN_ALBEDO_EPS 1.0e-3f /* demodulation divides by max(albedo, this) */
 #define RSRT_DN_DEPTH_EPS 1.0e-4f  /* keeps the relative-depth scale finite where nothing was hit (z = 0) */
+#define RSRT_DN_DEPTH_MAX 65504.0f /* the largest finite binary16: the packed mean distance saturates here */
 
 /* taps of the B3 spline: [1, 4, 6, 4, 1] / 16, exact in f32 */
 RSRT_HD float rsrt_dn_b3(int k) { return k == 0 ? 0.375f : ((k == 1 || k == -1) ? 0.25f : 0.0625f); }
@@ -40,10 +43,11 @@ RSRT_HD void rsrt_dn_albedo(const float aov[8], float aov_total, float a[3])
     for (int i = 0; i < 3; i++) a[i] = (aov[i] + miss) / aov_total;
 }
 
-/* the guide features before their binary16 packing: mean normal xyz, mean distance */
+/* the guide features before their binary16 packing: mean normal xyz, mean distance (saturated at RSRT_DN_DEPTH_MAX) */
 RSRT_HD void rsrt_dn_features(const float aov[8], float aov_total, float f[4])
 {
     for (int i = 0; i < 4; i++) f[i] = aov[4 + i] / aov_total;
+    f[3] = f[3] > RSRT_DN_DEPTH_MAX ? RSRT_DN_DEPTH_MAX : f[3];
 }
 
 /* the filtered quantity of one pixel */

@@ -9,6 +9,7 @@ F = np.float32
 B3 = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625], np.float32)
 ALBEDO_EPS = F(1.0e-3)
 DEPTH_EPS = F(1.0e-4)
+DEPTH_MAX = F(65504.0)  # the largest finite binary16: the packed mean distance saturates here
 
 
 def fma32(a, b, c):
@@ -25,6 +26,13 @@ def fma32(a, b, c):
 
 
 # -------------------------------------------------------------------------------------------------- filter
+def features(aov, aov_total):
+    """rsrt_dn_features and their binary16 packing: mean normal xyz, mean distance saturated at DEPTH_MAX -> [H, W, 4] f32."""
+    f = np.asarray(aov, np.float32)[..., 4:8] / F(aov_total)
+    f[..., 3] = np.where(f[..., 3] > DEPTH_MAX, DEPTH_MAX, f[..., 3])
+    return f.astype(np.float16).astype(np.float32)
+
+
 def denoise(sums, aov, sample_total, aov_total, iterations=5, sigma_color=2.0, sigma_normal=0.5, sigma_depth=0.3, demodulate=True):
     """rsrt_denoise: sums [H, W, 4] (the accumulator), aov [H, W, 8] -> [H, W, 3] f32."""
     S, T = F(sample_total), F(aov_total)
@@ -35,7 +43,7 @@ def denoise(sums, aov, sample_total, aov_total, iterations=5, sigma_color=2.0, s
     aov = np.asarray(aov, np.float32)
     miss = T - aov[..., 3]
     a = (aov[..., :3] + miss[..., None]) / T
-    f = (aov[..., 4:8] / T).astype(np.float16).astype(np.float32)  # the packed binary16 features
+    f = features(aov, T)  # the packed binary16 features
     r = c / np.where(a < ALBEDO_EPS, ALBEDO_EPS, a) if demodulate else c
     sc, sn, sz = F(sigma_color), F(sigma_normal), F(sigma_depth)
     kn = F(1.0) / (sn * sn)

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import denoise_ref
 import temporal_ref as T
 import test_denoise
 import test_temporal
@@ -174,7 +175,7 @@ def test_filter_branches_occur(host):
     border[[0, -1], :] = border[:, [0, -1]] = True
     assert hit.any() and (~hit).any() and (hit & border).any() and (~hit & border).any()
     assert np.array_equal(util.bits(clamped[~hit]), util.bits(r[~hit]))
-    f = (aov[..., 4:8] / np.float32(3)).astype(np.float16).astype(np.float32)
+    f = denoise_ref.features(aov, 3)
     m = synthetic_moments(h, w, 9)
     v, temporal = V.variance(m, f, 0.3, 0.2)
     assert temporal.any() and (~temporal).any() and (v == 0).any() and (v > 0).any()

@@ -238,7 +238,7 @@ def denoise(sums, aov, sample_total, aov_total, iterations=5, sigma_color=None, 
         return c
     assert demodulate or not variance_guided
     r = prepare(sums, aov, sample_total, aov_total, demodulate)
-    f = (np.asarray(aov, np.float32)[..., 4:8] / F(aov_total)).astype(np.float16).astype(np.float32)
+    f = denoise_ref.features(aov, aov_total)
     l = lum(r)
     if clamp_input:
         r, _ = clamp(r)
