@@ -68,14 +68,7 @@ def test_matches_golden_images_bit_exact(name):
             assert [st["paths"], st["ext_rays"], st["shadow_rays"]] == list(g["rays_%dspp_%db" % (spp, mb)])
 
 
-def probe_modes(name):
-    """Every way rsrt_cast_rays can run a query (include/rsrt.h): traversal 0 threaded / 1 stack / 2 typed leaf loops /
-    3 flat (what house, default and cube run in production; suzanne's 968 triangles do not qualify) / 4 fixed-order walk
-    / 5 wide walk (4-wide nodes, one ray a lane) / 6 cooperative wide walk (the same nodes, a wave's rays as work items on two LDS stacks: what
-    suzanne and anything bigger run), x scene read from global memory or from LDS as the production kernel stages
-    it for that traversal (bit 4), x cast_ray / cast_ray_bvh (bit 0)."""
-    sels = [0, 1, 2, 4, 5, 6] + ([3] if name != "suzanne" else [])  # (5, 6: the wide walks — every builder-made tree qualifies)
-    return [(sel << 1) | lds | bvh_only for sel in sels for lds in (0, 16) for bvh_only in (0, 1)]
+probe_modes = util.probe_modes  # (shared with test_scene_edges_gpu.py)
 
 
 @pytest.mark.parametrize("name", SCENES)

@@ -43,6 +43,27 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def same_bits_or_nan(a, b):
+    """Bit for bit where a NaN's payload is left out (x86 and gfx950 make different default NaNs): the same elements are NaN, every
+    other element has the same bits.  For tests/test_scene_edges*.py only; elsewhere results are finite and compared with bits()."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    if a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    return bool(np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb]))
+
+
+def probe_modes(name, flat=None):
+    """Every way rsrt_cast_rays can run a query (include/rsrt.h): traversal 0 threaded / 1 stack / 2 typed leaf loops /
+    3 flat (what house, default and cube run in production; suzanne's 968 triangles do not qualify) / 4 fixed-order walk
+    / 5 wide walk (4-wide nodes, one ray a lane) / 6 cooperative wide walk (the same nodes, a wave's rays as work items on two LDS stacks: what
+    suzanne and anything bigger run), x scene read from global memory or from LDS as the production kernel stages
+    it for that traversal (bit 4), x cast_ray / cast_ray_bvh (bit 0).  flat: whether the scene qualifies for traversal 3 (default: by name)."""
+    flat = (name != "suzanne") if flat is None else flat
+    sels = [0, 1, 2, 4, 5, 6] + ([3] if flat else [])  # (5, 6: the wide walks — every builder-made tree qualifies)
+    return [(sel << 1) | lds | bvh_only for sel in sels for lds in (0, 16) for bvh_only in (0, 1)]
+
+
 def rmse_per_channel(a, b, spp):
     d = (a[..., :3].astype(np.float64) - b[..., :3].astype(np.float64)) / spp
     return np.sqrt((d * d).mean(axis=(0, 1)))
