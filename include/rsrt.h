@@ -96,7 +96,15 @@ const char *rsrt_last_error(const rsrt_context *ctx);
 /* -- scene: bind group 2, the eight storage buffers (state.rs:394-458) -----------------------
  * Arrays are in the layouts of rsrt_types.h; the library copies and re-lays them out for the
  * device, the caller keeps ownership.  Any array may be empty (pointer ignored when count 0)
- * except bvh_nodes.  Indices are validated; an out-of-range index is RSRT_ERR_INVALID_ARGUMENT. */
+ * except bvh_nodes.  Indices are validated; an out-of-range index is RSRT_ERR_INVALID_ARGUMENT.
+ * A context may be given a new scene at any time: the next render, probe or AOV pass uses it.  Every call, a refused one
+ * included, drops the temporal history first thing (rsrt_temporal_download is RSRT_ERR_NOT_READY until the next temporal frame).
+ * A REFUSED call: every array, every index and the tree's shape are checked before the scene is touched, so a call refused for
+ * any of them leaves the previous scene in place (it still renders, the same image and ray counts) and the accumulator as it was.
+ * One refusal comes later: a valid tree deeper than the traversal stack holds (more than 128 levels: "bvh depth ... exceeds the
+ * supported traversal stack", RSRT_ERR_INVALID_ARGUMENT) is found after the previous scene has been freed.  The context then has
+ * NO scene: rsrt_render, rsrt_cast_rays and rsrt_aov_render return RSRT_ERR_NOT_READY until the next successful upload; the
+ * accumulator is untouched. */
 rsrt_status rsrt_upload_scene(rsrt_context *ctx,
                               const rsrt_material *materials, uint32_t n_materials,
                               const rsrt_sphere *spheres, uint32_t n_spheres,
@@ -111,7 +119,12 @@ rsrt_status rsrt_upload_scene(rsrt_context *ctx,
  * slot = index into the reference's binding_array / `environments` array.  rgba: width*height*4
  * f32, rows top to bottom, alpha ignored (texture.rs:112-115 writes 0).  alias: width*height
  * entries as AliasTable::build_by_luminance produces (rsrt_host.h has that builder), or NULL to have the
- * library build the table on the device (rsrt_environment_build_alias below). */
+ * library build the table on the device (rsrt_environment_build_alias below).
+ * Slots are 0 .. 63 and need not be filled in order: a slot below the highest one may stay empty, and rendering with an empty slot
+ * is RSRT_ERR_NOT_READY (nothing is launched, the accumulator is not touched).  Uploading to a filled slot replaces it, whatever
+ * the two sizes.  Every call, a refused one included, drops the temporal history first thing.  A REFUSED call (NULL data, a zero
+ * size, slot > 63, an alias_index out of range: all RSRT_ERR_INVALID_ARGUMENT) leaves every slot, the one it named included, as it
+ * was: what rendered before renders the same afterwards. */
 rsrt_status rsrt_upload_environment(rsrt_context *ctx, uint32_t slot, uint32_t width, uint32_t height,
                                     const float *rgba, const rsrt_alias_entry *alias);
 /* AliasTable::build_by_luminance (src/environments.rs:96-187) ON THE DEVICE, for the texels already uploaded in `slot`
@@ -139,7 +152,10 @@ rsrt_status rsrt_build_bvh_device(rsrt_context *ctx, const rsrt_sphere *spheres,
  * rank — interleaved in x, each tile row shifted by `skew` (the smallest odd number >= 3 coprime to world_size: 3 for 2, 4, 8
  * GPUs) against the row above, so that a rank's tiles form a lattice whatever the frame width (t % world_size would give every
  * rank fixed column stripes whenever the tiles per row are a multiple of world_size) — and leaves every other pixel of the
- * accumulator untouched.  Default: rank 0 of 1 (whole frame). */
+ * accumulator untouched.  Default: rank 0 of 1 (whole frame).  A tile is any tile_w x tile_h whose pixel count is a multiple of 64
+ * and at most 4096 (64 x 1, 1 x 64 and 128 x 32 included); it may be larger than the frame.  The partition holds from the next
+ * render on, whatever the size.  A REFUSED call (rank >= world_size, an empty tile, a pixel count that is no multiple of 64 or is
+ * above 4096: RSRT_ERR_INVALID_ARGUMENT) leaves the previous partition in force. */
 rsrt_status rsrt_set_partition(rsrt_context *ctx, uint32_t rank, uint32_t world_size, uint32_t tile_w, uint32_t tile_h);
 
 /* Pure host arithmetic of that partition (no GPU needed): the rank that renders pixel (x, y) (UINT32_MAX for bad

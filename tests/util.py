@@ -78,6 +78,33 @@ def small_env(w=64, h=32):
     return _env_cache[(w, h)]
 
 
+def long_leaf_scene():
+    """A foreign BVH over scene `default`: a root and two leaves of ~11 primitives each — more than the 8 the per-type leaf masks and
+    the wide nodes hold, so neither the typed leaf loops nor the wide walks take it."""
+    base = R.Scene.load_toml(scene_path("default"))
+    nodes, prims = base.bvh_nodes, base.primitives
+    leaves = [n for n in nodes if n["primitives_len"] > 0]
+    leaves.sort(key=lambda n: int(n["primitives_or_second_child_index"]))
+    half = len(prims) // 2
+    cut = min((int(n["primitives_or_second_child_index"]) for n in leaves), key=lambda i: abs(i - half))
+    assert 8 < cut < len(prims) - 8
+
+    def union(sel):
+        return (np.min([n["bounds_min"] for n in sel], axis=0), np.max([n["bounds_max"] for n in sel], axis=0))
+
+    new = np.zeros(3, nodes.dtype)
+    new[0]["bounds_min"], new[0]["bounds_max"] = union(leaves)
+    new[0]["primitives_or_second_child_index"], new[0]["primitives_len"], new[0]["split_axis"] = 2, 0, 0
+    a = [n for n in leaves if int(n["primitives_or_second_child_index"]) < cut]
+    b = [n for n in leaves if int(n["primitives_or_second_child_index"]) >= cut]
+    new[1]["bounds_min"], new[1]["bounds_max"] = union(a)
+    new[1]["primitives_or_second_child_index"], new[1]["primitives_len"] = 0, cut
+    new[2]["bounds_min"], new[2]["bounds_max"] = union(b)
+    new[2]["primitives_or_second_child_index"], new[2]["primitives_len"] = cut, len(prims) - cut
+    return R.Scene(base.materials, base.spheres, base.plane_descs, base.vertices, base.normals, base.triangles, base.camera_desc,
+                   planes=base.planes, primitives=prims, bvh_nodes=new, bvh_depth=2)
+
+
 def deck_scene(levels=14):
     """A hand-built scene whose WIDE tree is deeper than the wide walk's eight stack registers, with few nodes: `levels` pairs of
     triangles stacked along z (a deck of cards, seen edge-on by the camera), and a binary BVH that is one long chain — node N_k has
