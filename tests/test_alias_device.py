@@ -39,7 +39,8 @@ def test_a_tree_reduction_is_not_the_reference_sum():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("w,h,kind", [(8, 4, "sun"), (64, 32, "sun"), (2048, 1024, "sun"), (100, 37, "sun"), (256, 128, "flat"), (300, 200, "noise"), (64, 1, "flat"), (1, 1, "sun"), (128, 64, "wild"), (96, 48, "zero"), (512, 256, "spike"), (64, 64, "equal")])
+@pytest.mark.parametrize("w,h,kind", [(8, 4, "sun"), (64, 32, "sun"), (2048, 1024, "sun"), (100, 37, "sun"), (256, 128, "flat"), (300, 200, "noise"), (64, 1, "flat"), (1, 1, "sun"), (128, 64, "wild"), (96, 48, "zero"), (512, 256, "spike"), (64, 64, "equal"),
+                                      (2, 1, "noise"), (1, 2, "noise"), (2, 2, "noise"), (3, 2, "noise"), (1, 37, "noise"), (5, 3, "noise"), (5, 3, "zero"), (5, 3, "spike")])
 def test_device_alias_table_is_the_host_table_bit_for_bit(w, h, kind):
     """kind: "sun" = the synthetic HDRI (a few hundred very large entries each pair with thousands of small ones: long runs of one
     large), "flat" = every texel within a few per cent of the mean (half the entries are larges that take one small or two and are
