@@ -376,6 +376,51 @@ rsrt_status rsrt_temporal_moments_download(rsrt_context *ctx, float *host_f32x4,
  *                          history it is estimated over a 7x7 window.  Requires RSRT_DENOISE_DEMODULATE (RSRT_ERR_INVALID_ARGUMENT). */
 enum { RSRT_DENOISE_VARIANCE = 4u, RSRT_DENOISE_CLAMP = 8u };
 
+/* -- guided upsampling: trace at a low size, rebuild the detail from first-hit records of the output size (no reference counterpart) --
+ * A path sample costs several times what a first hit costs, and the demodulated colour (colour / first-hit albedo) is smooth: the
+ * edges and the albedo's detail live in the first-hit records.  So an interactive caller renders the accumulator and its AOV buffer
+ * at a LOW size w x h (of the output's aspect: ceil(W / 2) x ceil(H / 2) for half size), the first hits alone at the output size
+ * W x H (the guide), and rsrt_upsample rebuilds the W x H picture: a joint-bilateral upsample of the low frame's demodulated colour,
+ * nine taps weighted by a tent and by the denoiser's normal and relative-depth terms against the guide, multiplied by the guide's
+ * albedo.  The arithmetic is published in include/rsrt_upsample.h.  Whole frame only, like the denoiser.
+ *
+ * The guide: width*height*8 f32 records exactly like the AOV buffer's, of a size of its own, W >= w, H >= h, both at most 16384.
+ * Library-owned (allocated and zeroed by rsrt_guide_render on first use or when the size it is given changes; freed on destroy) or
+ * caller-owned through rsrt_guide_bind (16-byte aligned; NULL goes back to the library's).  rsrt_guide_render adds the first hits of
+ * samples [sample_begin, sample_begin + sample_count) as rsrt_aov_render does, for a frame of width x height; it needs no accumulator
+ * and touches neither the accumulator nor the AOV buffer.  flags must be 0.  Give the guide as many samples as the low frame: its
+ * edges then alias as the render's own pixel filter does (a 1-sample guide under a 4-sample frame measured worse than bilinear on
+ * suzanne). */
+rsrt_status rsrt_guide_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin,
+                              uint32_t sample_count, uint32_t flags, void *hip_stream);
+rsrt_status rsrt_guide_bind(rsrt_context *ctx, void *device_f32x8, uint32_t width, uint32_t height);
+rsrt_status rsrt_guide_clear(rsrt_context *ctx);
+rsrt_status rsrt_guide_download(rsrt_context *ctx, float *host_f32x8, size_t n_floats);
+
+/* rsrt_upsample_params.flags: DEMODULATE as the denoiser's; the low colour is the accumulator's sum / sample_total (default), the last
+ * rsrt_denoise output (DENOISED) or the last temporal frame's colour (TEMPORAL); under either, sample_total is ignored.
+ * Defaults: flags RSRT_UPSAMPLE_DEMODULATE, sigma_normal 0.5, sigma_depth 0.3 (each in [1e-6, 1e6]). */
+enum { RSRT_UPSAMPLE_DEMODULATE = 1u, RSRT_UPSAMPLE_DENOISED = 2u, RSRT_UPSAMPLE_TEMPORAL = 4u };
+typedef struct rsrt_upsample_params {
+    uint32_t flags;
+    float sigma_normal; /* of the mean normal, low tap against guide */
+    float sigma_depth;  /* of the mean distance, relative to the guide pixel's */
+} rsrt_upsample_params;
+/* Writes W*H RGBA32F (alpha 1), W x H the guide's size, to device_out_rgba32f (16-byte aligned) or, when it is NULL, to a
+ * library-owned buffer.  The AOV records hold aov_sample_total samples, the guide's guide_sample_total.  Writes nothing but its own
+ * scratch (24 B a low pixel) and the output: the accumulator, the AOV buffer, the guide, the denoised image and the temporal history
+ * keep their bits.  RSRT_ERR_NOT_READY: no accumulator, AOV buffer or guide, no denoised image under DENOISED, no temporal frame since
+ * the last reset under TEMPORAL.  RSRT_ERR_INVALID_ARGUMENT: NULL params, unknown flags, DENOISED and TEMPORAL together, a sigma out
+ * of range, a total of 0, an AOV buffer of another size than the accumulator, a guide smaller than the accumulator in either
+ * dimension or above 16384, world_size > 1, a misaligned output pointer.  Nothing is launched on a refused call.  Asynchronous on
+ * hip_stream (NULL = the context's stream). */
+rsrt_status rsrt_upsample(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_sample_total, uint32_t guide_sample_total,
+                          const rsrt_upsample_params *params, void *device_out_rgba32f, void *hip_stream);
+/* the last rsrt_upsample output (wherever it was written), to the host: W*H*4 floats */
+rsrt_status rsrt_upsampled_download(rsrt_context *ctx, float *host_rgba, size_t n_floats);
+/* ... through the display pass: rsrt_display_pixel(upsampled, 1.0f) per pixel (include/rsrt_tonemap.h), RGBA8, alpha 255 */
+rsrt_status rsrt_upsampled_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -137,6 +137,7 @@ public:
             check(rsrt_multi_clear(m_));
             sample_count_ = 0;
             if (have_aov_) clear_aov();
+            if (guide_width_) clear_guide();
         }
         rsrt_camera cam;
         rsrt_camera_uniform(&camera_, &cam);
@@ -178,6 +179,65 @@ public:
         std::vector<float> out((size_t)width_ * height_ * 4);
         check_ctx(rsrt_denoised_download(context(0), out.data(), out.size()));
         return out;
+    }
+    // -- guided upsampling (rsrt.h "guided upsampling"): one device, like the denoiser -----------------------------
+    // The State's own size is the LOW size the paths are traced at; the guide has the output's.  The caller picks a low size of the
+    // output's aspect (ceil(W / 2) x ceil(H / 2) for half size).  The guide wants as many samples as the low frame.
+    // rsrt_guide_render of samples [sample_begin, sample_begin + n) for a frame of width x height into device 0's guide (raw: no hash check)
+    void render_guide(uint32_t width, uint32_t height, uint32_t sample_begin, uint32_t n)
+    {
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        check_ctx(rsrt_guide_render(context(0), &cam, width, height, sample_begin, n, 0, nullptr));
+        guide_width_ = width; guide_height_ = height;
+        guide_sample_count_ += n;
+    }
+    void clear_guide()
+    {
+        check_ctx(rsrt_guide_clear(context(0)));
+        guide_sample_count_ = 0;
+    }
+    uint32_t guide_sample_count() const { return guide_sample_count_; }
+    uint32_t guide_width() const { return guide_width_; }
+    uint32_t guide_height() const { return guide_height_; }
+    std::vector<float> download_guide() // W*H*8 of the guide's size: albedo sum xyz, hits, normal sum xyz, distance sum
+    {
+        std::vector<float> out((size_t)guide_width_ * guide_height_ * 8);
+        check_ctx(rsrt_guide_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    static rsrt_upsample_params upsample_defaults() { return rsrt_upsample_params{RSRT_UPSAMPLE_DEMODULATE, 0.5f, 0.3f}; }
+    // rsrt_upsample of the low frame to the guide's size: W*H*4 f32 (alpha 1).  The low colour is the mean of sample_count() samples, or
+    // with RSRT_UPSAMPLE_DENOISED / RSRT_UPSAMPLE_TEMPORAL in p.flags the last denoise() output / the last render_temporal frame's colour.
+    std::vector<float> upsample(const rsrt_upsample_params &p = upsample_defaults())
+    {
+        check_ctx(rsrt_upsample(context(0), sample_count_, aov_sample_count_, guide_sample_count_, &p, nullptr, nullptr));
+        std::vector<float> out((size_t)guide_width_ * guide_height_ * 4);
+        check_ctx(rsrt_upsampled_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    std::vector<uint8_t> upsampled_display() // the last upsample() through the display pass
+    {
+        std::vector<uint8_t> out((size_t)guide_width_ * guide_height_ * 4);
+        check_ctx(rsrt_upsampled_display_srgb8(context(0), out.data(), out.size()));
+        return out;
+    }
+    // one progressive step of a picture of out_width x out_height traced at the State's own (low) size: render_samples(n, true), the
+    // guide over the same samples at the output size (a changed camera / environment cleared it with the accumulator; another size
+    // starts it anew), denoise() and the upsample of its output — or of the mean with denoise = false
+    std::vector<float> render_upsampled(uint32_t out_width, uint32_t out_height, uint32_t n = 1, bool denoise = true)
+    {
+        const uint32_t begin = (have_hash_ && scene_hash() == last_hash_) ? sample_count_ : 0u;
+        render_samples(n, true);
+        if (guide_width_ != out_width || guide_height_ != out_height) guide_sample_count_ = 0; // a guide of another size is allocated zeroed
+        render_guide(out_width, out_height, begin, n);
+        rsrt_upsample_params p = upsample_defaults();
+        if (denoise) {
+            const rsrt_denoise_params d = denoise_defaults();
+            check_ctx(rsrt_denoise(context(0), sample_count_, aov_sample_count_, &d, nullptr, nullptr));
+            p.flags |= RSRT_UPSAMPLE_DENOISED;
+        }
+        return upsample(p);
     }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
@@ -277,6 +337,7 @@ private:
     rsrt_camera_desc camera_{};
     uint32_t width_ = 0, height_ = 0, sample_count_ = 0, aov_sample_count_ = 0;
     bool have_aov_ = false;
+    uint32_t guide_width_ = 0, guide_height_ = 0, guide_sample_count_ = 0;
     uint32_t temporal_sample_count_ = 0, temporal_key_[6] = {0, 0, 0, 0, 0, 0};
     bool have_temporal_key_ = false;
     size_t last_hash_ = 0;

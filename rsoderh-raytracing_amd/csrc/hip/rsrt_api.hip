@@ -601,6 +601,17 @@ struct rsrt_context {
     // history) and whether the last frame carried them
     float4 *tp_mom = nullptr;
     uint32_t tp_moments = 0;
+    // guided upsampling (rt_upsample.h): the guide records of the output size (bound or owned, 2 float4 a pixel; independent of the
+    // accumulator's size), the low pass's scratch (float4 + ushort4 a low pixel), the library-owned output and where the last rsrt_upsample wrote
+    float4 *guide = nullptr;
+    float4 *guide_owned = nullptr;
+    uint32_t guide_w = 0, guide_h = 0;
+    void *up_scratch = nullptr;
+    uint32_t up_w = 0, up_h = 0;
+    float4 *up_out = nullptr;
+    uint32_t up_out_w = 0, up_out_h = 0;
+    float4 *up_last = nullptr;
+    uint32_t up_last_w = 0, up_last_h = 0;
 };
 
 namespace {
@@ -1075,11 +1086,10 @@ rsrt_status pack_environment(rsrt_context *ctx, Env &e)
     return RSRT_OK;
 }
 
-// rsrt_display_srgb8 on any W*H RGBA32F sum that lives on ctx's device (the multi-GPU frame buffer uses it too)
-rsrt_status display_from(rsrt_context *ctx, const float4 *sum, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
+// rsrt_display_srgb8 on any RGBA32F sum of n pixels that lives on ctx's device
+rsrt_status display_from_n(rsrt_context *ctx, const float4 *sum, size_t n, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
 {
     DeviceGuard g(ctx->device);
-    const size_t n = (size_t)ctx->acc_w * ctx->acc_h;
     if (!host_rgba8 || n_bytes != n * 4 || sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_srgb8: expected %zu bytes and sample_total > 0", n * 4);
     rsrt_status st = ensure_scratch(ctx, n * sizeof(uchar4));
     if (st || (st = begin_work(ctx, ctx->stream))) return st;
@@ -1090,6 +1100,12 @@ rsrt_status display_from(rsrt_context *ctx, const float4 *sum, uint32_t sample_t
     if ((st = end_work(ctx, ctx->stream))) return st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RSRT_OK;
+}
+
+// ... of the accumulator's size (the multi-GPU frame buffer uses it too)
+rsrt_status display_from(rsrt_context *ctx, const float4 *sum, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
+{
+    return display_from_n(ctx, sum, (size_t)ctx->acc_w * ctx->acc_h, sample_total, host_rgba8, n_bytes);
 }
 
 } // namespace
@@ -1175,6 +1191,9 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->dn_scratch);
     (void)hipFree(ctx->tp_buf);
     (void)hipFree(ctx->tp_mom);
+    (void)hipFree(ctx->guide_owned);
+    (void)hipFree(ctx->up_scratch);
+    (void)hipFree(ctx->up_out);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -2261,3 +2280,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_denoise.h"
 #include "rt_temporal.h"
 #include "rt_variance.h"
+#include "rt_upsample.h"

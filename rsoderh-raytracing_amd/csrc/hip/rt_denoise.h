@@ -169,6 +169,32 @@ rsrt_status ensure_denoise_scratch(rsrt_context *ctx)
     return RSRT_OK;
 }
 
+// the AOV pass of samples [sample_begin, sample_begin + sample_count) into `aov`, a width x height record buffer (the AOV buffer, or the
+// upsampler's guide: rt_upsample.h)
+rsrt_status launch_aov(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin, uint32_t sample_count,
+                       float4 *aov, hipStream_t stream)
+{
+    RenderParams P;
+    memset(&P, 0, sizeof P);
+    P.scene = ctx->scene;
+    memcpy(P.cam_pos, camera->pos, 12);
+    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) P.cam_rot[3 * j + k] = camera->rot_transform[j][k];
+    P.fov_y = camera->fov_y;
+    P.width = width; P.height = height;
+    P.sample_begin = sample_begin; P.sample_count = sample_count;
+    const bool lds = P.scene.lds_float4s != 0;
+    const size_t smem = lds ? (size_t)P.scene.lds_float4s * sizeof(float4) : 0u;
+    const void *kfn = lds ? reinterpret_cast<const void *>(&rt_aov_kernel<1>) : reinterpret_cast<const void *>(&rt_aov_kernel<0>);
+    if (lds) HIP_TRY(ctx, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const uint64_t n = (uint64_t)width * height;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + RT_BLOCK - 1) / RT_BLOCK, (uint64_t)ctx->cus * 8u);
+    rsrt_status st = begin_work(ctx, stream);
+    if (st) return st;
+    void *kargs[] = {&P, &aov};
+    HIP_TRY(ctx, hipLaunchKernel(kfn, dim3(blocks), dim3(RT_BLOCK), kargs, smem, stream));
+    return end_work(ctx, stream);
+}
+
 bool sigma_ok(float s) { return s >= 1.0e-6f && s <= 1.0e6f; }
 
 // the clamp / variance pass and the L >= 1 levels after rt_dn_prepare_kernel wrote ping and feat (rt_variance.h)
@@ -194,25 +220,7 @@ rsrt_status rsrt_aov_render(rsrt_context *ctx, const rsrt_camera *camera, uint32
     rsrt_status st = ensure_accumulator(ctx, width, height);
     if (st || (st = ensure_aov(ctx))) return st;
     if (sample_count == 0) return RSRT_OK;
-    RenderParams P;
-    memset(&P, 0, sizeof P);
-    P.scene = ctx->scene;
-    memcpy(P.cam_pos, camera->pos, 12);
-    for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) P.cam_rot[3 * j + k] = camera->rot_transform[j][k];
-    P.fov_y = camera->fov_y;
-    P.width = width; P.height = height;
-    P.sample_begin = sample_begin; P.sample_count = sample_count;
-    const bool lds = P.scene.lds_float4s != 0;
-    const size_t smem = lds ? (size_t)P.scene.lds_float4s * sizeof(float4) : 0u;
-    const void *kfn = lds ? reinterpret_cast<const void *>(&rt_aov_kernel<1>) : reinterpret_cast<const void *>(&rt_aov_kernel<0>);
-    if (lds) HIP_TRY(ctx, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    const uint64_t n = (uint64_t)width * height;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + RT_BLOCK - 1) / RT_BLOCK, (uint64_t)ctx->cus * 8u);
-    if ((st = begin_work(ctx, stream))) return st;
-    float4 *aov = ctx->aov;
-    void *kargs[] = {&P, &aov};
-    HIP_TRY(ctx, hipLaunchKernel(kfn, dim3(blocks), dim3(RT_BLOCK), kargs, smem, stream));
-    return end_work(ctx, stream);
+    return launch_aov(ctx, camera, width, height, sample_begin, sample_count, ctx->aov, stream);
 }
 
 rsrt_status rsrt_aov_bind(rsrt_context *ctx, void *device_f32x8, uint32_t width, uint32_t height)

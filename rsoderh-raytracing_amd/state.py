@@ -32,7 +32,9 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_multi_synchronize", "rsrt_multi_download", "rsrt_multi_display_srgb8", "rsrt_multi_get_stats", "rsrt_multi_uses_rccl",
             "rsrt_aov_render", "rsrt_aov_bind", "rsrt_aov_clear", "rsrt_aov_download", "rsrt_denoise", "rsrt_denoised_download",
             "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download",
-            "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download"]
+            "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download",
+            "rsrt_guide_render", "rsrt_guide_bind", "rsrt_guide_clear", "rsrt_guide_download", "rsrt_upsample", "rsrt_upsampled_download",
+            "rsrt_upsampled_display_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -54,6 +56,17 @@ TEMPORAL_MOMENTS = 1  # rsrt_temporal_accumulate_ex flags: keep the luminance mo
 DENOISE_VARIANCE = 4  # rsrt_denoise_params.flags: variance-guided levels (include/rsrt_variance.h)
 DENOISE_CLAMP = 8     # ... and the firefly clamp of the filter's input
 VARIANCE_SIGMA_L = 4.0  # sigma_color's default under DENOISE_VARIANCE (RSRT_SV_SIGMA_L: SVGF's sigma_l)
+
+
+# rsrt_upsample_params.flags and defaults (include/rsrt.h "guided upsampling")
+UPSAMPLE_DEMODULATE = 1  # upsample colour / albedo, then multiply the guide's albedo back
+UPSAMPLE_DENOISED = 2    # the low colour is the last denoise() output
+UPSAMPLE_TEMPORAL = 4    # ... the last render_temporal frame's colour
+UPSAMPLE_DEFAULTS = {"sigma_normal": 0.5, "sigma_depth": 0.3, "demodulate": True}
+
+
+class UpsampleParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
 
 
 class TemporalParams(C.Structure):
@@ -162,6 +175,13 @@ def lib():
         L.rsrt_temporal_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_temporal_accumulate_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
         L.rsrt_temporal_moments_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_guide_render.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 5 + [C.c_void_p]
+        L.rsrt_guide_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.rsrt_guide_clear.argtypes = [C.c_void_p]
+        L.rsrt_guide_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_upsample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsrt_upsampled_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_upsampled_display_srgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -188,6 +208,9 @@ class State:
         self._has_aov = False
         self.temporal_sample_count = 0  # first sample index of the next render_temporal frame (only grows until temporal_reset)
         self._temporal_key = None       # what the history was rendered under: environment, bounces, flags, size
+        self.guide_sample_count = 0     # samples in the upsampler's guide (render_guide / render_upsampled)
+        self.guide_width = self.guide_height = 0  # the guide's size: what upsample() returns
+        self._guide_bound = False
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -306,6 +329,8 @@ class State:
             self.clear()
             if self._has_aov:
                 self.clear_aov()
+            if self.guide_width:
+                self.clear_guide()
         self._check(self._L.rsrt_render(self._ctx, _p(self.camera), self.width, self.height, self.sample_count, n,
                                         self.max_bounces, self.environment_index, self.flags,
                                         C.c_void_p(stream) if stream else None), "rsrt_render")
@@ -380,6 +405,78 @@ class State:
         out = np.empty((self.height, self.width, 4), np.uint8)
         self._check(self._L.rsrt_denoised_display_srgb8(self._ctx, _p(out), out.size), "rsrt_denoised_display_srgb8")
         return out
+
+    # -- guided upsampling (include/rsrt.h "guided upsampling") --------------------------------------
+    # The state's own size (resize) is the LOW size the paths are traced at; the guide has the output's.  The caller picks a low size of
+    # the output's aspect: ceil(W / 2) x ceil(H / 2) for half size.  The guide wants as many samples as the low frame.
+    def render_guide(self, width, height, sample_begin, sample_count, stream=None):
+        """rsrt_guide_render: adds the first hits of the camera rays of samples [sample_begin, sample_begin + sample_count), for a frame of
+        width x height, to the guide.  Raw, like render_aov: no hash check; guide_sample_count grows by sample_count."""
+        self._check(self._L.rsrt_guide_render(self._ctx, _p(self.camera), width, height, sample_begin, sample_count, 0,
+                                              C.c_void_p(stream) if stream else None), "rsrt_guide_render")
+        self.guide_width, self.guide_height = width, height
+        self.guide_sample_count += sample_count
+
+    def bind_guide(self, device_ptr, width, height):
+        """Use caller-owned device memory (W*H*8 f32) as the guide (None: back to the library's, which the next render_guide allocates)."""
+        self._check(self._L.rsrt_guide_bind(self._ctx, C.c_void_p(device_ptr) if device_ptr else None, width, height), "rsrt_guide_bind")
+        if device_ptr:
+            self.guide_width, self.guide_height, self._guide_bound = width, height, True
+        elif self._guide_bound:  # (the library gave its own buffer up at the bind)
+            self.guide_width, self.guide_height, self._guide_bound = 0, 0, False
+
+    def clear_guide(self):
+        self._check(self._L.rsrt_guide_clear(self._ctx), "rsrt_guide_clear")
+        self.guide_sample_count = 0
+
+    def download_guide(self):
+        """[H, W, 8] float32 of the guide's size: albedo sum xyz, hits, normal sum xyz, distance sum."""
+        out = np.empty((self.guide_height, self.guide_width, AOV_FLOATS), np.float32)
+        self._check(self._L.rsrt_guide_download(self._ctx, _p(out), out.size), "rsrt_guide_download")
+        return out
+
+    def upsample(self, source="mean", sigma_normal=None, sigma_depth=None, demodulate=None, sample_total=None, aov_sample_total=None,
+                 guide_sample_total=None, out_ptr=None, stream=None, download=True):
+        """rsrt_upsample of the low frame to the guide's size: [H, W, 4] float32 (alpha 1), or None with download=False (the result stays
+        on the device: upsampled_display_srgb8, or out_ptr when given).  source: "mean" (the accumulator's), "denoised" (the last
+        denoise() output) or "temporal" (the last render_temporal frame's colour).  Unset arguments take UPSAMPLE_DEFAULTS and the
+        sample counters."""
+        d = UPSAMPLE_DEFAULTS
+        pick = lambda v, k: d[k] if v is None else v  # noqa: E731
+        src = {"mean": 0, "denoised": UPSAMPLE_DENOISED, "temporal": UPSAMPLE_TEMPORAL}
+        if source not in src:
+            raise ValueError("upsample: source is 'mean', 'denoised' or 'temporal', not %r" % (source,))
+        p = UpsampleParams((UPSAMPLE_DEMODULATE if pick(demodulate, "demodulate") else 0) | src[source], pick(sigma_normal, "sigma_normal"),
+                           pick(sigma_depth, "sigma_depth"))
+        n = self.sample_count if sample_total is None else sample_total
+        na = self.aov_sample_count if aov_sample_total is None else aov_sample_total
+        ng = self.guide_sample_count if guide_sample_total is None else guide_sample_total
+        self._check(self._L.rsrt_upsample(self._ctx, n, na, ng, C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
+                                          C.c_void_p(stream) if stream else None), "rsrt_upsample")
+        if not download:
+            return None
+        out = np.empty((self.guide_height, self.guide_width, 4), np.float32)
+        self._check(self._L.rsrt_upsampled_download(self._ctx, _p(out), out.size), "rsrt_upsampled_download")
+        return out
+
+    def upsampled_display_srgb8(self):
+        """The last upsample() output through the display pass (rsrt_display_pixel(upsampled, 1)): [H, W, 4] uint8."""
+        out = np.empty((self.guide_height, self.guide_width, 4), np.uint8)
+        self._check(self._L.rsrt_upsampled_display_srgb8(self._ctx, _p(out), out.size), "rsrt_upsampled_display_srgb8")
+        return out
+
+    def render_upsampled(self, out_width, out_height, n=1, denoise=True):
+        """One progressive step of a picture of out_width x out_height traced at the state's own (low) size: render_samples(n, aov=True),
+        the guide over the same samples at the output size (cleared first when the camera / environment changed or its size differs),
+        denoise() and upsample("denoised") — or upsample("mean") with denoise=False.  Returns the picture, [out_height, out_width, 4]."""
+        begin = self.sample_count if self._scene_hash() == self._last_hash else 0
+        self.render_samples(n, aov=True)  # (a changed camera / environment cleared the guide with the accumulator)
+        if (self.guide_width, self.guide_height) != (out_width, out_height):
+            self.guide_sample_count = 0  # a guide of another size is allocated zeroed
+        self.render_guide(out_width, out_height, begin, n)
+        if denoise:
+            self.denoise(download=False)
+        return self.upsample("denoised" if denoise else "mean")
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):
