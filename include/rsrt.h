@@ -421,6 +421,44 @@ rsrt_status rsrt_upsampled_download(rsrt_context *ctx, float *host_rgba, size_t 
 /* ... through the display pass: rsrt_display_pixel(upsampled, 1.0f) per pixel (include/rsrt_tonemap.h), RGBA8, alpha 255 */
 rsrt_status rsrt_upsampled_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes);
 
+/* -- noise estimate: how noisy is the picture in the accumulator still, and where (no reference counterpart) ------------------
+ * The accumulator sums a pixel's samples in increasing order, so a copy of it taken at n1 samples and the accumulator at n2 > n1
+ * hold two estimates of every pixel, the first n1 samples and all n2 (the half buffer of Dammertz et al., "A Hierarchical Automatic
+ * Stopping Condition for Monte Carlo Global Illumination", 2010): one device copy, no extra ray.  Per pixel the estimate is the
+ * summed absolute difference of the two means over the square root of the mean's rgb sum; per tile the mean over the tile's pixels
+ * inside the frame; the arithmetic is published in include/rsrt_noise.h.  With n1 = n2 / 2 it estimates the error of the mean of all
+ * n2 samples.  Whole frame only, like the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.  Nothing here
+ * writes the accumulator, the AOV buffer, the guide or any history.
+ *
+ * The snapshot and the last estimate are dropped by rsrt_noise_reset, rsrt_accumulator_clear (a cleared accumulator makes the pair
+ * meaningless), rsrt_accumulator_resize to another size and rsrt_accumulator_bind of another size; a bind of the same size keeps them.
+ * rsrt_noise_params defaults: tile_w 16, tile_h 16, threshold 0, flags 0. */
+typedef struct rsrt_noise_params {
+    uint32_t tile_w, tile_h; /* tile_w * tile_h a multiple of 64, at most 4096 (the partition's rule); a tile may exceed the frame */
+    float threshold;         /* what rsrt_noise_summary.tiles_above counts against: >= 0, +inf allowed */
+    uint32_t flags;          /* 0 */
+} rsrt_noise_params;
+typedef struct rsrt_noise_summary {
+    float max_error, mean_error; /* over the tile map in row-major order; the mean is a sequential f32 sum / tile count */
+    uint32_t tiles_x, tiles_y;   /* ceil(width / tile_w), ceil(height / tile_h) */
+    uint32_t tiles_above;        /* tiles with error > threshold; an infinite error (a pixel with inf or NaN radiance) always counts */
+    uint32_t _pad;
+} rsrt_noise_summary;
+/* Copies the accumulator, the sum of sample_total >= 1 samples, into a library-owned buffer of its size (device to device, ordered
+ * after everything enqueued so far; asynchronous on hip_stream, NULL = the context's stream).  RSRT_ERR_NOT_READY without an
+ * accumulator; RSRT_ERR_INVALID_ARGUMENT for sample_total 0. */
+rsrt_status rsrt_noise_snapshot(rsrt_context *ctx, uint32_t sample_total, void *hip_stream);
+/* The tile map of the accumulator, now the sum of sample_total samples, against the snapshot: tiles_x * tiles_y floats in a
+ * library-owned buffer.  Asynchronous.  RSRT_ERR_NOT_READY without an accumulator or a snapshot of it; RSRT_ERR_INVALID_ARGUMENT for
+ * NULL params, non-zero flags, a bad tile, a negative or NaN threshold, sample_total not above the snapshot's.  Nothing is launched
+ * on a refused call, and the last estimate stays what it was. */
+rsrt_status rsrt_noise_estimate(rsrt_context *ctx, uint32_t sample_total, const rsrt_noise_params *params, void *hip_stream);
+/* Waits, copies the last estimate's tiles_x * tiles_y floats (row-major) to host_tiles and fills *out.  host_tiles may be NULL for
+ * the summary alone (n_floats is then ignored), out may be NULL for the tiles alone.  RSRT_ERR_NOT_READY without an estimate since
+ * the last reset; RSRT_ERR_INVALID_ARGUMENT for another n_floats. */
+rsrt_status rsrt_noise_download(rsrt_context *ctx, float *host_tiles, size_t n_floats, rsrt_noise_summary *out);
+rsrt_status rsrt_noise_reset(rsrt_context *ctx);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -239,6 +239,46 @@ public:
         }
         return upsample(p);
     }
+    // -- the noise estimate (rsrt.h "noise estimate"): one device, like the denoiser -------------------------------
+    struct NoiseRound { uint32_t n1, n2; float max_error, mean_error; uint32_t tiles_above; };
+    static rsrt_noise_params noise_defaults() { return rsrt_noise_params{16u, 16u, 0.0f, 0u}; }
+    void noise_snapshot() { check_ctx(rsrt_noise_snapshot(context(0), sample_count_, nullptr)); } // a copy of the sum of sample_count() samples
+    // rsrt_noise_estimate of the accumulator against the last noise_snapshot(): the tile map, tiles_y rows of tiles_x; *summary when given
+    std::vector<float> noise_estimate(const rsrt_noise_params &p = noise_defaults(), rsrt_noise_summary *summary = nullptr)
+    {
+        check_ctx(rsrt_noise_estimate(context(0), sample_count_, &p, nullptr));
+        return noise_download(summary);
+    }
+    std::vector<float> noise_download(rsrt_noise_summary *summary = nullptr) // the last noise_estimate()
+    {
+        rsrt_noise_summary s;
+        check_ctx(rsrt_noise_download(context(0), nullptr, 0, &s));
+        std::vector<float> tiles((size_t)s.tiles_x * s.tiles_y);
+        check_ctx(rsrt_noise_download(context(0), tiles.data(), tiles.size(), &s));
+        if (summary) *summary = s;
+        return tiles;
+    }
+    void noise_reset() { check_ctx(rsrt_noise_reset(context(0))); }
+    // renders until the largest tile error is at most `threshold` or max_samples are in: clears and renders min_samples, then per round
+    // snapshots at n samples, renders up to min(2 n, max_samples) and estimates.  Returns the rounds; sample_count() is the total.  The
+    // accumulator is what render_samples(total) leaves from a clear, bit for bit.
+    std::vector<NoiseRound> render_to_noise(float threshold, uint32_t min_samples = 8, uint32_t max_samples = 1024, uint32_t tile_w = 16,
+                                            uint32_t tile_h = 16)
+    {
+        if (min_samples < 1 || max_samples <= min_samples) throw Error("render_to_noise: 1 <= min_samples < max_samples");
+        have_hash_ = false; // start from a clear, whatever was rendered before
+        render_samples(min_samples);
+        std::vector<NoiseRound> rounds;
+        for (;;) {
+            const uint32_t n1 = sample_count_;
+            noise_snapshot();
+            render_samples((2u * n1 < max_samples ? 2u * n1 : max_samples) - n1);
+            rsrt_noise_summary s;
+            noise_estimate(rsrt_noise_params{tile_w, tile_h, threshold, 0u}, &s);
+            rounds.push_back(NoiseRound{n1, sample_count_, s.max_error, s.mean_error, s.tiles_above});
+            if (s.max_error <= threshold || sample_count_ >= max_samples) return rounds;
+        }
+    }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
     // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass

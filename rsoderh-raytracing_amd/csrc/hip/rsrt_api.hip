@@ -612,6 +612,15 @@ struct rsrt_context {
     uint32_t up_out_w = 0, up_out_h = 0;
     float4 *up_last = nullptr;
     uint32_t up_last_w = 0, up_last_h = 0;
+    // noise estimate (rt_noise.h): the snapshot of the accumulator (freed when the accumulator's size changes), how many samples it holds
+    // (0: none), the tile map of the last rsrt_noise_estimate, its shape and threshold and whether there was one since the last reset
+    float4 *ns_snap = nullptr;
+    uint32_t ns_w = 0, ns_h = 0, ns_total = 0;
+    float *ns_tiles = nullptr;
+    size_t ns_tiles_cap = 0;
+    uint32_t ns_tx = 0, ns_ty = 0;
+    float ns_threshold = 0.0f;
+    bool ns_have = false;
 };
 
 namespace {
@@ -839,6 +848,24 @@ void free_temporal(rsrt_context *ctx)
     ctx->tp_w = ctx->tp_h = ctx->tp_cur = ctx->tp_frames = ctx->tp_moments = 0;
 }
 
+// the snapshot and the last estimate mean nothing any more (a cleared accumulator, a reset); the buffers stay
+void drop_noise(rsrt_context *ctx)
+{
+    ctx->ns_total = 0;
+    ctx->ns_have = false;
+}
+
+void free_noise(rsrt_context *ctx)
+{
+    (void)hipFree(ctx->ns_snap);
+    (void)hipFree(ctx->ns_tiles);
+    ctx->ns_snap = nullptr;
+    ctx->ns_tiles = nullptr;
+    ctx->ns_tiles_cap = 0;
+    ctx->ns_w = ctx->ns_h = ctx->ns_tx = ctx->ns_ty = 0;
+    drop_noise(ctx);
+}
+
 // the temporal history of the last frame (valid when tp_frames > 0)
 float4 *temporal_history(rsrt_context *ctx) { return ctx->tp_buf + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
 // ... and its moment records (valid when tp_moments is set too)
@@ -853,6 +880,7 @@ rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
     HIP_TRY(ctx, hipDeviceSynchronize());
     free_denoise_scratch(ctx);
     free_temporal(ctx);
+    free_noise(ctx);
     HIP_TRY(ctx, hipMalloc(&ctx->accum_owned, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipMemset(ctx->accum_owned, 0, (size_t)w * h * sizeof(float4)));
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -1194,6 +1222,8 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->guide_owned);
     (void)hipFree(ctx->up_scratch);
     (void)hipFree(ctx->up_out);
+    (void)hipFree(ctx->ns_snap);
+    (void)hipFree(ctx->ns_tiles);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -1895,7 +1925,7 @@ rsrt_status rsrt_accumulator_bind(rsrt_context *ctx, void *device_rgba32f, uint3
     if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
     if ((uintptr_t)device_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "accumulator pointer must be 16-byte aligned");
     if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; }
-    if (width != ctx->acc_w || height != ctx->acc_h) { free_denoise_scratch(ctx); free_temporal(ctx); }
+    if (width != ctx->acc_w || height != ctx->acc_h) { free_denoise_scratch(ctx); free_temporal(ctx); free_noise(ctx); }
     ctx->accum = static_cast<float4 *>(device_rgba32f);
     ctx->acc_w = width;
     ctx->acc_h = height;
@@ -1910,6 +1940,7 @@ rsrt_status rsrt_accumulator_clear(rsrt_context *ctx)
     rsrt_status st = begin_work(ctx, ctx->stream);
     if (st) return st;
     HIP_TRY(ctx, hipMemsetAsync(ctx->accum, 0, (size_t)ctx->acc_w * ctx->acc_h * sizeof(float4), ctx->stream));
+    drop_noise(ctx); // (a snapshot of what was cleared pairs with nothing)
     return end_work(ctx, ctx->stream);
 }
 
@@ -2281,3 +2312,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_temporal.h"
 #include "rt_variance.h"
 #include "rt_upsample.h"
+#include "rt_noise.h"

@@ -34,7 +34,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download",
             "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download",
             "rsrt_guide_render", "rsrt_guide_bind", "rsrt_guide_clear", "rsrt_guide_download", "rsrt_upsample", "rsrt_upsampled_download",
-            "rsrt_upsampled_display_srgb8"]
+            "rsrt_upsampled_display_srgb8", "rsrt_noise_snapshot", "rsrt_noise_estimate", "rsrt_noise_download", "rsrt_noise_reset"]
 
 
 class RsrtError(RuntimeError):
@@ -67,6 +67,19 @@ UPSAMPLE_DEFAULTS = {"sigma_normal": 0.5, "sigma_depth": 0.3, "demodulate": True
 
 class UpsampleParams(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float)]
+
+
+# rsrt_noise_params defaults (include/rsrt.h "noise estimate")
+NOISE_DEFAULTS = {"tile": (16, 16), "threshold": 0.0}
+
+
+class NoiseParams(C.Structure):
+    _fields_ = [("tile_w", C.c_uint32), ("tile_h", C.c_uint32), ("threshold", C.c_float), ("flags", C.c_uint32)]
+
+
+class NoiseSummary(C.Structure):
+    _fields_ = [("max_error", C.c_float), ("mean_error", C.c_float), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
+                ("tiles_above", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class TemporalParams(C.Structure):
@@ -182,6 +195,10 @@ def lib():
         L.rsrt_upsample.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsrt_upsampled_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_upsampled_display_srgb8.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_noise_snapshot.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.rsrt_noise_estimate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_noise_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_noise_reset.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -477,6 +494,55 @@ class State:
         if denoise:
             self.denoise(download=False)
         return self.upsample("denoised" if denoise else "mean")
+
+    # -- noise estimate (include/rsrt.h "noise estimate") --------------------------------------------
+    def noise_snapshot(self, sample_total=None, stream=None):
+        """rsrt_noise_snapshot: keeps a copy of the accumulator, the sum of sample_total (default: sample_count) samples."""
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_noise_snapshot(self._ctx, n, C.c_void_p(stream) if stream else None), "rsrt_noise_snapshot")
+
+    def noise_estimate(self, tile=(16, 16), threshold=0.0, sample_total=None, stream=None, download=True):
+        """rsrt_noise_estimate of the accumulator (sample_total samples, default sample_count) against the last noise_snapshot():
+        (tile map [tiles_y, tiles_x] float32, summary dict with max_error, mean_error, tiles_x, tiles_y, tiles_above), or None with
+        download=False (noise_download() fetches it later)."""
+        p = NoiseParams(tile[0], tile[1], threshold, 0)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_noise_estimate(self._ctx, n, C.byref(p), C.c_void_p(stream) if stream else None), "rsrt_noise_estimate")
+        return self.noise_download() if download else None
+
+    def noise_download(self):
+        """The last noise_estimate(): (tile map [tiles_y, tiles_x] float32, summary dict)."""
+        s = NoiseSummary()
+        self._check(self._L.rsrt_noise_download(self._ctx, None, 0, C.byref(s)), "rsrt_noise_download")
+        tiles = np.empty((s.tiles_y, s.tiles_x), np.float32)
+        self._check(self._L.rsrt_noise_download(self._ctx, _p(tiles), tiles.size, C.byref(s)), "rsrt_noise_download")
+        return tiles, {"max_error": s.max_error, "mean_error": s.mean_error, "tiles_x": s.tiles_x, "tiles_y": s.tiles_y,
+                       "tiles_above": s.tiles_above}
+
+    def noise_reset(self):
+        """Drops the snapshot and the last estimate (clear(), resize() and a bind of another size do so too)."""
+        self._check(self._L.rsrt_noise_reset(self._ctx), "rsrt_noise_reset")
+
+    def render_to_noise(self, threshold, min_samples=8, max_samples=1024, tile=(16, 16), on_round=None):
+        """Renders until the largest tile error is at most `threshold` or max_samples are in: clears and renders min_samples, then per
+        round snapshots at n samples, renders up to min(2 n, max_samples) and estimates.  Returns (total, rounds), rounds a list of
+        (n1, n2, max_error, mean_error, tiles_above); on_round, when given, is called with each as it is known.  The accumulator is
+        what render_samples(total) leaves from a clear, bit for bit: the estimate only reads it."""
+        if not (min_samples >= 1 and max_samples > min_samples):
+            raise ValueError("render_to_noise: 1 <= min_samples < max_samples")
+        self._last_hash = None  # start from a clear, whatever was rendered before
+        self.render_samples(min_samples)
+        rounds = []
+        while True:
+            n1 = self.sample_count
+            self.noise_snapshot()
+            self.render_samples(min(2 * n1, max_samples) - n1)
+            _, s = self.noise_estimate(tile, threshold)
+            rounds.append((n1, self.sample_count, s["max_error"], s["mean_error"], s["tiles_above"]))
+            if on_round:
+                on_round(rounds[-1])
+            if s["max_error"] <= threshold or self.sample_count >= max_samples:
+                return self.sample_count, rounds
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):

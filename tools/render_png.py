@@ -1,5 +1,7 @@
-"""python tools/render_png.py <scene> <w> <h> <spp> <bounces> <out.png> [--denoise] — render through the product path and write the
-display image; --denoise: the AOV pass over the same samples and the default filter, the denoised display image instead."""
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] — render through the product path and
+write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise estimate is at most X
+(State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the same samples and the
+default filter, the denoised display image instead."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -7,10 +9,18 @@ import rsoderh_raytracing_amd as R
 from rsoderh_raytracing_amd import host
 denoise = "--denoise" in sys.argv
 args = [a for a in sys.argv[1:] if a != "--denoise"]
-name, w, h, spp, mb, out = args[0], int(args[1]), int(args[2]), int(args[3]), int(args[4]), args[5]
+name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
-st.render_samples(spp, aov=denoise)
+if args[3].startswith("noise="):
+    target = args[3][len("noise="):].split(",")
+    spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024,
+                                on_round=lambda r: print("samples %4d -> %4d: max tile error %.4f, mean %.4f, %d tiles above" % r, flush=True))
+    print("stopped at", spp, "samples")
+    if denoise:
+        st.render_aov(0, spp)
+else:
+    st.render_samples(int(args[3]), aov=denoise)
 if denoise:
     st.denoise(download=False)
     host.write_png(out, st.denoised_display_srgb8())
