@@ -459,6 +459,60 @@ rsrt_status rsrt_noise_estimate(rsrt_context *ctx, uint32_t sample_total, const 
 rsrt_status rsrt_noise_download(rsrt_context *ctx, float *host_tiles, size_t n_floats, rsrt_noise_summary *out);
 rsrt_status rsrt_noise_reset(rsrt_context *ctx);
 
+/* -- auto-exposure: a luminance histogram meter and an exposed display (no reference counterpart) -----------------------------
+ * Every other display call shows the picture at an exposure of 1, so whether it is usable depends on the scale of the environment
+ * the caller uploaded.  rsrt_exposure_meter builds, on the device and in integers, a 256-bin histogram of the log-luminance of one
+ * of the four images the library can hold (eight bins an octave, 2^-16 .. 2^16; word 256 counts the pixels with no positive
+ * luminance); rsrt_exposure_download turns it into an exposure — the log-average ("key") meter of Reinhard et al. 2002 over the
+ * ranks [low_permille, high_permille) of the metered pixels; rsrt_display_exposed_srgb8 is the display pass with the exposure
+ * multiplied in after the binary16 rounding of the mean.  The arithmetic is published in include/rsrt_exposure.h; the histogram
+ * is independent of the order pixels are counted in, so it and the exposure are bitwise reproducible.
+ *
+ * The library keeps NO exposure: adaptation over time goes through previous_exposure and blend (the State classes remember the
+ * last value).  The histogram stays valid until the next rsrt_exposure_meter, rsrt_exposure_reset or rsrt_context_destroy.  Whole
+ * frame only, like the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.  Nothing here writes the
+ * accumulator, the AOV buffer, the guide, any history, the denoised image or the upsampled image.  A refused call launches nothing
+ * and leaves the last histogram as it was.
+ * rsrt_exposure_params defaults: low_permille 100, high_permille 950, key 0.18, min_exposure 2^-16, max_exposure 2^16, blend 1,
+ * previous_exposure 0, flags 0. */
+enum {
+    RSRT_EXPOSURE_MEAN = 0,      /* the accumulator, sum / sample_total */
+    RSRT_EXPOSURE_DENOISED = 1,  /* the last rsrt_denoise output */
+    RSRT_EXPOSURE_TEMPORAL = 2,  /* the colour of the last temporal frame's history */
+    RSRT_EXPOSURE_UPSAMPLED = 3  /* the last rsrt_upsample output, of the guide's size */
+};
+typedef struct rsrt_exposure_params {
+    uint32_t low_permille, high_permille; /* the ranks metered, in thousandths of the metered pixels: low < high <= 1000 */
+    float key;                            /* what the average luminance is exposed to: finite, > 0 */
+    float min_exposure, max_exposure;     /* the clamp of the target: finite, > 0, min <= max */
+    float blend;                          /* in [0, 1]: how far the exposure moves from previous_exposure towards the target */
+    float previous_exposure;              /* 0: none, the exposure is the target; otherwise finite and > 0 */
+    uint32_t flags;                       /* 0 */
+} rsrt_exposure_params;
+typedef struct rsrt_exposure_result {
+    float exposure, target;    /* what to display with; the clamped key / average_luminance */
+    float average_luminance;   /* the meter's reading (0: nothing metered) */
+    uint32_t metered, skipped; /* pixels in the 256 bins; pixels with !(luminance > 0) */
+    uint32_t _pad;
+} rsrt_exposure_result;
+/* Builds the histogram of `source` in a library-owned buffer (zeroed and filled by the enqueued work; asynchronous on hip_stream,
+ * NULL = the context's stream, ordered after everything enqueued so far).  sample_total is ignored for all sources but
+ * RSRT_EXPOSURE_MEAN.  RSRT_ERR_NOT_READY when the source image does not exist (no accumulator, no denoised or upsampled image, no
+ * temporal frame since the last reset); RSRT_ERR_INVALID_ARGUMENT for an unknown source, sample_total 0 under RSRT_EXPOSURE_MEAN. */
+rsrt_status rsrt_exposure_meter(rsrt_context *ctx, uint32_t source, uint32_t sample_total, void *hip_stream);
+/* Waits, copies the last histogram's 257 words to host_hist and fills *out from it (rsrt_exposure_from_histogram, on the host).
+ * host_hist may be NULL (n_words is then ignored), out may be NULL.  RSRT_ERR_NOT_READY without a histogram since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for NULL params, params rsrt_exposure_params_ok refuses, non-zero flags, n_words != 257 with a
+ * non-NULL host_hist. */
+rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params *params, uint32_t *host_hist, size_t n_words,
+                                   rsrt_exposure_result *out);
+rsrt_status rsrt_exposure_reset(rsrt_context *ctx); /* drops the histogram */
+/* `source` through the exposed display pass: rsrt_display_pixel_exposed per pixel (include/rsrt_exposure.h), RGBA8, alpha 255; with
+ * exposure 1 the bytes of rsrt_display_srgb8 / rsrt_denoised_display_srgb8 / rsrt_upsampled_display_srgb8.  Errors as for
+ * rsrt_exposure_meter, and RSRT_ERR_INVALID_ARGUMENT for an exposure that is not finite and > 0 or another n_bytes than 4 a pixel. */
+rsrt_status rsrt_display_exposed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, uint8_t *host_rgba8,
+                                       size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

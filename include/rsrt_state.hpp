@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rsrt.h"
+#include "rsrt_exposure.h"
 #include "rsrt_host.h"
 
 namespace rsrt {
@@ -261,13 +262,23 @@ public:
     void noise_reset() { check_ctx(rsrt_noise_reset(context(0))); }
     // renders until the largest tile error is at most `threshold` or max_samples are in: clears and renders min_samples, then per round
     // snapshots at n samples, renders up to min(2 n, max_samples) and estimates.  Returns the rounds; sample_count() is the total.  The
-    // accumulator is what render_samples(total) leaves from a clear, bit for bit.
+    // accumulator is what render_samples(total) leaves from a clear, bit for bit.  exposure: 0 compares the errors with `threshold`
+    // itself; E > 0, or kAutoExposure (metered once with blend 1 after the min_samples render, and remembered), compares them with
+    // threshold / sqrt(E) in f32: the threshold is then in displayed units.
+    static constexpr float kAutoExposure = -1.0f;
     std::vector<NoiseRound> render_to_noise(float threshold, uint32_t min_samples = 8, uint32_t max_samples = 1024, uint32_t tile_w = 16,
-                                            uint32_t tile_h = 16)
+                                            uint32_t tile_h = 16, float exposure = 0.0f)
     {
         if (min_samples < 1 || max_samples <= min_samples) throw Error("render_to_noise: 1 <= min_samples < max_samples");
         have_hash_ = false; // start from a clear, whatever was rendered before
         render_samples(min_samples);
+        if (exposure != 0.0f) {
+            if (exposure == kAutoExposure) {
+                exposure_ = 0.0f;
+                exposure = auto_exposure().exposure;
+            }
+            threshold = threshold / rsrt_sqrtf(exposure);
+        }
         std::vector<NoiseRound> rounds;
         for (;;) {
             const uint32_t n1 = sample_count_;
@@ -278,6 +289,51 @@ public:
             rounds.push_back(NoiseRound{n1, sample_count_, s.max_error, s.mean_error, s.tiles_above});
             if (s.max_error <= threshold || sample_count_ >= max_samples) return rounds;
         }
+    }
+    // -- auto-exposure (rsrt.h "auto-exposure"): one device, like the denoiser ---------------------------------------
+    static rsrt_exposure_params exposure_defaults()
+    {
+        return rsrt_exposure_params{RSRT_EXPOSURE_LOW_PERMILLE, RSRT_EXPOSURE_HIGH_PERMILLE, RSRT_EXPOSURE_KEY, RSRT_EXPOSURE_MIN, RSRT_EXPOSURE_MAX,
+                                    RSRT_EXPOSURE_BLEND, RSRT_EXPOSURE_PREVIOUS, 0u};
+    }
+    // the luminance histogram of `source` (RSRT_EXPOSURE_MEAN: the accumulator over sample_count() samples), built on the device
+    void exposure_meter(uint32_t source = RSRT_EXPOSURE_MEAN) { check_ctx(rsrt_exposure_meter(context(0), source, sample_count_, nullptr)); }
+    // the last exposure_meter(): its 257 words (256 bins, the skipped pixels) and, when given, the exposure of it under p
+    std::vector<uint32_t> exposure_download(const rsrt_exposure_params &p = exposure_defaults(), rsrt_exposure_result *result = nullptr)
+    {
+        std::vector<uint32_t> hist(RSRT_EXPOSURE_WORDS);
+        check_ctx(rsrt_exposure_download(context(0), &p, hist.data(), hist.size(), result));
+        return hist;
+    }
+    // meters `source`, downloads with the remembered exposure as previous_exposure and remembers the new one: the first call takes the
+    // target, later ones move a fraction `blend` of the way to it
+    rsrt_exposure_result auto_exposure(uint32_t source = RSRT_EXPOSURE_MEAN, float blend = 1.0f, rsrt_exposure_params p = exposure_defaults())
+    {
+        exposure_meter(source);
+        p.blend = blend;
+        p.previous_exposure = exposure_;
+        rsrt_exposure_result r;
+        exposure_download(p, &r);
+        exposure_ = r.exposure;
+        return r;
+    }
+    float exposure() const { return exposure_; } // the remembered exposure (0: none)
+    void exposure_reset() // forgets the remembered exposure and drops the histogram
+    {
+        exposure_ = 0.0f;
+        check_ctx(rsrt_exposure_reset(context(0)));
+    }
+    // `source` through the display pass at `exposure` (0: the remembered one); of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    std::vector<uint8_t> display_exposed(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f)
+    {
+        if (exposure == 0.0f) {
+            if (exposure_ == 0.0f) throw Error("display_exposed: no remembered exposure (auto_exposure first): RSRT_ERR_NOT_READY");
+            exposure = exposure_;
+        }
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
+        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        check_ctx(rsrt_display_exposed_srgb8(context(0), source, sample_count_, exposure, out.data(), out.size()));
+        return out;
     }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
@@ -382,6 +438,7 @@ private:
     bool have_temporal_key_ = false;
     size_t last_hash_ = 0;
     bool have_hash_ = false;
+    float exposure_ = 0.0f; // the last auto_exposure() (0: none since exposure_reset)
 };
 
 } // namespace rsrt

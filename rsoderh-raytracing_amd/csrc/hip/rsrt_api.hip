@@ -621,6 +621,12 @@ struct rsrt_context {
     uint32_t ns_tx = 0, ns_ty = 0;
     float ns_threshold = 0.0f;
     bool ns_have = false;
+    // auto-exposure (rt_exposure.h): two histograms (a call adds into the zero one and zeroes the other for the next call), which of
+    // them holds the last rsrt_exposure_meter's, whether there was one since the last reset, and whether a failed launch left them in an
+    // unknown state.  The library keeps no exposure.
+    uint32_t *ex_hist = nullptr;
+    uint32_t ex_cur = 0;
+    bool ex_have = false, ex_dirty = false;
 };
 
 namespace {
@@ -1224,6 +1230,7 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->up_out);
     (void)hipFree(ctx->ns_snap);
     (void)hipFree(ctx->ns_tiles);
+    (void)hipFree(ctx->ex_hist);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -2313,3 +2320,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_variance.h"
 #include "rt_upsample.h"
 #include "rt_noise.h"
+#include "rt_exposure.h"

@@ -1,0 +1,200 @@
+// rt_exposure.h — the auto-exposure meter's kernel, the exposed display kernel and their C-ABI (include/rsrt.h "auto-exposure";
+// DESIGN.md §15).  Included at the end of rsrt_api.hip.
+//
+//  rt_exposure_hist_kernel     a 256-thread workgroup walks trips of 2048 consecutive pixels of a float4 image (16 B a lane, coalesced;
+//                              the eight loads of a trip are issued before the first is used).  A pixel's word — its bin, or 256 for a
+//                              skipped pixel (include/rsrt_exposure.h) — is counted in the WAVE's own 257-word histogram in LDS with an
+//                              integer add whose result is not used.  A wave whose 64 pixels share a word (sky, a wall: the common
+//                              case, and 64 adds on one LDS address) finds that out with readfirstlane + ballot and lets lane 0 add
+//                              64.  After one __syncthreads the workgroup sums its four histograms and adds every non-zero word to
+//                              the histogram in global memory with one integer atomic; at most one workgroup a CU is launched,
+//                              because the time of that hand-on grows with the number of workgroups.  Integers only:
+//                              the result does not depend on the order of anything.  No scratch memory, 4112 B of LDS.
+//                              The context holds TWO histograms, each 2 KB aligned: a call adds into the one that is zero and its
+//                              workgroup 0 zeroes the other — the result of the call before, which the new call supersedes — for
+//                              the call after.  So a meter call is one launch, with no memset in front of it.
+//  rt_display_exposed_kernel   rt_display_kernel with rsrt_display_pixel_exposed.
+#include "../../../include/rsrt_exposure.h"
+
+#define RT_EX_BLOCK 256u
+#define RT_EX_WAVES (RT_EX_BLOCK / RT_WAVE)
+#define RT_EX_AHEAD 8u              // loads in flight a lane
+#define RT_EX_NONE 0xffffffffu      // a lane past the image's end
+#define RT_EX_STRIDE 512u           // words from one histogram to the other: each starts a 2 KB line of its own (a histogram that
+                                    // starts 4 B into a 128-byte line takes 4 us longer to add into)
+
+// hist: zero before the launch; next: zeroed here for the call after this one
+__global__ __launch_bounds__(RT_EX_BLOCK) void rt_exposure_hist_kernel(const float4 *img, size_t n, float total, uint32_t *hist, uint32_t *next)
+{
+    __shared__ uint32_t h[RT_EX_WAVES][RSRT_EXPOSURE_WORDS];
+    if (blockIdx.x == 0)
+        for (uint32_t w = threadIdx.x; w < RSRT_EXPOSURE_WORDS; w += RT_EX_BLOCK) next[w] = 0u;
+    const uint32_t lane = threadIdx.x & (RT_WAVE - 1u);
+    uint32_t *const mine = h[threadIdx.x / RT_WAVE];
+    for (uint32_t i = threadIdx.x; i < RT_EX_WAVES * RSRT_EXPOSURE_WORDS; i += RT_EX_BLOCK) (&h[0][0])[i] = 0u;
+    __syncthreads();
+    const size_t trip = (size_t)RT_EX_BLOCK * RT_EX_AHEAD;
+    for (size_t base = (size_t)blockIdx.x * trip; base < n; base += (size_t)gridDim.x * trip) { // (base is the workgroup's: no lane leaves early)
+        float4 c[RT_EX_AHEAD];
+        bool in[RT_EX_AHEAD];
+#pragma unroll
+        for (uint32_t k = 0; k < RT_EX_AHEAD; k++) {
+            const size_t p = base + (size_t)k * RT_EX_BLOCK + threadIdx.x;
+            in[k] = p < n;
+            if (in[k]) c[k] = img[p];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < RT_EX_AHEAD; k++) {
+            uint32_t word = RT_EX_NONE;
+            if (in[k]) {
+                const float sum[3] = {c[k].x, c[k].y, c[k].z};
+                word = rsrt_exposure_word(rsrt_exposure_luminance(sum, total));
+            }
+            const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)word);
+            if (__ballot(word == first) == ~0ull) { // all 64 lanes are here, and they agree
+                if (first != RT_EX_NONE && lane == 0u) atomicAdd(&mine[first], (uint32_t)RT_WAVE);
+            } else if (word != RT_EX_NONE) {
+                atomicAdd(&mine[word], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    for (uint32_t w = threadIdx.x; w < RSRT_EXPOSURE_WORDS; w += RT_EX_BLOCK) {
+        uint32_t s = 0u;
+#pragma unroll
+        for (uint32_t v = 0; v < RT_EX_WAVES; v++) s += h[v][w];
+        if (s) atomicAdd(&hist[w], s);
+    }
+}
+
+__global__ void rt_display_exposed_kernel(const float4 *img, size_t n, float total, float exposure, uchar4 *out)
+{
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = img[i];
+    const float sum[3] = {a.x, a.y, a.z};
+    unsigned char rgb[3];
+    rsrt_display_pixel_exposed(sum, total, exposure, rgb);
+    out[i] = make_uchar4(rgb[0], rgb[1], rgb[2], 255);
+}
+
+namespace {
+
+// where `source` lives, how many pixels it has and what its sums are divided by; `what` names the caller in the error text
+rsrt_status exposure_source(rsrt_context *ctx, const char *what, uint32_t source, uint32_t sample_total, const float4 **img, size_t *n, float *total)
+{
+    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: whole frame only (partition of %u ranks)", what, ctx->world);
+    *total = 1.0f;
+    switch (source) {
+    case RSRT_EXPOSURE_MEAN:
+        if (sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: sample_total must be > 0", what);
+        if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+        *img = ctx->accum;
+        *n = (size_t)ctx->acc_w * ctx->acc_h;
+        *total = (float)sample_total;
+        return RSRT_OK;
+    case RSRT_EXPOSURE_DENOISED:
+        if (!ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "no denoised image (rsrt_denoise first)");
+        *img = ctx->dn_last;
+        *n = (size_t)ctx->acc_w * ctx->acc_h;
+        return RSRT_OK;
+    case RSRT_EXPOSURE_TEMPORAL:
+        if (!ctx->tp_buf || !ctx->tp_frames) return fail(ctx, RSRT_ERR_NOT_READY, "no temporal frame since the last reset (rsrt_temporal_accumulate first)");
+        *img = temporal_history(ctx);
+        *n = (size_t)ctx->tp_w * ctx->tp_h;
+        return RSRT_OK;
+    case RSRT_EXPOSURE_UPSAMPLED:
+        if (!ctx->up_last) return fail(ctx, RSRT_ERR_NOT_READY, "no upsampled image (rsrt_upsample first)");
+        *img = ctx->up_last;
+        *n = (size_t)ctx->up_last_w * ctx->up_last_h;
+        return RSRT_OK;
+    default:
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+rsrt_status rsrt_exposure_meter(rsrt_context *ctx, uint32_t source, uint32_t sample_total, void *hip_stream)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const float4 *img = nullptr;
+    size_t n = 0;
+    float total = 1.0f;
+    { rsrt_status st0 = exposure_source(ctx, "exposure_meter", source, sample_total, &img, &n, &total); if (st0) return st0; }
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+    if (!ctx->ex_hist || ctx->ex_dirty) { // both histograms zero: once, and after a launch that failed
+        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+        if (!ctx->ex_hist) HIP_TRY(ctx, hipMalloc(&ctx->ex_hist, 2u * RT_EX_STRIDE * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMemset(ctx->ex_hist, 0, 2u * RT_EX_STRIDE * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipDeviceSynchronize()); // (the memset is enqueued on the null stream, which the kernel's stream does not wait for)
+        ctx->ex_cur = 0;
+        ctx->ex_dirty = ctx->ex_have = false;
+    }
+    rsrt_status st = begin_work(ctx, stream);
+    if (st) return st;
+    const size_t trip = (size_t)RT_EX_BLOCK * RT_EX_AHEAD, want = (n + trip - 1u) / trip;
+    uint32_t *const now = ctx->ex_hist + (ctx->ex_cur ^ 1u) * RT_EX_STRIDE, *const old = ctx->ex_hist + ctx->ex_cur * RT_EX_STRIDE;
+    ctx->ex_have = false; // (a failed launch leaves no histogram, and neither buffer known to be zero)
+    ctx->ex_dirty = true;
+    rt_exposure_hist_kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(RT_EX_BLOCK), 0, stream>>>(img, n, total, now, old);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->ex_cur ^= 1u;
+    ctx->ex_dirty = false;
+    ctx->ex_have = true;
+    return end_work(ctx, stream);
+}
+
+rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params *params, uint32_t *host_hist, size_t n_words, rsrt_exposure_result *out)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: whole frame only (partition of %u ranks)", ctx->world);
+    if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: params is NULL");
+    if (params->flags != 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: flags must be 0");
+    if (!rsrt_exposure_params_ok(params))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: want low_permille < high_permille <= 1000, key and 0 < min_exposure <= max_exposure finite and > 0, "
+                                                     "blend in [0, 1], previous_exposure 0 or finite and > 0");
+    if (host_hist && n_words != RSRT_EXPOSURE_WORDS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: expected %u words", RSRT_EXPOSURE_WORDS);
+    if (!ctx->ex_have) return fail(ctx, RSRT_ERR_NOT_READY, "no exposure histogram (rsrt_exposure_meter first)");
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    uint32_t own[RSRT_EXPOSURE_WORDS];
+    if (!host_hist) host_hist = own;
+    HIP_TRY(ctx, hipMemcpy(host_hist, ctx->ex_hist + ctx->ex_cur * RT_EX_STRIDE, RSRT_EXPOSURE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (out) rsrt_exposure_from_histogram(host_hist, params, out);
+    return RSRT_OK;
+}
+
+rsrt_status rsrt_exposure_reset(rsrt_context *ctx)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_reset: whole frame only (partition of %u ranks)", ctx->world);
+    ctx->ex_have = false;
+    return RSRT_OK;
+}
+
+rsrt_status rsrt_display_exposed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, uint8_t *host_rgba8, size_t n_bytes)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    const float4 *img = nullptr;
+    size_t n = 0;
+    float total = 1.0f;
+    { rsrt_status st0 = exposure_source(ctx, "display_exposed_srgb8", source, sample_total, &img, &n, &total); if (st0) return st0; }
+    if (!rsrt_exposure_finite_positive(exposure)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_exposed_srgb8: exposure must be finite and > 0");
+    if (!host_rgba8 || n_bytes != n * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_exposed_srgb8: expected %zu bytes", n * 4);
+    rsrt_status st = ensure_scratch(ctx, n * sizeof(uchar4));
+    if (st || (st = begin_work(ctx, ctx->stream))) return st;
+    uchar4 *tmp = static_cast<uchar4 *>(ctx->scratch);
+    rt_display_exposed_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(img, n, total, exposure, tmp);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(host_rgba8, tmp, n * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
+    if ((st = end_work(ctx, ctx->stream))) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RSRT_OK;
+}
+
+} // extern "C"

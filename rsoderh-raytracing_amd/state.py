@@ -34,7 +34,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_denoised_display_srgb8", "rsrt_temporal_accumulate", "rsrt_temporal_reset", "rsrt_temporal_download",
             "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download",
             "rsrt_guide_render", "rsrt_guide_bind", "rsrt_guide_clear", "rsrt_guide_download", "rsrt_upsample", "rsrt_upsampled_download",
-            "rsrt_upsampled_display_srgb8", "rsrt_noise_snapshot", "rsrt_noise_estimate", "rsrt_noise_download", "rsrt_noise_reset"]
+            "rsrt_upsampled_display_srgb8", "rsrt_noise_snapshot", "rsrt_noise_estimate", "rsrt_noise_download", "rsrt_noise_reset",
+            "rsrt_exposure_meter", "rsrt_exposure_download", "rsrt_exposure_reset", "rsrt_display_exposed_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -80,6 +81,24 @@ class NoiseParams(C.Structure):
 class NoiseSummary(C.Structure):
     _fields_ = [("max_error", C.c_float), ("mean_error", C.c_float), ("tiles_x", C.c_uint32), ("tiles_y", C.c_uint32),
                 ("tiles_above", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# rsrt_exposure_params defaults (include/rsrt.h "auto-exposure", include/rsrt_exposure.h) and the source names
+EXPOSURE_DEFAULTS = {"low_permille": 100, "high_permille": 950, "key": 0.18, "min_exposure": 2.0 ** -16, "max_exposure": 2.0 ** 16,
+                     "blend": 1.0, "previous_exposure": 0.0}
+EXPOSURE_SOURCES = {"mean": 0, "denoised": 1, "temporal": 2, "upsampled": 3}
+EXPOSURE_WORDS = 257
+NOT_READY = 4  # RSRT_ERR_NOT_READY
+
+
+class ExposureParams(C.Structure):
+    _fields_ = [("low_permille", C.c_uint32), ("high_permille", C.c_uint32), ("key", C.c_float), ("min_exposure", C.c_float),
+                ("max_exposure", C.c_float), ("blend", C.c_float), ("previous_exposure", C.c_float), ("flags", C.c_uint32)]
+
+
+class ExposureResult(C.Structure):
+    _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("average_luminance", C.c_float), ("metered", C.c_uint32),
+                ("skipped", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class TemporalParams(C.Structure):
@@ -199,6 +218,10 @@ def lib():
         L.rsrt_noise_estimate.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rsrt_noise_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsrt_noise_reset.argtypes = [C.c_void_p]
+        L.rsrt_exposure_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_exposure_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_exposure_reset.argtypes = [C.c_void_p]
+        L.rsrt_display_exposed_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -228,6 +251,7 @@ class State:
         self.guide_sample_count = 0     # samples in the upsampler's guide (render_guide / render_upsampled)
         self.guide_width = self.guide_height = 0  # the guide's size: what upsample() returns
         self._guide_bound = False
+        self.exposure = None            # the last auto_exposure() (None: none since exposure_reset)
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -523,15 +547,23 @@ class State:
         """Drops the snapshot and the last estimate (clear(), resize() and a bind of another size do so too)."""
         self._check(self._L.rsrt_noise_reset(self._ctx), "rsrt_noise_reset")
 
-    def render_to_noise(self, threshold, min_samples=8, max_samples=1024, tile=(16, 16), on_round=None):
+    def render_to_noise(self, threshold, min_samples=8, max_samples=1024, tile=(16, 16), on_round=None, exposure=None):
         """Renders until the largest tile error is at most `threshold` or max_samples are in: clears and renders min_samples, then per
         round snapshots at n samples, renders up to min(2 n, max_samples) and estimates.  Returns (total, rounds), rounds a list of
         (n1, n2, max_error, mean_error, tiles_above); on_round, when given, is called with each as it is known.  The accumulator is
-        what render_samples(total) leaves from a clear, bit for bit: the estimate only reads it."""
+        what render_samples(total) leaves from a clear, bit for bit: the estimate only reads it.  exposure: None compares the errors
+        with `threshold` itself; a float E, or "auto" (metered once with blend 1 after the min_samples render, and remembered),
+        compares them with threshold / sqrt(E) in f32 — the threshold is then in displayed units."""
         if not (min_samples >= 1 and max_samples > min_samples):
             raise ValueError("render_to_noise: 1 <= min_samples < max_samples")
         self._last_hash = None  # start from a clear, whatever was rendered before
         self.render_samples(min_samples)
+        if exposure is not None:
+            if exposure == "auto":
+                self.exposure = None
+                exposure = self.auto_exposure()["exposure"]
+            with np.errstate(all="ignore"):
+                threshold = float(np.float32(threshold) / np.sqrt(np.float32(exposure)))
         rounds = []
         while True:
             n1 = self.sample_count
@@ -543,6 +575,53 @@ class State:
                 on_round(rounds[-1])
             if s["max_error"] <= threshold or self.sample_count >= max_samples:
                 return self.sample_count, rounds
+
+    # -- auto-exposure (include/rsrt.h "auto-exposure") -----------------------------------------------
+    def exposure_meter(self, source="mean", sample_total=None, stream=None):
+        """rsrt_exposure_meter: builds the luminance histogram of `source` ("mean": the accumulator over sample_total, default
+        sample_count; "denoised", "temporal", "upsampled") on the device.  Asynchronous."""
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_exposure_meter(self._ctx, EXPOSURE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
+                    "rsrt_exposure_meter")
+
+    def exposure_download(self, **params):
+        """rsrt_exposure_download of the last exposure_meter(): (histogram, 257 uint32: 256 bins and the skipped pixels; result dict
+        with exposure, target, average_luminance, metered, skipped).  params: rsrt_exposure_params fields, EXPOSURE_DEFAULTS otherwise."""
+        q = dict(EXPOSURE_DEFAULTS, **params)
+        p = ExposureParams(q["low_permille"], q["high_permille"], q["key"], q["min_exposure"], q["max_exposure"], q["blend"],
+                           q["previous_exposure"], 0)
+        hist = np.zeros(EXPOSURE_WORDS, np.uint32)
+        r = ExposureResult()
+        self._check(self._L.rsrt_exposure_download(self._ctx, C.byref(p), _p(hist), hist.size, C.byref(r)), "rsrt_exposure_download")
+        return hist, {"exposure": r.exposure, "target": r.target, "average_luminance": r.average_luminance, "metered": r.metered,
+                      "skipped": r.skipped}
+
+    def auto_exposure(self, source="mean", blend=1.0, **params):
+        """Meters `source`, downloads with the remembered exposure as previous_exposure and remembers the new one (self.exposure):
+        the first call takes the target, later ones move a fraction `blend` of the way to it.  Returns the result dict."""
+        self.exposure_meter(source)
+        _, r = self.exposure_download(blend=blend, previous_exposure=self.exposure or 0.0, **params)
+        self.exposure = r["exposure"]
+        return r
+
+    def exposure_reset(self):
+        """Forgets the remembered exposure and drops the histogram."""
+        self.exposure = None
+        self._check(self._L.rsrt_exposure_reset(self._ctx), "rsrt_exposure_reset")
+
+    def display_exposed_srgb8(self, source="mean", exposure=None, sample_total=None):
+        """rsrt_display_exposed_srgb8: `source` through the display pass at `exposure` (None: the remembered one; RsrtError with
+        RSRT_ERR_NOT_READY if there is none): [H, W, 4] uint8, of the guide's size for "upsampled"."""
+        if exposure is None:
+            if self.exposure is None:
+                raise RsrtError("display_exposed_srgb8: no remembered exposure (auto_exposure first)", NOT_READY)
+            exposure = self.exposure
+        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
+        out = np.empty((self.guide_height, self.guide_width, 4) if up else (self.height, self.width, 4), np.uint8)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, exposure, _p(out), out.size),
+                    "rsrt_display_exposed_srgb8")
+        return out
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):

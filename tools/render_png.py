@@ -1,20 +1,25 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] — render through the product path and
-write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise estimate is at most X
-(State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the same samples and the
-default filter, the denoised display image instead."""
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] — render
+through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
+estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
+same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
+(State.auto_exposure), print the metered exposure and average luminance and write the exposed display image; exposure=X: that exposure.
+With noise=X the exposure also puts the threshold in displayed units (auto: metered after the first 8 samples)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rsoderh_raytracing_amd as R
 from rsoderh_raytracing_amd import host
 denoise = "--denoise" in sys.argv
-args = [a for a in sys.argv[1:] if a != "--denoise"]
+exposure = next((a[len("exposure="):] for a in sys.argv[1:] if a.startswith("exposure=")), None)
+if exposure is not None and exposure != "auto":
+    exposure = float(exposure)
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith("exposure=")]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
 if args[3].startswith("noise="):
     target = args[3][len("noise="):].split(",")
-    spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024,
+    spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024, exposure=exposure,
                                 on_round=lambda r: print("samples %4d -> %4d: max tile error %.4f, mean %.4f, %d tiles above" % r, flush=True))
     print("stopped at", spp, "samples")
     if denoise:
@@ -23,7 +28,14 @@ else:
     st.render_samples(int(args[3]), aov=denoise)
 if denoise:
     st.denoise(download=False)
-    host.write_png(out, st.denoised_display_srgb8())
+source = "denoised" if denoise else "mean"
+if exposure == "auto":
+    st.exposure_reset()  # meter the picture that is written, whatever render_to_noise metered on the way
+    r = st.auto_exposure(source)
+    print("metered exposure %.6g, average luminance %.6g (%d pixels metered, %d skipped)" % (r["exposure"], r["average_luminance"], r["metered"], r["skipped"]))
+    exposure = r["exposure"]
+if exposure is not None:
+    host.write_png(out, st.display_exposed_srgb8(source, exposure))
 else:
-    host.write_png(out, st.display_srgb8())
+    host.write_png(out, st.denoised_display_srgb8() if denoise else st.display_srgb8())
 g = st.stats(); print(name, 'kernel ms', g['kernel_ms'], 'rays', g['ext_rays'] + g['shadow_rays'])
