@@ -240,7 +240,10 @@ rsrt_status rsrt_multi_get_stats(rsrt_multi *m, rsrt_stats *out); /* counters su
  * Library-owned W*H RGBA32F sum on the device, (re)allocated and zeroed when the resolution
  * changes (State::resize).  rsrt_accumulator_bind lets the caller own it instead (a device
  * pointer of width*height*4 floats, e.g. a torch tensor that a RCCL reduce will read); pass NULL
- * to go back to the internal one. */
+ * to go back to the internal one (it was given up at the bind: the context then has no accumulator
+ * until the next resize or render).  Any change of the accumulator's size, to none included, drops
+ * what was derived from the old one: the denoised image, the temporal history and moments, the
+ * noise snapshot and estimate. */
 rsrt_status rsrt_accumulator_resize(rsrt_context *ctx, uint32_t width, uint32_t height);
 rsrt_status rsrt_accumulator_bind(rsrt_context *ctx, void *device_rgba32f, uint32_t width, uint32_t height);
 rsrt_status rsrt_accumulator_clear(rsrt_context *ctx);

@@ -487,6 +487,33 @@ static constexpr uint32_t kChunksPerWave = 32;      // work chunks a resident wa
 static constexpr uint32_t kDescendQuorum = 30;      // fixed-order / wide walk: a descending round ends once fewer than this percentage of its lanes are still descending
 static constexpr uint32_t kStopQuorum = 40;         // wide walk: a TRACE call ends (the unfinished rays park their stacks) once fewer than this percentage of its lanes are still walking
 
+// ------------------------------------------------------------------ image buffers (their helpers: "image buffers" below)
+// A pixel buffer the caller may bind memory of its own to: `p` is the one in use, `owned` the library's (none while a caller's is bound).
+struct PixelBuffer {
+    const char *name, *pointer_name; // in error texts: "bound AOV buffer is ...", "AOV pointer must be ..."
+    uint32_t f4;                     // float4 a pixel
+    float4 *p = nullptr, *owned = nullptr;
+    uint32_t w = 0, h = 0;
+    bool is(uint32_t W, uint32_t H) const { return p && w == W && h == H; }
+    size_t pixels() const { return (size_t)w * h; }
+    size_t bytes() const { return pixels() * f4 * sizeof(float4); }
+};
+// A library-owned allocation that follows a size.
+struct SizedAlloc {
+    void *p = nullptr;
+    uint32_t w = 0, h = 0;
+    bool is(uint32_t W, uint32_t H) const { return p && w == W && h == H; }
+    size_t pixels() const { return (size_t)w * h; }
+};
+// An image one of the passes can read: sums of `total` samples a pixel (1: a colour).
+struct ImageView {
+    const float4 *img = nullptr;
+    uint32_t w = 0, h = 0;
+    float total = 1.0f;
+    size_t pixels() const { return (size_t)w * h; }
+};
+enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
+
 struct rsrt_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -505,10 +532,8 @@ struct rsrt_context {
     std::vector<Env> envs;
     // partition
     uint32_t rank = 0, world = 1, tile_w = 16, tile_h = 16;
-    // accumulator
-    float4 *accum = nullptr;      // bound or owned
-    float4 *accum_owned = nullptr;
-    uint32_t acc_w = 0, acc_h = 0;
+    // accumulator (1 float4 a pixel).  A change of its size drops what was derived from it: accumulator_size_changed()
+    PixelBuffer acc{"accumulator", "accumulator", 1u};
     // work buffers
     // kLanes sets of work buffers ("lanes"), used in turn by successive passes: a pass's path-tracing kernel runs on its lane's own
     // stream and touches nothing but its lane's buffers, so the kernel of call k + 1 fills the CUs that call k's tail is leaving
@@ -584,38 +609,30 @@ struct rsrt_context {
     int hw_queues = 4;
     bool hw_queue_warned = false;
     unsigned long long debug_words[32] = {0};
-    // denoiser (rt_denoise.h): the AOV records (bound or owned, 2 float4 a pixel), the filter's scratch (freed when the accumulator's size
-    // changes) and where the last rsrt_denoise wrote
-    float4 *aov = nullptr;
-    float4 *aov_owned = nullptr;
-    uint32_t aov_w = 0, aov_h = 0;
-    void *dn_scratch = nullptr;
-    uint32_t dn_w = 0, dn_h = 0;
+    // The image-space passes' buffers (DESIGN.md §1 has the table: owner, size followed, what drops each).
+    // denoiser (rt_denoise.h): the AOV records (2 float4 a pixel, of the accumulator's size), the filter's scratch and where the last
+    // rsrt_denoise wrote
+    PixelBuffer aov{"AOV buffer", "AOV", 2u};
+    SizedAlloc dn_scratch;
     float4 *dn_last = nullptr;
-    // temporal pass (rt_temporal.h): two history and two feature buffers (float4 each, freed when the accumulator's size changes), which
-    // history holds the last frame, how many frames ran since the last reset (0: the next one is a first frame) and the last camera
-    float4 *tp_buf = nullptr;
-    uint32_t tp_w = 0, tp_h = 0, tp_cur = 0, tp_frames = 0;
+    // temporal pass (rt_temporal.h): two history and two feature buffers (float4 each), which history holds the last frame, how many frames
+    // ran since the last reset (0: the next one is a first frame) and the last camera
+    SizedAlloc tp_hist;
+    uint32_t tp_cur = 0, tp_frames = 0;
     float tp_cam[13] = {0}; // pos, rot (column-major 3x3), fov_y
-    // the luminance moments (RSRT_TEMPORAL_MOMENTS): two float4 record buffers (allocated on the first MOMENTS frame, freed with the
-    // history) and whether the last frame carried them
-    float4 *tp_mom = nullptr;
+    // the luminance moments (RSRT_TEMPORAL_MOMENTS): two float4 record buffers (allocated on the first MOMENTS frame) and whether the
+    // last frame carried them
+    SizedAlloc tp_mom;
     uint32_t tp_moments = 0;
-    // guided upsampling (rt_upsample.h): the guide records of the output size (bound or owned, 2 float4 a pixel; independent of the
-    // accumulator's size), the low pass's scratch (float4 + ushort4 a low pixel), the library-owned output and where the last rsrt_upsample wrote
-    float4 *guide = nullptr;
-    float4 *guide_owned = nullptr;
-    uint32_t guide_w = 0, guide_h = 0;
-    void *up_scratch = nullptr;
-    uint32_t up_w = 0, up_h = 0;
-    float4 *up_out = nullptr;
-    uint32_t up_out_w = 0, up_out_h = 0;
-    float4 *up_last = nullptr;
-    uint32_t up_last_w = 0, up_last_h = 0;
-    // noise estimate (rt_noise.h): the snapshot of the accumulator (freed when the accumulator's size changes), how many samples it holds
-    // (0: none), the tile map of the last rsrt_noise_estimate, its shape and threshold and whether there was one since the last reset
-    float4 *ns_snap = nullptr;
-    uint32_t ns_w = 0, ns_h = 0, ns_total = 0;
+    // guided upsampling (rt_upsample.h): the guide records of the output size (2 float4 a pixel; independent of the accumulator's size),
+    // the low pass's scratch (float4 + ushort4 a low pixel), the library-owned output and where the last rsrt_upsample wrote
+    PixelBuffer guide{"guide buffer", "guide", 2u};
+    SizedAlloc up_scratch, up_out;
+    ImageView up_last;
+    // noise estimate (rt_noise.h): the snapshot of the accumulator, how many samples it holds (0: none), the tile map of the last
+    // rsrt_noise_estimate (grow-only), its shape and threshold and whether there was one since the last reset
+    SizedAlloc ns_snap;
+    uint32_t ns_total = 0;
     float *ns_tiles = nullptr;
     size_t ns_tiles_cap = 0;
     uint32_t ns_tx = 0, ns_ty = 0;
@@ -837,65 +854,6 @@ void fill_wide_nodes(const std::vector<WideNode> &wide, const rsrt_bvh_node *nod
     }
 }
 
-void free_denoise_scratch(rsrt_context *ctx)
-{
-    (void)hipFree(ctx->dn_scratch);
-    ctx->dn_scratch = nullptr;
-    ctx->dn_w = ctx->dn_h = 0;
-    ctx->dn_last = nullptr;
-}
-
-void free_temporal(rsrt_context *ctx)
-{
-    (void)hipFree(ctx->tp_buf);
-    (void)hipFree(ctx->tp_mom);
-    ctx->tp_buf = nullptr;
-    ctx->tp_mom = nullptr;
-    ctx->tp_w = ctx->tp_h = ctx->tp_cur = ctx->tp_frames = ctx->tp_moments = 0;
-}
-
-// the snapshot and the last estimate mean nothing any more (a cleared accumulator, a reset); the buffers stay
-void drop_noise(rsrt_context *ctx)
-{
-    ctx->ns_total = 0;
-    ctx->ns_have = false;
-}
-
-void free_noise(rsrt_context *ctx)
-{
-    (void)hipFree(ctx->ns_snap);
-    (void)hipFree(ctx->ns_tiles);
-    ctx->ns_snap = nullptr;
-    ctx->ns_tiles = nullptr;
-    ctx->ns_tiles_cap = 0;
-    ctx->ns_w = ctx->ns_h = ctx->ns_tx = ctx->ns_ty = 0;
-    drop_noise(ctx);
-}
-
-// the temporal history of the last frame (valid when tp_frames > 0)
-float4 *temporal_history(rsrt_context *ctx) { return ctx->tp_buf + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
-// ... and its moment records (valid when tp_moments is set too)
-float4 *temporal_moments(rsrt_context *ctx) { return ctx->tp_mom + (size_t)ctx->tp_cur * ctx->tp_w * ctx->tp_h; }
-
-rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
-{
-    if (ctx->accum && ctx->acc_w == w && ctx->acc_h == h) return RSRT_OK;
-    if (ctx->accum && ctx->accum != ctx->accum_owned)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bound accumulator is %ux%u but %ux%u was requested", ctx->acc_w, ctx->acc_h, w, h);
-    if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; ctx->accum = nullptr; }
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    free_denoise_scratch(ctx);
-    free_temporal(ctx);
-    free_noise(ctx);
-    HIP_TRY(ctx, hipMalloc(&ctx->accum_owned, (size_t)w * h * sizeof(float4)));
-    HIP_TRY(ctx, hipMemset(ctx->accum_owned, 0, (size_t)w * h * sizeof(float4)));
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->accum = ctx->accum_owned;
-    ctx->acc_w = w;
-    ctx->acc_h = h;
-    return RSRT_OK;
-}
-
 // Orders `stream` after everything this context has enqueued so far (no-op on the same stream).
 rsrt_status begin_work(rsrt_context *ctx, hipStream_t stream)
 {
@@ -928,6 +886,203 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
     HIP_TRY(ctx, hipMalloc(&ctx->scratch, bytes));
     ctx->scratch_bytes = bytes;
     return RSRT_OK;
+}
+
+// ------------------------------------------------------------------ image buffers
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h) share on the host: the buffers a
+// caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
+// `what` is the calling entry point's name as its error texts spell it.
+
+hipStream_t stream_of(rsrt_context *ctx, void *hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream; }
+
+rsrt_status whole_frame(rsrt_context *ctx, const char *what)
+{
+    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: whole frame only (partition of %u ranks)", what, ctx->world);
+    return RSRT_OK;
+}
+
+void release(SizedAlloc &a)
+{
+    (void)hipFree(a.p);
+    a = SizedAlloc{};
+}
+// a.p: bytes_per_pixel for each of w x h pixels, not initialised.  A new allocation waits for everything in flight first.
+rsrt_status ensure_sized(rsrt_context *ctx, SizedAlloc &a, uint32_t w, uint32_t h, size_t bytes_per_pixel)
+{
+    if (a.is(w, h)) return RSRT_OK;
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    release(a);
+    HIP_TRY(ctx, hipMalloc(&a.p, (size_t)w * h * bytes_per_pixel));
+    a.w = w;
+    a.h = h;
+    return RSRT_OK;
+}
+
+// b is w x h: the bound buffer if it has that size, else the library's own, allocated zeroed
+rsrt_status buffer_ensure(rsrt_context *ctx, PixelBuffer &b, uint32_t w, uint32_t h)
+{
+    if (b.is(w, h)) return RSRT_OK;
+    if (b.p && b.p != b.owned) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bound %s is %ux%u but %ux%u was requested", b.name, b.w, b.h, w, h);
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    (void)hipFree(b.owned);
+    b.owned = b.p = nullptr;
+    b.w = b.h = 0;
+    const size_t bytes = (size_t)w * h * b.f4 * sizeof(float4);
+    HIP_TRY(ctx, hipMalloc(&b.owned, bytes));
+    // (on the context's stream, and finished before any pass can write the buffer: a plain hipMemset goes to the null stream, which the
+    // context's non-blocking streams are not ordered against, and could land on top of the first pass)
+    HIP_TRY(ctx, hipMemsetAsync(b.owned, 0, bytes, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    b.p = b.owned;
+    b.w = w;
+    b.h = h;
+    return RSRT_OK;
+}
+// The caller's memory instead of the library's, which is given up; NULL: back to the library's (there is none after a bind)
+rsrt_status buffer_bind(rsrt_context *ctx, PixelBuffer &b, void *device, uint32_t w, uint32_t h)
+{
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    if (!device) {
+        b.p = b.owned;
+        if (!b.p) b.w = b.h = 0;
+        return RSRT_OK;
+    }
+    if (w == 0 || h == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", w, h);
+    if ((uintptr_t)device % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s pointer must be 16-byte aligned", b.pointer_name);
+    (void)hipFree(b.owned);
+    b.owned = nullptr;
+    b.p = static_cast<float4 *>(device);
+    b.w = w;
+    b.h = h;
+    return RSRT_OK;
+}
+rsrt_status buffer_clear(rsrt_context *ctx, PixelBuffer &b)
+{
+    if (!b.p) return fail(ctx, RSRT_ERR_NOT_READY, "no %s", b.name);
+    rsrt_status st = begin_work(ctx, ctx->stream);
+    if (st) return st;
+    HIP_TRY(ctx, hipMemsetAsync(b.p, 0, b.bytes(), ctx->stream));
+    return end_work(ctx, ctx->stream);
+}
+
+// `want` floats at src -> host, after everything in flight
+rsrt_status download_floats(rsrt_context *ctx, const char *what, const void *src, size_t want, float *host, size_t n_floats)
+{
+    if (!host || n_floats != want) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu floats", what, want);
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    HIP_TRY(ctx, hipMemcpy(host, src, want * sizeof(float), hipMemcpyDeviceToHost));
+    return RSRT_OK;
+}
+rsrt_status buffer_download(rsrt_context *ctx, const char *what, const PixelBuffer &b, float *host, size_t n_floats)
+{
+    if (!b.p) return fail(ctx, RSRT_ERR_NOT_READY, "no %s", b.name);
+    return download_floats(ctx, what, b.p, b.pixels() * b.f4 * 4u, host, n_floats);
+}
+
+// A result computed into ctx->scratch and copied to the host: enqueue(scratch) launches the kernels on ctx->stream (scratch has
+// `bytes` + `extra` bytes; the first `bytes` of it are the result), and the call returns when `host` holds it.
+template <class Enqueue>
+rsrt_status read_back(rsrt_context *ctx, void *host, size_t bytes, size_t extra, Enqueue enqueue)
+{
+    rsrt_status st = ensure_scratch(ctx, bytes + extra);
+    if (st || (st = begin_work(ctx, ctx->stream)) || (st = enqueue(ctx->scratch))) return st;
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(host, ctx->scratch, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((st = end_work(ctx, ctx->stream))) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return RSRT_OK;
+}
+
+// the snapshot and the last estimate mean nothing any more (a cleared accumulator, a reset); the buffers stay
+void drop_noise(rsrt_context *ctx)
+{
+    ctx->ns_total = 0;
+    ctx->ns_have = false;
+}
+// The accumulator's size is another one now, or there is no accumulator any more: what was computed from the old size goes.  This is
+// the only place that knows the list, and every path that changes the size comes through here (after it has waited for the GPU).
+void accumulator_size_changed(rsrt_context *ctx)
+{
+    release(ctx->dn_scratch);
+    ctx->dn_last = nullptr;
+    release(ctx->tp_hist);
+    release(ctx->tp_mom);
+    ctx->tp_cur = ctx->tp_frames = ctx->tp_moments = 0;
+    release(ctx->ns_snap);
+    drop_noise(ctx);
+}
+rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
+{
+    if (ctx->acc.is(w, h)) return RSRT_OK;
+    if (ctx->acc.p == ctx->acc.owned) { // the library's own gives way to a new one (a bound one of another size is refused below)
+        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+        accumulator_size_changed(ctx);
+    }
+    return buffer_ensure(ctx, ctx->acc, w, h);
+}
+rsrt_status accumulator_and_aov(rsrt_context *ctx, const char *what, const PixelBuffer *also = nullptr)
+{
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    if (!ctx->aov.p) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no AOV buffer (rsrt_aov_render or rsrt_aov_bind first)", what);
+    if (also && !also->p) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no %s (rsrt_guide_render or rsrt_guide_bind first)", what, also->name); // (rsrt_upsample's guide)
+    if (ctx->aov.w != ctx->acc.w || ctx->aov.h != ctx->acc.h)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: AOV buffer is %ux%u, accumulator %ux%u", what, ctx->aov.w, ctx->aov.h, ctx->acc.w, ctx->acc.h);
+    return RSRT_OK;
+}
+
+// the temporal history of the last frame (valid when tp_frames > 0)
+float4 *temporal_history(rsrt_context *ctx) { return static_cast<float4 *>(ctx->tp_hist.p) + ctx->tp_cur * ctx->tp_hist.pixels(); }
+// ... and its moment records (valid when tp_moments is set too)
+float4 *temporal_moments(rsrt_context *ctx) { return static_cast<float4 *>(ctx->tp_mom.p) + ctx->tp_cur * ctx->tp_hist.pixels(); }
+
+// Which image `source` means, or why there is none: the one place with each source's readiness rule.  prefix: "" or the caller's
+// "name: " where its texts carry one.  acc_sized: the caller reads the image beside the accumulator, pixel for pixel.
+rsrt_status resolve_image(rsrt_context *ctx, const char *what, const char *prefix, uint32_t source, uint32_t sample_total, bool acc_sized, ImageView *v)
+{
+    switch (source) {
+    case IMAGE_MEAN:
+        if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+        *v = ImageView{ctx->acc.p, ctx->acc.w, ctx->acc.h, (float)sample_total};
+        return RSRT_OK;
+    case IMAGE_DENOISED:
+        if (!ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "%sno denoised image (rsrt_denoise first)", prefix);
+        *v = ImageView{ctx->dn_last, ctx->acc.w, ctx->acc.h, 1.0f};
+        return RSRT_OK;
+    case IMAGE_TEMPORAL:
+        if (!ctx->tp_hist.p || !ctx->tp_frames || (acc_sized && !ctx->tp_hist.is(ctx->acc.w, ctx->acc.h)))
+            return fail(ctx, RSRT_ERR_NOT_READY, "%sno temporal frame since the last reset (rsrt_temporal_accumulate first)", prefix);
+        *v = ImageView{temporal_history(ctx), ctx->tp_hist.w, ctx->tp_hist.h, 1.0f};
+        return RSRT_OK;
+    case IMAGE_UPSAMPLED:
+        if (!ctx->up_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno upsampled image (rsrt_upsample first)", prefix);
+        *v = ctx->up_last;
+        return RSRT_OK;
+    default:
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
+    }
+}
+rsrt_status image_download(rsrt_context *ctx, const char *what, uint32_t source, float *host, size_t n_floats)
+{
+    ImageView v;
+    rsrt_status st = resolve_image(ctx, what, "", source, 1u, false, &v);
+    return st ? st : download_floats(ctx, what, v.img, v.pixels() * 4u, host, n_floats);
+}
+// rsrt_display_srgb8 of any RGBA32F sum on ctx's device (sample_total is the kernel's integer, which v.total need not hold exactly)
+rsrt_status display_view(rsrt_context *ctx, const ImageView &v, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
+{
+    DeviceGuard g(ctx->device);
+    const size_t n = v.pixels();
+    if (!host_rgba8 || n_bytes != n * 4 || sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_srgb8: expected %zu bytes and sample_total > 0", n * 4);
+    return read_back(ctx, host_rgba8, n * sizeof(uchar4), 0, [&](void *tmp) {
+        hipLaunchKernelGGL(rt_display_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, v.img, n, sample_total, static_cast<uchar4 *>(tmp));
+        return RSRT_OK;
+    });
+}
+rsrt_status image_display(rsrt_context *ctx, const char *what, uint32_t source, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
+{
+    ImageView v;
+    rsrt_status st = resolve_image(ctx, what, "", source, sample_total, false, &v);
+    return st ? st : display_view(ctx, v, sample_total, host_rgba8, n_bytes);
 }
 
 hipEvent_t get_event(rsrt_context *ctx)
@@ -1095,7 +1250,7 @@ rsrt_status enqueue_pass(rsrt_context *ctx, RenderParams &P, const rsrt_context:
     HIP_TRY(ctx, hipEventRecord(lane.caller_at, caller_stream));
     HIP_TRY(ctx, hipStreamWaitEvent(stream, lane.caller_at, 0));
     if (ctx->last_valid && ctx->last_stream != stream) HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->last_event, 0));
-    hipLaunchKernelGGL(rt_resolve_kernel, dim3((P.n_slots + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, P, ctx->accum);
+    hipLaunchKernelGGL(rt_resolve_kernel, dim3((P.n_slots + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, P, ctx->acc.p);
     HIP_TRY(ctx, hipGetLastError());
     ctx->cum_launches++;
     HIP_TRY(ctx, hipEventRecord(pe.end, stream));
@@ -1118,28 +1273,6 @@ rsrt_status pack_environment(rsrt_context *ctx, Env &e)
     if ((st = end_work(ctx, ctx->stream))) return st;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return RSRT_OK;
-}
-
-// rsrt_display_srgb8 on any RGBA32F sum of n pixels that lives on ctx's device
-rsrt_status display_from_n(rsrt_context *ctx, const float4 *sum, size_t n, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
-{
-    DeviceGuard g(ctx->device);
-    if (!host_rgba8 || n_bytes != n * 4 || sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_srgb8: expected %zu bytes and sample_total > 0", n * 4);
-    rsrt_status st = ensure_scratch(ctx, n * sizeof(uchar4));
-    if (st || (st = begin_work(ctx, ctx->stream))) return st;
-    uchar4 *tmp = static_cast<uchar4 *>(ctx->scratch);
-    hipLaunchKernelGGL(rt_display_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, sum, n, sample_total, tmp);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(host_rgba8, tmp, n * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = end_work(ctx, ctx->stream))) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RSRT_OK;
-}
-
-// ... of the accumulator's size (the multi-GPU frame buffer uses it too)
-rsrt_status display_from(rsrt_context *ctx, const float4 *sum, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
-{
-    return display_from_n(ctx, sum, (size_t)ctx->acc_w * ctx->acc_h, sample_total, host_rgba8, n_bytes);
 }
 
 } // namespace
@@ -1176,7 +1309,7 @@ rsrt_status rsrt_context_create(int device_index, rsrt_context **out)
                    return r; }()) != hipSuccess ||
         (e = hipMalloc(&ctx->dev_stats, RT_STATS_WORDS * sizeof(unsigned long long))) != hipSuccess ||
         (e = hipMemsetAsync(ctx->dev_stats, 0, RT_STATS_WORDS * sizeof(unsigned long long), ctx->stream)) != hipSuccess || // (not the null stream:
-        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {                                                             // see ensure_aov)
+        (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) {                                                             // see buffer_ensure)
         fail(nullptr, RSRT_ERR_HIP, "context setup failed: %s", hipGetErrorString(e));
         delete ctx;
         return RSRT_ERR_HIP;
@@ -1220,15 +1353,10 @@ void rsrt_context_destroy(rsrt_context *ctx)
     for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
     (void)hipFree(ctx->scene_blob);
     for (auto &e : ctx->envs) { (void)hipFree(e.rgba); (void)hipFree(e.alias); }
-    (void)hipFree(ctx->accum_owned);
-    (void)hipFree(ctx->aov_owned);
-    (void)hipFree(ctx->dn_scratch);
-    (void)hipFree(ctx->tp_buf);
-    (void)hipFree(ctx->tp_mom);
-    (void)hipFree(ctx->guide_owned);
-    (void)hipFree(ctx->up_scratch);
-    (void)hipFree(ctx->up_out);
-    (void)hipFree(ctx->ns_snap);
+    accumulator_size_changed(ctx);
+    for (PixelBuffer *b : {&ctx->acc, &ctx->aov, &ctx->guide}) (void)hipFree(b->owned);
+    release(ctx->up_scratch);
+    release(ctx->up_out);
     (void)hipFree(ctx->ns_tiles);
     (void)hipFree(ctx->ex_hist);
     for (auto &L : ctx->lanes) {
@@ -1915,7 +2043,7 @@ rsrt_status rsrt_accumulator_resize(rsrt_context *ctx, uint32_t width, uint32_t 
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (width == 0 || height == 0 || (uint64_t)width * height > 0x7fffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
-    if (ctx->accum && ctx->accum != ctx->accum_owned) { ctx->accum = nullptr; ctx->acc_w = ctx->acc_h = 0; }
+    if (ctx->acc.p != ctx->acc.owned) { rsrt_status st0 = rsrt_accumulator_bind(ctx, nullptr, 0, 0); if (st0) return st0; } // a caller's is let go first
     return ensure_accumulator(ctx, width, height);
 }
 
@@ -1923,98 +2051,71 @@ rsrt_status rsrt_accumulator_bind(rsrt_context *ctx, void *device_rgba32f, uint3
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (!device_rgba32f) {
-        ctx->accum = ctx->accum_owned;
-        if (!ctx->accum) ctx->acc_w = ctx->acc_h = 0;
-        return RSRT_OK;
-    }
-    if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
-    if ((uintptr_t)device_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "accumulator pointer must be 16-byte aligned");
-    if (ctx->accum_owned) { (void)hipFree(ctx->accum_owned); ctx->accum_owned = nullptr; }
-    if (width != ctx->acc_w || height != ctx->acc_h) { free_denoise_scratch(ctx); free_temporal(ctx); free_noise(ctx); }
-    ctx->accum = static_cast<float4 *>(device_rgba32f);
-    ctx->acc_w = width;
-    ctx->acc_h = height;
-    return RSRT_OK;
+    const uint32_t w0 = ctx->acc.w, h0 = ctx->acc.h;
+    const rsrt_status st = buffer_bind(ctx, ctx->acc, device_rgba32f, width, height);
+    if (ctx->acc.w != w0 || ctx->acc.h != h0) accumulator_size_changed(ctx); // (to "none" too: NULL with no buffer of the library's to go back to)
+    return st;
 }
 
 rsrt_status rsrt_accumulator_clear(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    rsrt_status st = begin_work(ctx, ctx->stream);
-    if (st) return st;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->accum, 0, (size_t)ctx->acc_w * ctx->acc_h * sizeof(float4), ctx->stream));
-    drop_noise(ctx); // (a snapshot of what was cleared pairs with nothing)
-    return end_work(ctx, ctx->stream);
+    const rsrt_status st = buffer_clear(ctx, ctx->acc);
+    if (!st) drop_noise(ctx); // (a snapshot of what was cleared pairs with nothing)
+    return st;
 }
 
 rsrt_status rsrt_accumulator_download(rsrt_context *ctx, float *host_rgba, size_t n_floats)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    if (!host_rgba || n_floats != (size_t)ctx->acc_w * ctx->acc_h * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "download: expected %zu floats", (size_t)ctx->acc_w * ctx->acc_h * 4);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host_rgba, ctx->accum, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return buffer_download(ctx, "download", ctx->acc, host_rgba, n_floats);
 }
 
 rsrt_status rsrt_resolve_mean_f16(rsrt_context *ctx, uint32_t sample_total, uint16_t *host, size_t n_halfs)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    const size_t n = (size_t)ctx->acc_w * ctx->acc_h;
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    const size_t n = ctx->acc.pixels();
     if (!host || n_halfs != n * 4 || sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "resolve_mean_f16: expected %zu halfs and sample_total > 0", n * 4);
-    rsrt_status st = ensure_scratch(ctx, n * sizeof(ushort4));
-    if (st || (st = begin_work(ctx, ctx->stream))) return st;
-    ushort4 *tmp = static_cast<ushort4 *>(ctx->scratch);
-    hipLaunchKernelGGL(rt_mean_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->accum, n, 0.0f, sample_total, tmp);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(host, tmp, n * sizeof(ushort4), hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = end_work(ctx, ctx->stream))) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RSRT_OK;
+    return read_back(ctx, host, n * sizeof(ushort4), 0, [&](void *tmp) {
+        hipLaunchKernelGGL(rt_mean_f16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->acc.p, n, 0.0f, sample_total, static_cast<ushort4 *>(tmp));
+        return RSRT_OK;
+    });
 }
 
 rsrt_status rsrt_debug_view_f16(rsrt_context *ctx, uint32_t dev_index, uint32_t environment_index, uint32_t sample_count, uint16_t *host_inout, size_t n_halfs)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
     if (dev_index != 2u && dev_index != 3u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "debug_view: dev_index %u (2: draws of the alias table, 3: the HDRI)", dev_index);
     if (environment_index >= ctx->envs.size() || !ctx->envs[environment_index].rgba) return fail(ctx, RSRT_ERR_NOT_READY, "debug_view: environment slot %u is empty", environment_index);
     const Env &e = ctx->envs[environment_index];
-    const size_t n = (size_t)ctx->acc_w * ctx->acc_h;
+    const size_t n = ctx->acc.pixels();
     if (!host_inout || n_halfs != n * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "debug_view: expected %zu halfs", n * 4);
-    rsrt_status st = ensure_scratch(ctx, n * sizeof(ushort4) + n * sizeof(uint32_t));
-    if (st || (st = begin_work(ctx, ctx->stream))) return st;
-    ushort4 *tex = static_cast<ushort4 *>(ctx->scratch);
-    uint32_t *counts = reinterpret_cast<uint32_t *>(tex + n);
-    const unsigned nb = (unsigned)((n + 255) / 256);
-    if (dev_index == 3u) {
-        hipLaunchKernelGGL(rt_dev_view_hdri_kernel, dim3(nb), dim3(256), 0, ctx->stream, e.rgba, e.width, e.height, ctx->acc_w, ctx->acc_h, tex);
-    } else {
-        HIP_TRY(ctx, hipMemcpyAsync(tex, host_inout, n * sizeof(ushort4), hipMemcpyHostToDevice, ctx->stream)); // out_texture as the last frame left it
-        HIP_TRY(ctx, hipMemsetAsync(counts, 0, n * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(rt_dev_view_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, e.alias, e.width, e.height, ctx->acc_w, ctx->acc_h, sample_count, counts);
-        hipLaunchKernelGGL(rt_dev_view_apply_kernel, dim3(nb), dim3(256), 0, ctx->stream, counts, n, tex);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(host_inout, tex, n * sizeof(ushort4), hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = end_work(ctx, ctx->stream))) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RSRT_OK;
+    return read_back(ctx, host_inout, n * sizeof(ushort4), n * sizeof(uint32_t), [&](void *scratch) {
+        ushort4 *tex = static_cast<ushort4 *>(scratch);
+        uint32_t *counts = reinterpret_cast<uint32_t *>(tex + n);
+        const unsigned nb = (unsigned)((n + 255) / 256);
+        if (dev_index == 3u) {
+            hipLaunchKernelGGL(rt_dev_view_hdri_kernel, dim3(nb), dim3(256), 0, ctx->stream, e.rgba, e.width, e.height, ctx->acc.w, ctx->acc.h, tex);
+        } else {
+            HIP_TRY(ctx, hipMemcpyAsync(tex, host_inout, n * sizeof(ushort4), hipMemcpyHostToDevice, ctx->stream)); // out_texture as the last frame left it
+            HIP_TRY(ctx, hipMemsetAsync(counts, 0, n * sizeof(uint32_t), ctx->stream));
+            hipLaunchKernelGGL(rt_dev_view_count_kernel, dim3(nb), dim3(256), 0, ctx->stream, e.alias, e.width, e.height, ctx->acc.w, ctx->acc.h, sample_count, counts);
+            hipLaunchKernelGGL(rt_dev_view_apply_kernel, dim3(nb), dim3(256), 0, ctx->stream, counts, n, tex);
+        }
+        return RSRT_OK;
+    });
 }
 
 rsrt_status rsrt_display_srgb8(rsrt_context *ctx, uint32_t sample_total, uint8_t *host_rgba8, size_t n_bytes)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    return display_from(ctx, ctx->accum, sample_total, host_rgba8, n_bytes);
+    return image_display(ctx, "display_srgb8", IMAGE_MEAN, sample_total, host_rgba8, n_bytes);
 }
 
 rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin,

@@ -93,7 +93,7 @@ struct TileGeom {
 TileGeom tile_geom(const rsrt_context *ctx)
 {
     TileGeom g;
-    g.width = ctx->acc_w; g.height = ctx->acc_h; g.tile_w = ctx->tile_w; g.tile_h = ctx->tile_h; g.world = ctx->world;
+    g.width = ctx->acc.w; g.height = ctx->acc.h; g.tile_w = ctx->tile_w; g.tile_h = ctx->tile_h; g.world = ctx->world;
     g.tiles_x = (g.width + g.tile_w - 1) / g.tile_w;
     g.tiles_y = (g.height + g.tile_h - 1) / g.tile_h;
     g.per_row = (g.tiles_x + g.world - 1) / g.world;
@@ -163,13 +163,13 @@ bool comm_dense(const rsrt_context *ctx) { return ctx->comm_dense_mode; }
 rsrt_status exchange_begin(rsrt_context *ctx, uint32_t root, void *recv_device_rgba32f, hipStream_t stream, ExchangeInFlight &x)
 {
     DeviceGuard g(ctx->device);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
     if (root >= ctx->comm_world) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "comm_reduce: root %u not in [0,%u)", root, ctx->comm_world);
     if (ctx->comm && (ctx->comm_world != ctx->world || ctx->comm_rank != ctx->rank))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "comm_reduce: the partition (rank %u of %u) is not the communicator's (%u of %u)", ctx->rank, ctx->world, ctx->comm_rank, ctx->comm_world);
     x.stream = stream;
     x.root = ctx->comm_rank == root;
-    x.recv = (x.root && recv_device_rgba32f) ? static_cast<float4 *>(recv_device_rgba32f) : ctx->accum;
+    x.recv = (x.root && recv_device_rgba32f) ? static_cast<float4 *>(recv_device_rgba32f) : ctx->acc.p;
     x.dense = comm_dense(ctx);
     const TileGeom tg = tile_geom(ctx);
     const size_t seg = (size_t)tg.n_slots * sizeof(float4);
@@ -180,18 +180,18 @@ rsrt_status exchange_begin(rsrt_context *ctx, uint32_t root, void *recv_device_r
     x.begun = true;
     HIP_TRY(ctx, hipEventRecord(x.e0, stream));
     if (!ctx->comm || ctx->comm_world == 1) { // a world of one: the frame is the accumulator
-        if (x.recv != ctx->accum) HIP_TRY(ctx, hipMemcpyAsync(x.recv, ctx->accum, (size_t)ctx->acc_w * ctx->acc_h * sizeof(float4), hipMemcpyDeviceToDevice, stream));
+        if (x.recv != ctx->acc.p) HIP_TRY(ctx, hipMemcpyAsync(x.recv, ctx->acc.p, (size_t)ctx->acc.w * ctx->acc.h * sizeof(float4), hipMemcpyDeviceToDevice, stream));
         return RSRT_OK;
     }
     ncclComm_t comm = static_cast<ncclComm_t>(ctx->comm);
     if (x.dense) {
-        RCCL_TRY(ctx, rccl().Reduce(ctx->accum, x.recv, (size_t)ctx->acc_w * ctx->acc_h * 4, ncclFloat, ncclSum, (int)root, comm, stream));
+        RCCL_TRY(ctx, rccl().Reduce(ctx->acc.p, x.recv, (size_t)ctx->acc.w * ctx->acc.h * 4, ncclFloat, ncclSum, (int)root, comm, stream));
         return RSRT_OK;
     }
     // gather of the compact buffers: each pixel has ONE owner, so "sum of the accumulators" is "every rank's own tiles, side
     // by side" — 1 / world of the bytes of a dense reduce, point to point over xGMI, and no addition at all
     float4 *mine = static_cast<float4 *>(ctx->comm_buf) + (x.root ? (size_t)ctx->comm_rank * tg.n_slots : 0);
-    hipLaunchKernelGGL(rt_pack_tiles_kernel, dim3((tg.n_slots + 255) / 256), dim3(256), 0, stream, tg, ctx->comm_rank, ctx->accum, mine);
+    hipLaunchKernelGGL(rt_pack_tiles_kernel, dim3((tg.n_slots + 255) / 256), dim3(256), 0, stream, tg, ctx->comm_rank, ctx->acc.p, mine);
     HIP_TRY(ctx, hipGetLastError());
     if (x.root) {
         for (uint32_t r = 0; r < ctx->comm_world; r++)
@@ -394,12 +394,12 @@ rsrt_status for_each_ctx(rsrt_multi *m, const char *what, F f)
 rsrt_status multi_ensure_frame(rsrt_multi *m)
 {
     rsrt_context *c0 = m->ctx[0];
-    if (m->frame && m->frame_w == c0->acc_w && m->frame_h == c0->acc_h) return RSRT_OK;
+    if (m->frame && m->frame_w == c0->acc.w && m->frame_h == c0->acc.h) return RSRT_OK;
     DeviceGuard g(c0->device);
     if (m->frame) { (void)hipDeviceSynchronize(); (void)hipFree(m->frame); m->frame = nullptr; }
-    if (hipMalloc(&m->frame, (size_t)c0->acc_w * c0->acc_h * sizeof(float4)) != hipSuccess) return mfail(m, RSRT_ERR_OUT_OF_MEMORY, "multi frame buffer", "hipMalloc failed");
-    m->frame_w = c0->acc_w;
-    m->frame_h = c0->acc_h;
+    if (hipMalloc(&m->frame, (size_t)c0->acc.w * c0->acc.h * sizeof(float4)) != hipSuccess) return mfail(m, RSRT_ERR_OUT_OF_MEMORY, "multi frame buffer", "hipMalloc failed");
+    m->frame_w = c0->acc.w;
+    m->frame_h = c0->acc.h;
     return RSRT_OK;
 }
 
@@ -413,7 +413,7 @@ rsrt_status multi_reduce(rsrt_multi *m)
     if (n_dev == 1) { // one device: the frame is its accumulator (no communicator exists, none is needed)
         DeviceGuard g(c0->device);
         if ((st = begin_work(c0, c0->stream))) return mfail(m, st, "multi reduce", rsrt_last_error(c0));
-        const hipError_t e = hipMemcpyAsync(m->frame, c0->accum, (size_t)c0->acc_w * c0->acc_h * sizeof(float4), hipMemcpyDeviceToDevice, c0->stream);
+        const hipError_t e = hipMemcpyAsync(m->frame, c0->acc.p, (size_t)c0->acc.w * c0->acc.h * sizeof(float4), hipMemcpyDeviceToDevice, c0->stream);
         st = end_work(c0, c0->stream);
         if (e != hipSuccess) return mfail(m, RSRT_ERR_HIP, "multi reduce", hipGetErrorString(e));
         return st ? mfail(m, st, "multi reduce", rsrt_last_error(c0)) : RSRT_OK;
@@ -431,7 +431,7 @@ rsrt_status multi_reduce(rsrt_multi *m)
                 mine = static_cast<float4 *>(ci->comm_buf);
             }
             if ((st = begin_work(ci, ci->stream))) return mfail(m, st, "multi reduce", rsrt_last_error(ci));
-            hipLaunchKernelGGL(rt_pack_tiles_kernel, dim3((tg.n_slots + 255) / 256), dim3(256), 0, ci->stream, tg, (uint32_t)i, ci->accum, mine);
+            hipLaunchKernelGGL(rt_pack_tiles_kernel, dim3((tg.n_slots + 255) / 256), dim3(256), 0, ci->stream, tg, (uint32_t)i, ci->acc.p, mine);
             const hipError_t e = hipGetLastError();
             st = end_work(ci, ci->stream);
             if (e != hipSuccess) return mfail(m, RSRT_ERR_HIP, "multi reduce (pack)", hipGetErrorString(e));
@@ -589,8 +589,8 @@ rsrt_status rsrt_multi_download(rsrt_multi *m, float *host_rgba, size_t n_floats
 {
     if (!m || m->ctx.empty()) return RSRT_ERR_INVALID_ARGUMENT;
     rsrt_context *c0 = m->ctx[0];
-    if (!c0->accum) return mfail(m, RSRT_ERR_NOT_READY, "multi download", "no accumulator");
-    if (!host_rgba || n_floats != (size_t)c0->acc_w * c0->acc_h * 4) return mfail(m, RSRT_ERR_INVALID_ARGUMENT, "multi download", "wrong float count");
+    if (!c0->acc.p) return mfail(m, RSRT_ERR_NOT_READY, "multi download", "no accumulator");
+    if (!host_rgba || n_floats != (size_t)c0->acc.w * c0->acc.h * 4) return mfail(m, RSRT_ERR_INVALID_ARGUMENT, "multi download", "wrong float count");
     rsrt_status st = multi_reduce(m);
     if (st) return st;
     if ((st = rsrt_multi_synchronize(m))) return st;
@@ -606,7 +606,7 @@ rsrt_status rsrt_multi_display_srgb8(rsrt_multi *m, uint32_t sample_total, uint8
     rsrt_status st = multi_reduce(m);
     if (st) return st;
     rsrt_context *c0 = m->ctx[0];
-    st = display_from(c0, m->frame, sample_total, host_rgba8, n_bytes);
+    st = display_view(c0, ImageView{m->frame, c0->acc.w, c0->acc.h, (float)sample_total}, sample_total, host_rgba8, n_bytes);
     return st ? mfail(m, st, "multi display", rsrt_last_error(c0)) : RSRT_OK;
 }
 

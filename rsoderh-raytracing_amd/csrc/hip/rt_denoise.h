@@ -136,39 +136,6 @@ __global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_dn_level_kernel(const 
 
 namespace {
 
-// the AOV buffer follows the accumulator's size (a bound one must match it)
-rsrt_status ensure_aov(rsrt_context *ctx)
-{
-    if (ctx->aov && ctx->aov_w == ctx->acc_w && ctx->aov_h == ctx->acc_h) return RSRT_OK;
-    if (ctx->aov && ctx->aov != ctx->aov_owned)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bound AOV buffer is %ux%u but the accumulator is %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (ctx->aov_owned) { (void)hipFree(ctx->aov_owned); ctx->aov_owned = nullptr; ctx->aov = nullptr; ctx->aov_w = ctx->aov_h = 0; }
-    const size_t bytes = (size_t)ctx->acc_w * ctx->acc_h * 2u * sizeof(float4);
-    HIP_TRY(ctx, hipMalloc(&ctx->aov_owned, bytes));
-    // (on the context's stream, and finished before any pass can write the buffer: a plain hipMemset goes to the null stream, which the
-    // context's non-blocking streams are not ordered against, and could land on top of the first AOV pass)
-    HIP_TRY(ctx, hipMemsetAsync(ctx->aov_owned, 0, bytes, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->aov = ctx->aov_owned;
-    ctx->aov_w = ctx->acc_w;
-    ctx->aov_h = ctx->acc_h;
-    return RSRT_OK;
-}
-
-// ping, pong, the library-owned output (float4 each) and the packed features (ushort4), for the accumulator's size
-rsrt_status ensure_denoise_scratch(rsrt_context *ctx)
-{
-    if (ctx->dn_scratch && ctx->dn_w == ctx->acc_w && ctx->dn_h == ctx->acc_h) return RSRT_OK;
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    free_denoise_scratch(ctx);
-    const size_t n = (size_t)ctx->acc_w * ctx->acc_h;
-    HIP_TRY(ctx, hipMalloc(&ctx->dn_scratch, n * (3u * sizeof(float4) + sizeof(ushort4))));
-    ctx->dn_w = ctx->acc_w;
-    ctx->dn_h = ctx->acc_h;
-    return RSRT_OK;
-}
-
 // the AOV pass of samples [sample_begin, sample_begin + sample_count) into `aov`, a width x height record buffer (the AOV buffer, or the
 // upsampler's guide: rt_upsample.h)
 rsrt_status launch_aov(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin, uint32_t sample_count,
@@ -213,55 +180,34 @@ rsrt_status rsrt_aov_render(rsrt_context *ctx, const rsrt_camera *camera, uint32
     if (!camera) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "camera is NULL");
     if (!ctx->scene_ready) return fail(ctx, RSRT_ERR_NOT_READY, "no scene uploaded");
     if (flags != 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "aov_render: flags must be 0");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "aov_render: whole frame only (partition of %u ranks)", ctx->world);
+    rsrt_status st = whole_frame(ctx, "aov_render");
+    if (st) return st;
     if (width == 0 || height == 0 || (uint64_t)width * height > 0x7fffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
     if ((uint64_t)sample_begin + sample_count > 0xffffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "sample range overflows u32");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    rsrt_status st = ensure_accumulator(ctx, width, height);
-    if (st || (st = ensure_aov(ctx))) return st;
+    if ((st = ensure_accumulator(ctx, width, height)) || (st = buffer_ensure(ctx, ctx->aov, width, height))) return st; // (the AOV buffer follows the accumulator)
     if (sample_count == 0) return RSRT_OK;
-    return launch_aov(ctx, camera, width, height, sample_begin, sample_count, ctx->aov, stream);
+    return launch_aov(ctx, camera, width, height, sample_begin, sample_count, ctx->aov.p, stream_of(ctx, hip_stream));
 }
 
 rsrt_status rsrt_aov_bind(rsrt_context *ctx, void *device_f32x8, uint32_t width, uint32_t height)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (!device_f32x8) {
-        ctx->aov = ctx->aov_owned;
-        if (!ctx->aov) ctx->aov_w = ctx->aov_h = 0;
-        return RSRT_OK;
-    }
-    if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
-    if ((uintptr_t)device_f32x8 % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "AOV pointer must be 16-byte aligned");
-    if (ctx->aov_owned) { (void)hipFree(ctx->aov_owned); ctx->aov_owned = nullptr; }
-    ctx->aov = static_cast<float4 *>(device_f32x8);
-    ctx->aov_w = width;
-    ctx->aov_h = height;
-    return RSRT_OK;
+    return buffer_bind(ctx, ctx->aov, device_f32x8, width, height);
 }
 
 rsrt_status rsrt_aov_clear(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "no AOV buffer");
-    rsrt_status st = begin_work(ctx, ctx->stream);
-    if (st) return st;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->aov, 0, (size_t)ctx->aov_w * ctx->aov_h * 2u * sizeof(float4), ctx->stream));
-    return end_work(ctx, ctx->stream);
+    return buffer_clear(ctx, ctx->aov);
 }
 
 rsrt_status rsrt_aov_download(rsrt_context *ctx, float *host, size_t n_floats)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "no AOV buffer");
-    if (!host || n_floats != (size_t)ctx->aov_w * ctx->aov_h * 8u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "aov_download: expected %zu floats", (size_t)ctx->aov_w * ctx->aov_h * 8u);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, ctx->aov, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return buffer_download(ctx, "aov_download", ctx->aov, host, n_floats);
 }
 
 rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_sample_total, const rsrt_denoise_params *params,
@@ -270,11 +216,8 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: params is NULL");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: whole frame only (partition of %u ranks)", ctx->world);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "denoise: no AOV buffer (rsrt_aov_render or rsrt_aov_bind first)");
-    if (ctx->aov_w != ctx->acc_w || ctx->aov_h != ctx->acc_h)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
+    rsrt_status st = whole_frame(ctx, "denoise");
+    if (st || (st = accumulator_and_aov(ctx, "denoise"))) return st;
     const rsrt_denoise_params &p = *params;
     if (p.iterations > 8u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: iterations %u (at most 8)", p.iterations);
     if (p.flags & ~(uint32_t)(RSRT_DENOISE_DEMODULATE | RSRT_DENOISE_TEMPORAL | RSRT_DENOISE_VARIANCE | RSRT_DENOISE_CLAMP))
@@ -287,22 +230,22 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: sigmas must lie in [1e-6, 1e6]");
     if (sample_total == 0 || aov_sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: sample_total and aov_sample_total must be > 0");
     if ((uintptr_t)device_out_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoise: output pointer must be 16-byte aligned");
-    if (temporal && (!ctx->tp_frames || ctx->tp_w != ctx->acc_w || ctx->tp_h != ctx->acc_h))
-        return fail(ctx, RSRT_ERR_NOT_READY, "denoise: no temporal frame since the last reset (rsrt_temporal_accumulate first)");
+    ImageView colour;
+    if ((st = resolve_image(ctx, "denoise", "denoise: ", temporal ? IMAGE_TEMPORAL : IMAGE_MEAN, sample_total, true, &colour))) return st;
     if (temporal && (p.flags & RSRT_DENOISE_VARIANCE) && !ctx->tp_moments)
         return fail(ctx, RSRT_ERR_NOT_READY, "denoise: the last temporal frame carried no moments (RSRT_TEMPORAL_MOMENTS)");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    rsrt_status st = ensure_denoise_scratch(ctx);
-    if (st || (st = begin_work(ctx, stream))) return st;
-    const uint32_t w = ctx->acc_w, h = ctx->acc_h;
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    const uint32_t w = ctx->acc.w, h = ctx->acc.h;
     const size_t n = (size_t)w * h;
-    float4 *ping = static_cast<float4 *>(ctx->dn_scratch), *pong = ping + n, *own = pong + n;
+    // ping, pong, the library-owned output (float4 each) and the packed features (ushort4)
+    if ((st = ensure_sized(ctx, ctx->dn_scratch, w, h, 3u * sizeof(float4) + sizeof(ushort4))) || (st = begin_work(ctx, stream))) return st;
+    float4 *ping = static_cast<float4 *>(ctx->dn_scratch.p), *pong = ping + n, *own = pong + n;
     ushort4 *feat = reinterpret_cast<ushort4 *>(own + n);
     float4 *out = device_out_rgba32f ? static_cast<float4 *>(device_out_rgba32f) : own;
-    const float st_f = (float)sample_total, at_f = (float)aov_sample_total;
+    const float at_f = (float)aov_sample_total;
     const int demod = (p.flags & RSRT_DENOISE_DEMODULATE) ? 1 : 0;
     const uint32_t L = p.iterations;
-    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(temporal ? temporal_history(ctx) : ctx->accum, ctx->aov, n, st_f, at_f, demod, L == 0, L == 0 ? out : ping, feat);
+    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(colour.img, ctx->aov.p, n, colour.total, at_f, demod, L == 0, L == 0 ? out : ping, feat);
     const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
     if (L > 0 && (p.flags & (RSRT_DENOISE_VARIANCE | RSRT_DENOISE_CLAMP))) {
         sv_filter(ctx, stream, p, temporal, ping, pong, feat, out, w, h, at_f);
@@ -310,9 +253,9 @@ rsrt_status rsrt_denoise(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_
         for (uint32_t i = 0; i < L; i++) {
             const float4 *src = (i % 2u == 0u) ? ping : pong;
             if (i + 1u == L)
-                rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov, out, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, at_f, demod);
+                rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, out, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, at_f, demod);
             else
-                rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov, (i % 2u == 0u) ? pong : ping, w, h, i, p.sigma_color,
+                rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, (i % 2u == 0u) ? pong : ping, w, h, i, p.sigma_color,
                                                                       p.sigma_normal, p.sigma_depth, at_f, demod);
         }
     }
@@ -325,18 +268,13 @@ rsrt_status rsrt_denoised_download(rsrt_context *ctx, float *host, size_t n_floa
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "no denoised image (rsrt_denoise first)");
-    if (!host || n_floats != (size_t)ctx->acc_w * ctx->acc_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "denoised_download: expected %zu floats", (size_t)ctx->acc_w * ctx->acc_h * 4u);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, ctx->dn_last, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return image_download(ctx, "denoised_download", IMAGE_DENOISED, host, n_floats);
 }
 
 rsrt_status rsrt_denoised_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    if (!ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "no denoised image (rsrt_denoise first)");
-    return display_from(ctx, ctx->dn_last, 1u, host_rgba8, n_bytes);
+    return image_display(ctx, "denoised_display_srgb8", IMAGE_DENOISED, 1u, host_rgba8, n_bytes);
 }
 
 } // extern "C"

@@ -80,37 +80,13 @@ __global__ void rt_display_exposed_kernel(const float4 *img, size_t n, float tot
 
 namespace {
 
-// where `source` lives, how many pixels it has and what its sums are divided by; `what` names the caller in the error text
-rsrt_status exposure_source(rsrt_context *ctx, const char *what, uint32_t source, uint32_t sample_total, const float4 **img, size_t *n, float *total)
+// the image a metering or an exposed display means; `what` names the caller in the error texts
+rsrt_status exposure_source(rsrt_context *ctx, const char *what, uint32_t source, uint32_t sample_total, ImageView *v)
 {
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: whole frame only (partition of %u ranks)", what, ctx->world);
-    *total = 1.0f;
-    switch (source) {
-    case RSRT_EXPOSURE_MEAN:
-        if (sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: sample_total must be > 0", what);
-        if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-        *img = ctx->accum;
-        *n = (size_t)ctx->acc_w * ctx->acc_h;
-        *total = (float)sample_total;
-        return RSRT_OK;
-    case RSRT_EXPOSURE_DENOISED:
-        if (!ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "no denoised image (rsrt_denoise first)");
-        *img = ctx->dn_last;
-        *n = (size_t)ctx->acc_w * ctx->acc_h;
-        return RSRT_OK;
-    case RSRT_EXPOSURE_TEMPORAL:
-        if (!ctx->tp_buf || !ctx->tp_frames) return fail(ctx, RSRT_ERR_NOT_READY, "no temporal frame since the last reset (rsrt_temporal_accumulate first)");
-        *img = temporal_history(ctx);
-        *n = (size_t)ctx->tp_w * ctx->tp_h;
-        return RSRT_OK;
-    case RSRT_EXPOSURE_UPSAMPLED:
-        if (!ctx->up_last) return fail(ctx, RSRT_ERR_NOT_READY, "no upsampled image (rsrt_upsample first)");
-        *img = ctx->up_last;
-        *n = (size_t)ctx->up_last_w * ctx->up_last_h;
-        return RSRT_OK;
-    default:
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
-    }
+    const rsrt_status st = whole_frame(ctx, what);
+    if (st) return st;
+    if (source == IMAGE_MEAN && sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: sample_total must be > 0", what);
+    return resolve_image(ctx, what, "", source, sample_total, false, v);
 }
 
 } // namespace
@@ -121,11 +97,11 @@ rsrt_status rsrt_exposure_meter(rsrt_context *ctx, uint32_t source, uint32_t sam
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    const float4 *img = nullptr;
-    size_t n = 0;
-    float total = 1.0f;
-    { rsrt_status st0 = exposure_source(ctx, "exposure_meter", source, sample_total, &img, &n, &total); if (st0) return st0; }
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
+    ImageView v;
+    rsrt_status st = exposure_source(ctx, "exposure_meter", source, sample_total, &v);
+    if (st) return st;
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    const size_t n = v.pixels();
     if (!ctx->ex_hist || ctx->ex_dirty) { // both histograms zero: once, and after a launch that failed
         { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
         if (!ctx->ex_hist) HIP_TRY(ctx, hipMalloc(&ctx->ex_hist, 2u * RT_EX_STRIDE * sizeof(uint32_t)));
@@ -134,13 +110,12 @@ rsrt_status rsrt_exposure_meter(rsrt_context *ctx, uint32_t source, uint32_t sam
         ctx->ex_cur = 0;
         ctx->ex_dirty = ctx->ex_have = false;
     }
-    rsrt_status st = begin_work(ctx, stream);
-    if (st) return st;
+    if ((st = begin_work(ctx, stream))) return st;
     const size_t trip = (size_t)RT_EX_BLOCK * RT_EX_AHEAD, want = (n + trip - 1u) / trip;
     uint32_t *const now = ctx->ex_hist + (ctx->ex_cur ^ 1u) * RT_EX_STRIDE, *const old = ctx->ex_hist + ctx->ex_cur * RT_EX_STRIDE;
     ctx->ex_have = false; // (a failed launch leaves no histogram, and neither buffer known to be zero)
     ctx->ex_dirty = true;
-    rt_exposure_hist_kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(RT_EX_BLOCK), 0, stream>>>(img, n, total, now, old);
+    rt_exposure_hist_kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(RT_EX_BLOCK), 0, stream>>>(v.img, n, v.total, now, old);
     HIP_TRY(ctx, hipGetLastError());
     ctx->ex_cur ^= 1u;
     ctx->ex_dirty = false;
@@ -152,7 +127,7 @@ rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: whole frame only (partition of %u ranks)", ctx->world);
+    { rsrt_status st0 = whole_frame(ctx, "exposure_download"); if (st0) return st0; }
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: params is NULL");
     if (params->flags != 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: flags must be 0");
     if (!rsrt_exposure_params_ok(params))
@@ -171,7 +146,7 @@ rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params
 rsrt_status rsrt_exposure_reset(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_reset: whole frame only (partition of %u ranks)", ctx->world);
+    { rsrt_status st0 = whole_frame(ctx, "exposure_reset"); if (st0) return st0; }
     ctx->ex_have = false;
     return RSRT_OK;
 }
@@ -180,21 +155,16 @@ rsrt_status rsrt_display_exposed_srgb8(rsrt_context *ctx, uint32_t source, uint3
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    const float4 *img = nullptr;
-    size_t n = 0;
-    float total = 1.0f;
-    { rsrt_status st0 = exposure_source(ctx, "display_exposed_srgb8", source, sample_total, &img, &n, &total); if (st0) return st0; }
+    ImageView v;
+    rsrt_status st = exposure_source(ctx, "display_exposed_srgb8", source, sample_total, &v);
+    if (st) return st;
+    const size_t n = v.pixels();
     if (!rsrt_exposure_finite_positive(exposure)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_exposed_srgb8: exposure must be finite and > 0");
     if (!host_rgba8 || n_bytes != n * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_exposed_srgb8: expected %zu bytes", n * 4);
-    rsrt_status st = ensure_scratch(ctx, n * sizeof(uchar4));
-    if (st || (st = begin_work(ctx, ctx->stream))) return st;
-    uchar4 *tmp = static_cast<uchar4 *>(ctx->scratch);
-    rt_display_exposed_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(img, n, total, exposure, tmp);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(host_rgba8, tmp, n * sizeof(uchar4), hipMemcpyDeviceToHost, ctx->stream));
-    if ((st = end_work(ctx, ctx->stream))) return st;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return RSRT_OK;
+    return read_back(ctx, host_rgba8, n * sizeof(uchar4), 0, [&](void *tmp) {
+        rt_display_exposed_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(v.img, n, v.total, exposure, static_cast<uchar4 *>(tmp));
+        return RSRT_OK;
+    });
 }
 
 } // extern "C"

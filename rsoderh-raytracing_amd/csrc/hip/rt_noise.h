@@ -59,24 +59,14 @@ rsrt_status rsrt_noise_snapshot(rsrt_context *ctx, uint32_t sample_total, void *
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_snapshot: whole frame only (partition of %u ranks)", ctx->world);
-    if (sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_snapshot: sample_total must be > 0");
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    const size_t bytes = (size_t)ctx->acc_w * ctx->acc_h * sizeof(float4);
-    if (!ctx->ns_snap || ctx->ns_w != ctx->acc_w || ctx->ns_h != ctx->acc_h) {
-        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-        (void)hipFree(ctx->ns_snap);
-        ctx->ns_snap = nullptr;
-        ctx->ns_w = ctx->ns_h = ctx->ns_total = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->ns_snap, bytes));
-        ctx->ns_w = ctx->acc_w;
-        ctx->ns_h = ctx->acc_h;
-    }
-    ctx->ns_total = 0; // (a failed copy leaves no snapshot)
-    rsrt_status st = begin_work(ctx, stream);
+    rsrt_status st = whole_frame(ctx, "noise_snapshot");
     if (st) return st;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ns_snap, ctx->accum, bytes, hipMemcpyDeviceToDevice, stream));
+    if (sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_snapshot: sample_total must be > 0");
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    ctx->ns_total = 0; // (a new buffer or a failed copy leaves no snapshot)
+    if ((st = ensure_sized(ctx, ctx->ns_snap, ctx->acc.w, ctx->acc.h, sizeof(float4))) || (st = begin_work(ctx, stream))) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ns_snap.p, ctx->acc.p, ctx->acc.bytes(), hipMemcpyDeviceToDevice, stream));
     ctx->ns_total = sample_total;
     return end_work(ctx, stream);
 }
@@ -86,19 +76,20 @@ rsrt_status rsrt_noise_estimate(rsrt_context *ctx, uint32_t sample_total, const 
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: params is NULL");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: whole frame only (partition of %u ranks)", ctx->world);
+    rsrt_status st = whole_frame(ctx, "noise_estimate");
+    if (st) return st;
     const rsrt_noise_params &p = *params;
     if (p.flags != 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: flags must be 0");
     if (!rsrt_noise_tile_ok(p.tile_w, p.tile_h))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: tile %ux%u: pixel count must be a multiple of 64 and at most 4096", p.tile_w, p.tile_h);
     if (!(p.threshold >= 0.0f)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: threshold must be >= 0");
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    if (!ctx->ns_snap || ctx->ns_total == 0 || ctx->ns_w != ctx->acc_w || ctx->ns_h != ctx->acc_h)
+    if (!ctx->acc.p) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
+    if (ctx->ns_total == 0 || !ctx->ns_snap.is(ctx->acc.w, ctx->acc.h))
         return fail(ctx, RSRT_ERR_NOT_READY, "noise_estimate: no snapshot of this accumulator (rsrt_noise_snapshot first)");
     if (sample_total <= ctx->ns_total)
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_estimate: sample_total %u is not above the snapshot's %u", sample_total, ctx->ns_total);
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    const uint32_t W = ctx->acc_w, H = ctx->acc_h;
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    const uint32_t W = ctx->acc.w, H = ctx->acc.h;
     const uint32_t tiles_x = (W - 1u) / p.tile_w + 1u, tiles_y = (H - 1u) / p.tile_h + 1u;
     const size_t n_tiles = (size_t)tiles_x * tiles_y;
     if (n_tiles > ctx->ns_tiles_cap) {
@@ -110,10 +101,9 @@ rsrt_status rsrt_noise_estimate(rsrt_context *ctx, uint32_t sample_total, const 
         HIP_TRY(ctx, hipMalloc(&ctx->ns_tiles, n_tiles * sizeof(float)));
         ctx->ns_tiles_cap = n_tiles;
     }
-    rsrt_status st = begin_work(ctx, stream);
-    if (st) return st;
+    if ((st = begin_work(ctx, stream))) return st;
     rt_noise_tile_kernel<<<dim3((unsigned)((n_tiles + RT_NS_WAVES - 1u) / RT_NS_WAVES)), dim3(RT_NS_WAVES * RT_WAVE), 0, stream>>>(
-        ctx->accum, ctx->ns_snap, ctx->ns_tiles, W, H, p.tile_w, p.tile_h, tiles_x, (uint32_t)n_tiles, (float)ctx->ns_total, (float)sample_total);
+        ctx->acc.p, static_cast<const float4 *>(ctx->ns_snap.p), ctx->ns_tiles, W, H, p.tile_w, p.tile_h, tiles_x, (uint32_t)n_tiles, (float)ctx->ns_total, (float)sample_total);
     HIP_TRY(ctx, hipGetLastError());
     ctx->ns_tx = tiles_x;
     ctx->ns_ty = tiles_y;
@@ -126,7 +116,7 @@ rsrt_status rsrt_noise_download(rsrt_context *ctx, float *host_tiles, size_t n_f
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_download: whole frame only (partition of %u ranks)", ctx->world);
+    { rsrt_status st0 = whole_frame(ctx, "noise_download"); if (st0) return st0; }
     if (!ctx->ns_have) return fail(ctx, RSRT_ERR_NOT_READY, "no noise estimate (rsrt_noise_estimate first)");
     const size_t n = (size_t)ctx->ns_tx * ctx->ns_ty;
     if (host_tiles && n_floats != n) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_download: expected %zu floats", n);
@@ -155,7 +145,7 @@ rsrt_status rsrt_noise_download(rsrt_context *ctx, float *host_tiles, size_t n_f
 rsrt_status rsrt_noise_reset(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "noise_reset: whole frame only (partition of %u ranks)", ctx->world);
+    { rsrt_status st0 = whole_frame(ctx, "noise_reset"); if (st0) return st0; }
     drop_noise(ctx);
     return RSRT_OK;
 }

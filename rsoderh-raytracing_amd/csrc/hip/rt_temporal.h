@@ -76,26 +76,6 @@ __global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_temporal_moments_kerne
 
 namespace {
 
-// the two moment buffers (float4 each), allocated on the first MOMENTS frame after ensure_temporal and freed with the history
-rsrt_status ensure_moments(rsrt_context *ctx)
-{
-    if (ctx->tp_mom) return RSRT_OK;
-    HIP_TRY(ctx, hipMalloc(&ctx->tp_mom, (size_t)ctx->tp_w * ctx->tp_h * 2u * sizeof(float4)));
-    return RSRT_OK;
-}
-
-// history 0, history 1, features 0, features 1 (float4 each) for the accumulator's size; a new allocation starts without history
-rsrt_status ensure_temporal(rsrt_context *ctx)
-{
-    if (ctx->tp_buf && ctx->tp_w == ctx->acc_w && ctx->tp_h == ctx->acc_h) return RSRT_OK;
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    free_temporal(ctx);
-    HIP_TRY(ctx, hipMalloc(&ctx->tp_buf, (size_t)ctx->acc_w * ctx->acc_h * 4u * sizeof(float4)));
-    ctx->tp_w = ctx->acc_w;
-    ctx->tp_h = ctx->acc_h;
-    return RSRT_OK;
-}
-
 void tp_camera_of(const float c[13], rsrt_tp_camera *out) { rsrt_tp_camera_init(out, c, c + 3, c[12]); }
 
 } // namespace
@@ -117,11 +97,8 @@ rsrt_status rsrt_temporal_accumulate_ex(rsrt_context *ctx, const rsrt_camera *ca
     const bool moments = (flags & RSRT_TEMPORAL_MOMENTS) != 0;
     if (!camera) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: camera is NULL");
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: params is NULL");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: whole frame only (partition of %u ranks)", ctx->world);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "temporal: no AOV buffer (rsrt_aov_render or rsrt_aov_bind first)");
-    if (ctx->aov_w != ctx->acc_w || ctx->aov_h != ctx->acc_h)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
+    rsrt_status st = whole_frame(ctx, "temporal");
+    if (st || (st = accumulator_and_aov(ctx, "temporal"))) return st;
     const rsrt_temporal_params &p = *params;
     if (p.max_history < 1u || p.max_history > (1u << 24))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: max_history %u (1 .. 2^24)", p.max_history);
@@ -131,12 +108,14 @@ rsrt_status rsrt_temporal_accumulate_ex(rsrt_context *ctx, const rsrt_camera *ca
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: normal_tolerance must lie in [-1, 1]");
     if (sample_total == 0 || aov_sample_total == 0)
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal: sample_total and aov_sample_total must be > 0");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    rsrt_status st = ensure_temporal(ctx);
-    if (!st && moments) st = ensure_moments(ctx);
-    if (st || (st = begin_work(ctx, stream))) return st;
-    const uint32_t w = ctx->acc_w, h = ctx->acc_h;
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    const uint32_t w = ctx->acc.w, h = ctx->acc.h;
     const size_t n = (size_t)w * h;
+    // history 0, history 1, features 0, features 1 (float4 each), and on the first MOMENTS frame the two moment buffers (float4 each).  A new
+    // allocation starts without history: accumulator_size_changed() dropped it with the old one
+    if ((st = ensure_sized(ctx, ctx->tp_hist, w, h, 4u * sizeof(float4))) || (moments && (st = ensure_sized(ctx, ctx->tp_mom, w, h, 2u * sizeof(float4)))) ||
+        (st = begin_work(ctx, stream)))
+        return st;
     float cam[13];
     memcpy(cam, camera->pos, 12);
     for (int j = 0; j < 3; j++) for (int k = 0; k < 3; k++) cam[3 + 3 * j + k] = camera->rot_transform[j][k];
@@ -156,13 +135,13 @@ rsrt_status rsrt_temporal_accumulate_ex(rsrt_context *ctx, const rsrt_camera *ca
     fr.has_prev = ctx->tp_frames > 0 && ctx->tp_moments == (moments ? 1u : 0u); // (a MOMENTS toggle drops the history)
     fr.identity = fr.has_prev && rsrt_tp_same_camera(&fr.cur, &fr.prev); // (a resize frees the buffers, so W and H are the previous frame's)
     const uint32_t src = ctx->tp_cur, dst = src ^ 1u;
-    float4 *hist = ctx->tp_buf, *feat = ctx->tp_buf + 2u * n;
+    float4 *hist = static_cast<float4 *>(ctx->tp_hist.p), *feat = hist + 2u * n, *mom = static_cast<float4 *>(ctx->tp_mom.p);
     const dim3 grid((w + RT_DN_BX - 1) / RT_DN_BX, (h + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
     if (moments)
-        rt_temporal_moments_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, ctx->tp_mom + src * n,
-                                                               hist + dst * n, feat + dst * n, ctx->tp_mom + dst * n);
+        rt_temporal_moments_kernel<<<grid, block, 0, stream>>>(fr, ctx->acc.p, ctx->aov.p, hist + src * n, feat + src * n, mom + src * n,
+                                                               hist + dst * n, feat + dst * n, mom + dst * n);
     else
-        rt_temporal_kernel<<<grid, block, 0, stream>>>(fr, ctx->accum, ctx->aov, hist + src * n, feat + src * n, hist + dst * n, feat + dst * n);
+        rt_temporal_kernel<<<grid, block, 0, stream>>>(fr, ctx->acc.p, ctx->aov.p, hist + src * n, feat + src * n, hist + dst * n, feat + dst * n);
     HIP_TRY(ctx, hipGetLastError());
     ctx->tp_cur = dst;
     ctx->tp_frames++;
@@ -182,23 +161,16 @@ rsrt_status rsrt_temporal_download(rsrt_context *ctx, float *host, size_t n_floa
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->tp_buf || !ctx->tp_frames) return fail(ctx, RSRT_ERR_NOT_READY, "no temporal frame since the last reset (rsrt_temporal_accumulate first)");
-    if (!host || n_floats != (size_t)ctx->tp_w * ctx->tp_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal_download: expected %zu floats", (size_t)ctx->tp_w * ctx->tp_h * 4u);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, temporal_history(ctx), n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return image_download(ctx, "temporal_download", IMAGE_TEMPORAL, host, n_floats);
 }
 
 rsrt_status rsrt_temporal_moments_download(rsrt_context *ctx, float *host, size_t n_floats)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->tp_buf || !ctx->tp_frames || !ctx->tp_moments || !ctx->tp_mom)
+    if (!ctx->tp_hist.p || !ctx->tp_frames || !ctx->tp_moments || !ctx->tp_mom.p)
         return fail(ctx, RSRT_ERR_NOT_READY, "the last temporal frame carried no moments (rsrt_temporal_accumulate_ex with RSRT_TEMPORAL_MOMENTS first)");
-    if (!host || n_floats != (size_t)ctx->tp_w * ctx->tp_h * 4u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "temporal_moments_download: expected %zu floats", (size_t)ctx->tp_w * ctx->tp_h * 4u);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, temporal_moments(ctx), n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return download_floats(ctx, "temporal_moments_download", temporal_moments(ctx), ctx->tp_hist.pixels() * 4u, host, n_floats);
 }
 
 } // extern "C"

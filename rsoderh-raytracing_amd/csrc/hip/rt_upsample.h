@@ -55,56 +55,6 @@ __global__ __launch_bounds__(RT_DN_BX * RT_DN_BY) void rt_up_kernel(const float4
     out[P] = make_float4(o[0], o[1], o[2], 1.0f);
 }
 
-namespace {
-
-// the library's guide buffer: width x height records, zeroed; independent of the accumulator (a bound one must match)
-rsrt_status ensure_guide(rsrt_context *ctx, uint32_t width, uint32_t height)
-{
-    if (ctx->guide && ctx->guide_w == width && ctx->guide_h == height) return RSRT_OK;
-    if (ctx->guide && ctx->guide != ctx->guide_owned)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bound guide buffer is %ux%u but %ux%u was requested", ctx->guide_w, ctx->guide_h, width, height);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (ctx->guide_owned) { (void)hipFree(ctx->guide_owned); ctx->guide_owned = nullptr; ctx->guide = nullptr; ctx->guide_w = ctx->guide_h = 0; }
-    const size_t bytes = (size_t)width * height * 2u * sizeof(float4);
-    HIP_TRY(ctx, hipMalloc(&ctx->guide_owned, bytes));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->guide_owned, 0, bytes, ctx->stream)); // (on the context's stream: see ensure_aov)
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->guide = ctx->guide_owned;
-    ctx->guide_w = width;
-    ctx->guide_h = height;
-    return RSRT_OK;
-}
-
-// the low pass's colour (float4) and packed features (ushort4) for the accumulator's size, and the library-owned output for the guide's.
-// Scratch of its own: the denoiser's may hold the last denoise output, which is one of this pass's inputs.
-rsrt_status ensure_upsample_buffers(rsrt_context *ctx, bool own_output)
-{
-    const bool scratch_ok = ctx->up_scratch && ctx->up_w == ctx->acc_w && ctx->up_h == ctx->acc_h;
-    const bool out_ok = !own_output || (ctx->up_out && ctx->up_out_w == ctx->guide_w && ctx->up_out_h == ctx->guide_h);
-    if (scratch_ok && out_ok) return RSRT_OK;
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (!scratch_ok) {
-        (void)hipFree(ctx->up_scratch);
-        ctx->up_scratch = nullptr;
-        ctx->up_w = ctx->up_h = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->up_scratch, (size_t)ctx->acc_w * ctx->acc_h * (sizeof(float4) + sizeof(ushort4))));
-        ctx->up_w = ctx->acc_w;
-        ctx->up_h = ctx->acc_h;
-    }
-    if (!out_ok) {
-        if (ctx->up_last == ctx->up_out) ctx->up_last = nullptr;
-        (void)hipFree(ctx->up_out);
-        ctx->up_out = nullptr;
-        ctx->up_out_w = ctx->up_out_h = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->up_out, (size_t)ctx->guide_w * ctx->guide_h * sizeof(float4)));
-        ctx->up_out_w = ctx->guide_w;
-        ctx->up_out_h = ctx->guide_h;
-    }
-    return RSRT_OK;
-}
-
-} // namespace
-
 extern "C" {
 
 rsrt_status rsrt_guide_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin,
@@ -115,56 +65,35 @@ rsrt_status rsrt_guide_render(rsrt_context *ctx, const rsrt_camera *camera, uint
     if (!camera) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "camera is NULL");
     if (!ctx->scene_ready) return fail(ctx, RSRT_ERR_NOT_READY, "no scene uploaded");
     if (flags != 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "guide_render: flags must be 0");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "guide_render: whole frame only (partition of %u ranks)", ctx->world);
+    rsrt_status st = whole_frame(ctx, "guide_render");
+    if (st) return st;
     if (width == 0 || height == 0 || width > RSRT_UP_MAX_SIZE || height > RSRT_UP_MAX_SIZE)
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "guide_render: bad resolution %ux%u (1 .. %u)", width, height, RSRT_UP_MAX_SIZE);
     if ((uint64_t)sample_begin + sample_count > 0xffffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "sample range overflows u32");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    rsrt_status st = ensure_guide(ctx, width, height);
-    if (st) return st;
+    if ((st = buffer_ensure(ctx, ctx->guide, width, height))) return st; // (independent of the accumulator's size)
     if (sample_count == 0) return RSRT_OK;
-    return launch_aov(ctx, camera, width, height, sample_begin, sample_count, ctx->guide, stream);
+    return launch_aov(ctx, camera, width, height, sample_begin, sample_count, ctx->guide.p, stream_of(ctx, hip_stream));
 }
 
 rsrt_status rsrt_guide_bind(rsrt_context *ctx, void *device_f32x8, uint32_t width, uint32_t height)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    if (!device_f32x8) {
-        if (ctx->guide != ctx->guide_owned) ctx->guide_w = ctx->guide_h = 0; // (a bound buffer's size says nothing about the library's)
-        ctx->guide = ctx->guide_owned;
-        return RSRT_OK;
-    }
-    if (width == 0 || height == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
-    if ((uintptr_t)device_f32x8 % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "guide pointer must be 16-byte aligned");
-    if (ctx->guide_owned) { (void)hipFree(ctx->guide_owned); ctx->guide_owned = nullptr; }
-    ctx->guide = static_cast<float4 *>(device_f32x8);
-    ctx->guide_w = width;
-    ctx->guide_h = height;
-    return RSRT_OK;
+    return buffer_bind(ctx, ctx->guide, device_f32x8, width, height);
 }
 
 rsrt_status rsrt_guide_clear(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->guide) return fail(ctx, RSRT_ERR_NOT_READY, "no guide buffer");
-    rsrt_status st = begin_work(ctx, ctx->stream);
-    if (st) return st;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->guide, 0, (size_t)ctx->guide_w * ctx->guide_h * 2u * sizeof(float4), ctx->stream));
-    return end_work(ctx, ctx->stream);
+    return buffer_clear(ctx, ctx->guide);
 }
 
 rsrt_status rsrt_guide_download(rsrt_context *ctx, float *host, size_t n_floats)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->guide) return fail(ctx, RSRT_ERR_NOT_READY, "no guide buffer");
-    if (!host || n_floats != (size_t)ctx->guide_w * ctx->guide_h * 8u) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "guide_download: expected %zu floats", (size_t)ctx->guide_w * ctx->guide_h * 8u);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, ctx->guide, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return buffer_download(ctx, "guide_download", ctx->guide, host, n_floats);
 }
 
 rsrt_status rsrt_upsample(rsrt_context *ctx, uint32_t sample_total, uint32_t aov_sample_total, uint32_t guide_sample_total,
@@ -173,15 +102,11 @@ rsrt_status rsrt_upsample(rsrt_context *ctx, uint32_t sample_total, uint32_t aov
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: params is NULL");
-    if (ctx->world != 1) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: whole frame only (partition of %u ranks)", ctx->world);
-    if (!ctx->accum) return fail(ctx, RSRT_ERR_NOT_READY, "no accumulator");
-    if (!ctx->aov) return fail(ctx, RSRT_ERR_NOT_READY, "upsample: no AOV buffer (rsrt_aov_render or rsrt_aov_bind first)");
-    if (!ctx->guide) return fail(ctx, RSRT_ERR_NOT_READY, "upsample: no guide buffer (rsrt_guide_render or rsrt_guide_bind first)");
-    if (ctx->aov_w != ctx->acc_w || ctx->aov_h != ctx->acc_h)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: AOV buffer is %ux%u, accumulator %ux%u", ctx->aov_w, ctx->aov_h, ctx->acc_w, ctx->acc_h);
-    if (ctx->guide_w < ctx->acc_w || ctx->guide_h < ctx->acc_h || ctx->guide_w > RSRT_UP_MAX_SIZE || ctx->guide_h > RSRT_UP_MAX_SIZE)
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: guide is %ux%u, accumulator %ux%u (the guide is at least as large, at most %u)", ctx->guide_w,
-                    ctx->guide_h, ctx->acc_w, ctx->acc_h, RSRT_UP_MAX_SIZE);
+    rsrt_status st = whole_frame(ctx, "upsample");
+    if (st || (st = accumulator_and_aov(ctx, "upsample", &ctx->guide))) return st;
+    const uint32_t w = ctx->acc.w, h = ctx->acc.h, W = ctx->guide.w, H = ctx->guide.h;
+    if (W < w || H < h || W > RSRT_UP_MAX_SIZE || H > RSRT_UP_MAX_SIZE)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: guide is %ux%u, accumulator %ux%u (the guide is at least as large, at most %u)", W, H, w, h, RSRT_UP_MAX_SIZE);
     const rsrt_upsample_params &p = *params;
     if (p.flags & ~(uint32_t)(RSRT_UPSAMPLE_DEMODULATE | RSRT_UPSAMPLE_DENOISED | RSRT_UPSAMPLE_TEMPORAL))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: unknown flags 0x%x", p.flags);
@@ -192,27 +117,28 @@ rsrt_status rsrt_upsample(rsrt_context *ctx, uint32_t sample_total, uint32_t aov
     if (sample_total == 0 || aov_sample_total == 0 || guide_sample_total == 0)
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: sample_total, aov_sample_total and guide_sample_total must be > 0");
     if ((uintptr_t)device_out_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsample: output pointer must be 16-byte aligned");
-    if (denoised && !ctx->dn_last) return fail(ctx, RSRT_ERR_NOT_READY, "upsample: no denoised image (rsrt_denoise first)");
-    if (temporal && (!ctx->tp_frames || ctx->tp_w != ctx->acc_w || ctx->tp_h != ctx->acc_h))
-        return fail(ctx, RSRT_ERR_NOT_READY, "upsample: no temporal frame since the last reset (rsrt_temporal_accumulate first)");
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : ctx->stream;
-    rsrt_status st = ensure_upsample_buffers(ctx, device_out_rgba32f == nullptr);
-    if (st || (st = begin_work(ctx, stream))) return st;
-    const uint32_t w = ctx->acc_w, h = ctx->acc_h, W = ctx->guide_w, H = ctx->guide_h;
+    ImageView colour;
+    if ((st = resolve_image(ctx, "upsample", "upsample: ", denoised ? IMAGE_DENOISED : (temporal ? IMAGE_TEMPORAL : IMAGE_MEAN), sample_total, true, &colour))) return st;
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    // The low pass's colour (float4) and packed features (ushort4) for the accumulator's size — scratch of its own: the denoiser's may hold
+    // the last denoise output, which is one of this pass's inputs — and, unless the caller gave one, the output for the guide's size.
+    if ((st = ensure_sized(ctx, ctx->up_scratch, w, h, sizeof(float4) + sizeof(ushort4)))) return st;
+    if (!device_out_rgba32f) {
+        if (!ctx->up_out.is(W, H) && ctx->up_last.img == ctx->up_out.p) ctx->up_last = ImageView{}; // (it goes with the buffer it is in)
+        if ((st = ensure_sized(ctx, ctx->up_out, W, H, sizeof(float4)))) return st;
+    }
+    if ((st = begin_work(ctx, stream))) return st;
     const size_t n = (size_t)w * h;
-    float4 *r_lo = static_cast<float4 *>(ctx->up_scratch);
+    float4 *r_lo = static_cast<float4 *>(ctx->up_scratch.p);
     ushort4 *f_lo = reinterpret_cast<ushort4 *>(r_lo + n);
-    float4 *out = device_out_rgba32f ? static_cast<float4 *>(device_out_rgba32f) : ctx->up_out;
-    const float4 *colour = denoised ? ctx->dn_last : (temporal ? temporal_history(ctx) : ctx->accum);
+    float4 *out = static_cast<float4 *>(device_out_rgba32f ? device_out_rgba32f : ctx->up_out.p);
     const int demod = (p.flags & RSRT_UPSAMPLE_DEMODULATE) ? 1 : 0;
-    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(colour, ctx->aov, n, (float)sample_total, (float)aov_sample_total, demod, 0,
-                                                                                      r_lo, f_lo);
+    rt_dn_prepare_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(colour.img, ctx->aov.p, n, colour.total, (float)aov_sample_total, demod, 0, r_lo,
+                                                                                      f_lo);
     const dim3 grid((W + RT_DN_BX - 1) / RT_DN_BX, (H + RT_DN_BY - 1) / RT_DN_BY), block(RT_DN_BX, RT_DN_BY);
-    rt_up_kernel<<<grid, block, 0, stream>>>(r_lo, f_lo, ctx->guide, out, w, h, W, H, p.sigma_normal, p.sigma_depth, (float)guide_sample_total, demod);
+    rt_up_kernel<<<grid, block, 0, stream>>>(r_lo, f_lo, ctx->guide.p, out, w, h, W, H, p.sigma_normal, p.sigma_depth, (float)guide_sample_total, demod);
     HIP_TRY(ctx, hipGetLastError());
-    ctx->up_last = out;
-    ctx->up_last_w = W;
-    ctx->up_last_h = H;
+    ctx->up_last = ImageView{out, W, H, 1.0f};
     return end_work(ctx, stream);
 }
 
@@ -220,19 +146,13 @@ rsrt_status rsrt_upsampled_download(rsrt_context *ctx, float *host, size_t n_flo
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    if (!ctx->up_last) return fail(ctx, RSRT_ERR_NOT_READY, "no upsampled image (rsrt_upsample first)");
-    const size_t want = (size_t)ctx->up_last_w * ctx->up_last_h * 4u;
-    if (!host || n_floats != want) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "upsampled_download: expected %zu floats", want);
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    HIP_TRY(ctx, hipMemcpy(host, ctx->up_last, n_floats * sizeof(float), hipMemcpyDeviceToHost));
-    return RSRT_OK;
+    return image_download(ctx, "upsampled_download", IMAGE_UPSAMPLED, host, n_floats);
 }
 
 rsrt_status rsrt_upsampled_display_srgb8(rsrt_context *ctx, uint8_t *host_rgba8, size_t n_bytes)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    if (!ctx->up_last) return fail(ctx, RSRT_ERR_NOT_READY, "no upsampled image (rsrt_upsample first)");
-    return display_from_n(ctx, ctx->up_last, (size_t)ctx->up_last_w * ctx->up_last_h, 1u, host_rgba8, n_bytes);
+    return image_display(ctx, "upsampled_display_srgb8", IMAGE_UPSAMPLED, 1u, host_rgba8, n_bytes);
 }
 
 } // extern "C"

@@ -154,13 +154,13 @@ void sv_filter(rsrt_context *ctx, hipStream_t stream, const rsrt_denoise_params 
         float4 *dst = (i + 1u == L) ? out : ((i % 2u == 0u) ? b : a);
         if (variance) {
             if (i + 1u == L)
-                rt_sv_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total);
+                rt_sv_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total);
             else
-                rt_sv_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total);
+                rt_sv_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total);
         } else if (i + 1u == L) {
-            rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total, demod);
+            rt_dn_level_kernel<true><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total, demod);
         } else {
-            rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total, demod);
+            rt_dn_level_kernel<false><<<grid, block, 0, stream>>>(src, feat, ctx->aov.p, dst, w, h, i, p.sigma_color, p.sigma_normal, p.sigma_depth, aov_total, demod);
         }
     }
 }
