@@ -516,6 +516,54 @@ rsrt_status rsrt_exposure_reset(rsrt_context *ctx); /* drops the histogram */
 rsrt_status rsrt_display_exposed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, uint8_t *host_rgba8,
                                        size_t n_bytes);
 
+/* -- bloom: a bright-pass mip pyramid and a bloomed display (no reference counterpart) -----------------------------------------
+ * The exposed display clips everything brighter than display white to the same white, so the sun and the glints on metal are dots.
+ * rsrt_bloom builds, between the meter and the tone map, the thresholded mip-pyramid bloom of Jimenez 2014 (with the firefly
+ * weighting of Karis 2013 on the first downsample) of one of the four images the library can hold: a prefilter (exposure, clamp,
+ * threshold), `levels` 13-tap downsamples, a tent and a doubling on the way back up.  The bloom image B is half the source's size,
+ * ceil(w / 2) x ceil(h / 2); rsrt_display_bloomed_srgb8 is the exposed display pass with intensity * up(B) added before the tone map.
+ * The arithmetic is published in include/rsrt_bloom.h and is bitwise reproducible.
+ *
+ * The library keeps NO exposure: the caller passes the same exposure to rsrt_bloom and to rsrt_display_bloomed_srgb8 (the State
+ * classes do).  B and the size of the source it was built for stay valid until the next rsrt_bloom, rsrt_bloom_reset, a change of the
+ * accumulator's size (rsrt_accumulator_resize, a bind of another size or of NULL) or rsrt_context_destroy.  Whole frame only, like
+ * the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.  Nothing here writes the accumulator, the AOV
+ * buffer, the guide, any history, the denoised or upsampled image or the exposure histogram.  A refused call launches nothing and
+ * leaves the last bloom image as it was.
+ * rsrt_bloom_params defaults: levels 6, flags RSRT_BLOOM_KARIS, threshold 1.0 (in exposed units: what is brighter than display
+ * white blooms); the default intensity is 0.1 (RSRT_BLOOM_* in include/rsrt_bloom.h). */
+enum { RSRT_BLOOM_KARIS = 1u }; /* the first downsample weighs its five groups by 1 / (1 + luminance) */
+typedef struct rsrt_bloom_params {
+    uint32_t levels;  /* 1 .. 8 (RSRT_BLOOM_MAX_LEVELS); a level may be 1 x 1 */
+    uint32_t flags;   /* RSRT_BLOOM_KARIS or 0 */
+    float threshold;  /* finite, >= 0, in exposed units */
+    float _pad;
+} rsrt_bloom_params;
+/* Builds B of `source` (RSRT_EXPOSURE_*) in a library-owned pyramid (about 11 bytes a source pixel); asynchronous on hip_stream,
+ * NULL = the context's stream, ordered after everything enqueued so far.  sample_total is ignored for all sources but
+ * RSRT_EXPOSURE_MEAN.  RSRT_ERR_NOT_READY when the source image does not exist; RSRT_ERR_INVALID_ARGUMENT for an unknown source,
+ * sample_total 0 under RSRT_EXPOSURE_MEAN, an exposure that is not finite and > 0, NULL params or params rsrt_bloom_params_ok refuses
+ * (levels, unknown flags, threshold).
+ * Rust: pub fn rsrt_bloom(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32, params: *const RsrtBloomParams,
+ *                         hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_bloom(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_bloom_params *params,
+                       void *hip_stream);
+/* Waits and copies B to host_rgba as RGBA32F, alpha 1; *width and *height (either may be NULL) receive its size, which is all a
+ * call with host_rgba NULL and n_floats 0 asks for.  RSRT_ERR_NOT_READY without a bloom image since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for another n_floats than 4 a texel.
+ * Rust: pub fn rsrt_bloom_download(ctx: *mut RsrtContext, host_rgba: *mut f32, n_floats: usize, width: *mut u32, height: *mut u32) -> i32; */
+rsrt_status rsrt_bloom_download(rsrt_context *ctx, float *host_rgba, size_t n_floats, uint32_t *width, uint32_t *height);
+/* Rust: pub fn rsrt_bloom_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_bloom_reset(rsrt_context *ctx); /* drops the bloom image */
+/* `source` through the bloomed display pass: rsrt_display_pixel_bloomed per pixel (include/rsrt_bloom.h), RGBA8, alpha 255; with
+ * intensity 0 the bytes of rsrt_display_exposed_srgb8.  Errors as for rsrt_exposure_meter, RSRT_ERR_NOT_READY without a bloom image
+ * since the last reset, and RSRT_ERR_INVALID_ARGUMENT for an exposure that is not finite and > 0, an intensity that is not finite and
+ * >= 0, a bloom image built for another size than `source` has, or another n_bytes than 4 a pixel.
+ * Rust: pub fn rsrt_display_bloomed_srgb8(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32, intensity: f32,
+ *                                         host_rgba8: *mut u8, n_bytes: usize) -> i32; */
+rsrt_status rsrt_display_bloomed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, float intensity,
+                                       uint8_t *host_rgba8, size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "rsrt.h"
+#include "rsrt_bloom.h"
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
 
@@ -335,6 +336,32 @@ public:
         check_ctx(rsrt_display_exposed_srgb8(context(0), source, sample_count_, exposure, out.data(), out.size()));
         return out;
     }
+    // -- bloom (rsrt.h "bloom"): one device, like the denoiser -----------------------------------------------------
+    static rsrt_bloom_params bloom_defaults() { return rsrt_bloom_params{RSRT_BLOOM_LEVELS, RSRT_BLOOM_FLAGS, RSRT_BLOOM_THRESHOLD, 0.0f}; }
+    // the bloom image of `source` at `exposure` (0: the remembered one, else 1), built on the device
+    void bloom(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_bloom_params &p = bloom_defaults())
+    {
+        check_ctx(rsrt_bloom(context(0), source, sample_count_, exposure_or_one(exposure), &p, nullptr));
+    }
+    // the last bloom(): RGBA32F, alpha 1, ceil(width / 2) x ceil(height / 2) of its source; the size where asked for
+    std::vector<float> bloom_download(uint32_t *width = nullptr, uint32_t *height = nullptr)
+    {
+        uint32_t w = 0, h = 0;
+        check_ctx(rsrt_bloom_download(context(0), nullptr, 0, &w, &h));
+        std::vector<float> out((size_t)w * h * 4);
+        check_ctx(rsrt_bloom_download(context(0), out.data(), out.size(), width, height));
+        return out;
+    }
+    void bloom_reset() { check_ctx(rsrt_bloom_reset(context(0))); } // drops the bloom image
+    // `source` through the display pass at `exposure` (0: the remembered one, else 1 — what bloom() took) with `intensity` times the
+    // doubled bloom image added before the tone map; of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    std::vector<uint8_t> display_bloomed(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, float intensity = RSRT_BLOOM_INTENSITY)
+    {
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
+        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        check_ctx(rsrt_display_bloomed_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), intensity, out.data(), out.size()));
+        return out;
+    }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
     // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass
@@ -439,6 +466,7 @@ private:
     size_t last_hash_ = 0;
     bool have_hash_ = false;
     float exposure_ = 0.0f; // the last auto_exposure() (0: none since exposure_reset)
+    float exposure_or_one(float exposure) const { return exposure != 0.0f ? exposure : (exposure_ != 0.0f ? exposure_ : 1.0f); }
 };
 
 } // namespace rsrt

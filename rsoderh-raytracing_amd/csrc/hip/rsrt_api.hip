@@ -644,6 +644,10 @@ struct rsrt_context {
     uint32_t *ex_hist = nullptr;
     uint32_t ex_cur = 0;
     bool ex_have = false, ex_dirty = false;
+    // bloom (rt_bloom.h): the pyramid of the last rsrt_bloom — B, then D_1 .. D_8 — which follows the size of the source B was built
+    // for, and whether there was one since the last reset
+    SizedAlloc bl_pyr;
+    bool bl_have = false;
 };
 
 namespace {
@@ -889,7 +893,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -1010,6 +1014,8 @@ void accumulator_size_changed(rsrt_context *ctx)
     ctx->tp_cur = ctx->tp_frames = ctx->tp_moments = 0;
     release(ctx->ns_snap);
     drop_noise(ctx);
+    release(ctx->bl_pyr);
+    ctx->bl_have = false;
 }
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -2422,3 +2428,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_upsample.h"
 #include "rt_noise.h"
 #include "rt_exposure.h"
+#include "rt_bloom.h"

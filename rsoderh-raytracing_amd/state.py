@@ -35,7 +35,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_temporal_accumulate_ex", "rsrt_temporal_moments_download",
             "rsrt_guide_render", "rsrt_guide_bind", "rsrt_guide_clear", "rsrt_guide_download", "rsrt_upsample", "rsrt_upsampled_download",
             "rsrt_upsampled_display_srgb8", "rsrt_noise_snapshot", "rsrt_noise_estimate", "rsrt_noise_download", "rsrt_noise_reset",
-            "rsrt_exposure_meter", "rsrt_exposure_download", "rsrt_exposure_reset", "rsrt_display_exposed_srgb8"]
+            "rsrt_exposure_meter", "rsrt_exposure_download", "rsrt_exposure_reset", "rsrt_display_exposed_srgb8",
+            "rsrt_bloom", "rsrt_bloom_download", "rsrt_bloom_reset", "rsrt_display_bloomed_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -99,6 +100,16 @@ class ExposureParams(C.Structure):
 class ExposureResult(C.Structure):
     _fields_ = [("exposure", C.c_float), ("target", C.c_float), ("average_luminance", C.c_float), ("metered", C.c_uint32),
                 ("skipped", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# rsrt_bloom_params.flags, its defaults and the default intensity (include/rsrt.h "bloom", include/rsrt_bloom.h)
+BLOOM_KARIS = 1  # the first downsample weighs its groups by 1 / (1 + luminance)
+BLOOM_MAX_LEVELS = 8
+BLOOM_DEFAULTS = {"levels": 6, "flags": BLOOM_KARIS, "threshold": 1.0, "intensity": 0.1}
+
+
+class BloomParams(C.Structure):
+    _fields_ = [("levels", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("_pad", C.c_float)]
 
 
 class TemporalParams(C.Structure):
@@ -222,6 +233,10 @@ def lib():
         L.rsrt_exposure_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsrt_exposure_reset.argtypes = [C.c_void_p]
         L.rsrt_display_exposed_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_size_t]
+        L.rsrt_bloom.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        L.rsrt_bloom_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.rsrt_bloom_reset.argtypes = [C.c_void_p]
+        L.rsrt_display_bloomed_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -621,6 +636,44 @@ class State:
         n = self.sample_count if sample_total is None else sample_total
         self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, exposure, _p(out), out.size),
                     "rsrt_display_exposed_srgb8")
+        return out
+
+    # -- bloom (include/rsrt.h "bloom") -----------------------------------------------------------------
+    def _exposure_or_one(self, exposure):
+        return (1.0 if self.exposure is None else self.exposure) if exposure is None else exposure
+
+    def bloom(self, source="mean", exposure=None, levels=None, threshold=None, karis=True, sample_total=None, stream=None):
+        """rsrt_bloom: builds the bloom image of `source` ("mean": the accumulator over sample_total, default sample_count;
+        "denoised", "temporal", "upsampled") at `exposure` (None: the remembered one, else 1) on the device.  levels, threshold:
+        BLOOM_DEFAULTS otherwise; karis: the firefly weighting of the first downsample.  Asynchronous."""
+        p = BloomParams(BLOOM_DEFAULTS["levels"] if levels is None else levels, BLOOM_KARIS if karis else 0,
+                        BLOOM_DEFAULTS["threshold"] if threshold is None else threshold, 0.0)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_bloom(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+                                       C.c_void_p(stream) if stream else None), "rsrt_bloom")
+
+    def bloom_download(self):
+        """rsrt_bloom_download: the bloom image of the last bloom(), [ceil(H / 2), ceil(W / 2), 4] float32, alpha 1."""
+        w, h = C.c_uint32(), C.c_uint32()
+        self._check(self._L.rsrt_bloom_download(self._ctx, None, 0, C.byref(w), C.byref(h)), "rsrt_bloom_download")
+        out = np.empty((h.value, w.value, 4), np.float32)
+        self._check(self._L.rsrt_bloom_download(self._ctx, _p(out), out.size, None, None), "rsrt_bloom_download")
+        return out
+
+    def bloom_reset(self):
+        """Drops the bloom image."""
+        self._check(self._L.rsrt_bloom_reset(self._ctx), "rsrt_bloom_reset")
+
+    def display_bloomed_srgb8(self, source="mean", exposure=None, intensity=None, sample_total=None):
+        """rsrt_display_bloomed_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1 — what
+        bloom() took) with `intensity` (BLOOM_DEFAULTS otherwise) times the doubled bloom image added before the tone map:
+        [H, W, 4] uint8, of the guide's size for "upsampled"."""
+        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
+        out = np.empty((self.guide_height, self.guide_width, 4) if up else (self.height, self.width, 4), np.uint8)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+                                                       BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
+                    "rsrt_display_bloomed_srgb8")
         return out
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
