@@ -564,6 +564,64 @@ rsrt_status rsrt_bloom_reset(rsrt_context *ctx); /* drops the bloom image */
 rsrt_status rsrt_display_bloomed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, float intensity,
                                        uint8_t *host_rgba8, size_t n_bytes);
 
+/* -- local exposure: a bilateral-grid base layer and a graded display (no reference counterpart) ---------------------------------
+ * The meter gives a frame ONE exposure: inside the house the walls are right and the sky through the openings clips, or the sky is
+ * right and the room is black.  rsrt_local_exposure builds, between the meter and the tone map, the bilateral grid (Chen, Paris,
+ * Durand 2007) of the log-luminance of one of the four images the library can hold: gx x gy x 32 cells of `cell` x `cell` pixels and
+ * one octave, each a count and a sum, blurred with a 1-2-1 tent along every axis.  rsrt_display_local_srgb8 is the exposed (or
+ * bloomed) display pass with a per-pixel gain before the tone map: the grid sliced at the pixel's position and log-luminance is the
+ * base layer (Durand, Dorsey 2002), and the gain moves the base towards key / exposure by `shadows` (below it) or `highlights` (above
+ * it) of the distance in octaves, at most max_stops.  The detail passes through.  The arithmetic is published in
+ * include/rsrt_local.h and is bitwise reproducible.
+ *
+ * The grid is of the UNEXPOSED image: the library keeps NO exposure and no strengths, they enter at the display alone, and a change
+ * of either needs no rebuild.  The grid and the size of the source it was built for stay valid until the next rsrt_local_exposure,
+ * rsrt_local_exposure_reset, a change of the accumulator's size (rsrt_accumulator_resize, a bind of another size or of NULL) or
+ * rsrt_context_destroy.  Whole frame only, like the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.
+ * Nothing here writes the accumulator, the AOV buffer, the guide, any history, the denoised or upsampled image, the exposure
+ * histogram or the bloom image.  A refused call launches nothing and leaves the last grid as it was.
+ * rsrt_local_params defaults: shadows 0.5, highlights 0.5, key 0.18, max_stops 4; the default cell is 32 (RSRT_LOCAL_* in
+ * include/rsrt_local.h). */
+typedef struct rsrt_local_params {
+    float shadows;    /* 0 .. 1: how far a base below key / exposure is lifted towards it */
+    float highlights; /* 0 .. 1: how far a base above it is lowered */
+    float key;        /* finite, > 0: the luminance the exposure is taken to put at mid-grey (the meter's key) */
+    float max_stops;  /* 0 .. 16: the most octaves a gain moves a pixel, either way */
+    uint32_t flags;   /* 0 */
+    uint32_t _pad;
+} rsrt_local_params;
+/* Builds the blurred grid of `source` (RSRT_EXPOSURE_*) in library-owned memory (2 x 256 bytes a grid column: 0.5 MB at 1920 x 1080
+ * and cell 32); asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far.  sample_total is
+ * ignored for all sources but RSRT_EXPOSURE_MEAN.  RSRT_ERR_NOT_READY when the source image does not exist;
+ * RSRT_ERR_INVALID_ARGUMENT for an unknown source, sample_total 0 under RSRT_EXPOSURE_MEAN or a cell other than 8, 16, 32, 64.
+ * Rust: pub fn rsrt_local_exposure(ctx: *mut RsrtContext, source: u32, sample_total: u32, cell: u32, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_local_exposure(rsrt_context *ctx, uint32_t source, uint32_t sample_total, uint32_t cell, void *hip_stream);
+/* Waits and copies the BLURRED grid to host_words: z-major, then y, then x, two words a cell (count, sum of q); dims_out (may be
+ * NULL) receives gx, gy, gz, cell, which is all a call with host_words NULL and n_words 0 asks for.  RSRT_ERR_NOT_READY without a
+ * grid since the last reset; RSRT_ERR_INVALID_ARGUMENT for another n_words than 2 * gx * gy * gz.
+ * Rust: pub fn rsrt_local_exposure_download(ctx: *mut RsrtContext, host_words: *mut u32, n_words: usize, dims_out: *mut u32) -> i32; */
+rsrt_status rsrt_local_exposure_download(rsrt_context *ctx, uint32_t *host_words, size_t n_words, uint32_t dims_out[4]);
+/* Rust: pub fn rsrt_local_exposure_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_local_exposure_reset(rsrt_context *ctx); /* drops the grid */
+/* The gain of every pixel of `source` at `exposure` under `params`, W x H f32 (1 for a skipped pixel): what
+ * rsrt_display_local_srgb8 multiplies by, so that the slice can be held bit for bit.  Errors as for rsrt_display_local_srgb8, with
+ * n_floats one a pixel.
+ * Rust: pub fn rsrt_local_gain_download(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                       params: *const RsrtLocalParams, host_gain: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_local_gain_download(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *params,
+                                     float *host_gain, size_t n_floats);
+/* `source` through the graded display pass: rsrt_display_pixel_local per pixel (include/rsrt_local.h), RGBA8, alpha 255.  With
+ * bloom_intensity 0 no bloom image is needed; with bloom_intensity > 0 the rules are rsrt_display_bloomed_srgb8's.  With shadows and
+ * highlights 0 the bytes are rsrt_display_exposed_srgb8's or rsrt_display_bloomed_srgb8's.  Errors as for rsrt_exposure_meter,
+ * RSRT_ERR_NOT_READY without a grid (or, with bloom_intensity > 0, a bloom image) since the last reset, and
+ * RSRT_ERR_INVALID_ARGUMENT for an exposure that is not finite and > 0, NULL params or params rsrt_local_params_ok refuses, a
+ * bloom_intensity that is not finite and >= 0, a grid or a bloom image built for another size than `source` has, or another n_bytes
+ * than 4 a pixel.
+ * Rust: pub fn rsrt_display_local_srgb8(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                       params: *const RsrtLocalParams, bloom_intensity: f32, host_rgba8: *mut u8, n_bytes: usize) -> i32; */
+rsrt_status rsrt_display_local_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *params,
+                                     float bloom_intensity, uint8_t *host_rgba8, size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -14,6 +14,7 @@
 #include "rsrt_bloom.h"
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
+#include "rsrt_local.h"
 
 namespace rsrt {
 
@@ -360,6 +361,44 @@ public:
         const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
         std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
         check_ctx(rsrt_display_bloomed_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), intensity, out.data(), out.size()));
+        return out;
+    }
+    // -- local exposure (rsrt.h "local exposure"): one device, like the denoiser --------------------------------------
+    static rsrt_local_params local_defaults()
+    {
+        return rsrt_local_params{RSRT_LOCAL_SHADOWS, RSRT_LOCAL_HIGHLIGHTS, RSRT_LOCAL_KEY, RSRT_LOCAL_MAX_STOPS, 0u, 0u};
+    }
+    // the blurred bilateral grid of `source` (unexposed), built on the device in cells of `cell` pixels
+    void local_exposure(uint32_t source = RSRT_EXPOSURE_MEAN, uint32_t cell = RSRT_LOCAL_CELL)
+    {
+        check_ctx(rsrt_local_exposure(context(0), source, sample_count_, cell, nullptr));
+    }
+    // the last local_exposure(): z-major, then y, then x, two words a cell (count, sum of q); gx, gy, gz, cell where asked for
+    std::vector<uint32_t> local_exposure_download(uint32_t dims_out[4] = nullptr)
+    {
+        uint32_t dims[4] = {0, 0, 0, 0};
+        check_ctx(rsrt_local_exposure_download(context(0), nullptr, 0, dims));
+        std::vector<uint32_t> out((size_t)dims[0] * dims[1] * dims[2] * 2);
+        check_ctx(rsrt_local_exposure_download(context(0), out.data(), out.size(), dims_out));
+        return out;
+    }
+    void local_exposure_reset() { check_ctx(rsrt_local_exposure_reset(context(0))); } // drops the grid
+    // the gain display_local() multiplies every pixel of `source` by at `exposure` (0: the remembered one, else 1)
+    std::vector<float> local_gain(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_local_params &p = local_defaults())
+    {
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
+        std::vector<float> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_));
+        check_ctx(rsrt_local_gain_download(context(0), source, sample_count_, exposure_or_one(exposure), &p, out.data(), out.size()));
+        return out;
+    }
+    // `source` through the display pass at `exposure` (0: the remembered one, else 1) with the local gain of the last local_exposure()
+    // and, with bloom_intensity > 0, the last bloom() added before it; of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    std::vector<uint8_t> display_local(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_local_params &p = local_defaults(),
+                                       float bloom_intensity = 0.0f)
+    {
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
+        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        check_ctx(rsrt_display_local_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), &p, bloom_intensity, out.data(), out.size()));
         return out;
     }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------

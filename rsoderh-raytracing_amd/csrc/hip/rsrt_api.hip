@@ -648,6 +648,12 @@ struct rsrt_context {
     // for, and whether there was one since the last reset
     SizedAlloc bl_pyr;
     bool bl_have = false;
+    // local exposure (rt_local.h): the raw and the blurred bilateral grid of the last rsrt_local_exposure, one allocation that follows
+    // the size of the source the grid was built for and has room for the smallest cell; the cell, and whether there was a grid since
+    // the last reset.  The library keeps no exposure and no strengths.
+    SizedAlloc lc_grid;
+    uint32_t lc_cell = 0;
+    bool lc_have = false;
 };
 
 namespace {
@@ -893,7 +899,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -1016,6 +1022,8 @@ void accumulator_size_changed(rsrt_context *ctx)
     drop_noise(ctx);
     release(ctx->bl_pyr);
     ctx->bl_have = false;
+    release(ctx->lc_grid);
+    ctx->lc_have = false;
 }
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -2429,3 +2437,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_noise.h"
 #include "rt_exposure.h"
 #include "rt_bloom.h"
+#include "rt_local.h"

@@ -36,7 +36,9 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_guide_render", "rsrt_guide_bind", "rsrt_guide_clear", "rsrt_guide_download", "rsrt_upsample", "rsrt_upsampled_download",
             "rsrt_upsampled_display_srgb8", "rsrt_noise_snapshot", "rsrt_noise_estimate", "rsrt_noise_download", "rsrt_noise_reset",
             "rsrt_exposure_meter", "rsrt_exposure_download", "rsrt_exposure_reset", "rsrt_display_exposed_srgb8",
-            "rsrt_bloom", "rsrt_bloom_download", "rsrt_bloom_reset", "rsrt_display_bloomed_srgb8"]
+            "rsrt_bloom", "rsrt_bloom_download", "rsrt_bloom_reset", "rsrt_display_bloomed_srgb8",
+            "rsrt_local_exposure", "rsrt_local_exposure_download", "rsrt_local_exposure_reset", "rsrt_local_gain_download",
+            "rsrt_display_local_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -110,6 +112,17 @@ BLOOM_DEFAULTS = {"levels": 6, "flags": BLOOM_KARIS, "threshold": 1.0, "intensit
 
 class BloomParams(C.Structure):
     _fields_ = [("levels", C.c_uint32), ("flags", C.c_uint32), ("threshold", C.c_float), ("_pad", C.c_float)]
+
+
+# the local exposure pass's cells and defaults (include/rsrt.h "local exposure", include/rsrt_local.h)
+LOCAL_CELLS = (8, 16, 32, 64)
+LOCAL_GZ = 32
+LOCAL_DEFAULTS = {"cell": 32, "shadows": 0.5, "highlights": 0.5, "key": 0.18, "max_stops": 4.0}
+
+
+class LocalParams(C.Structure):
+    _fields_ = [("shadows", C.c_float), ("highlights", C.c_float), ("key", C.c_float), ("max_stops", C.c_float), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
 
 
 class TemporalParams(C.Structure):
@@ -237,6 +250,11 @@ def lib():
         L.rsrt_bloom_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.rsrt_bloom_reset.argtypes = [C.c_void_p]
         L.rsrt_display_bloomed_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_size_t]
+        L.rsrt_local_exposure.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_local_exposure_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_local_exposure_reset.argtypes = [C.c_void_p]
+        L.rsrt_local_gain_download.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_display_local_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -674,6 +692,59 @@ class State:
         self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                        BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
                     "rsrt_display_bloomed_srgb8")
+        return out
+
+    # -- local exposure (include/rsrt.h "local exposure") ---------------------------------------------------
+    def local_exposure(self, source="mean", cell=None, sample_total=None, stream=None):
+        """rsrt_local_exposure: builds the blurred bilateral grid of `source` ("mean": the accumulator over sample_total, default
+        sample_count; "denoised", "temporal", "upsampled") on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
+        otherwise).  The grid is of the unexposed image.  Asynchronous."""
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_local_exposure(self._ctx, EXPOSURE_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
+                                                C.c_void_p(stream) if stream else None), "rsrt_local_exposure")
+
+    def local_exposure_download(self):
+        """rsrt_local_exposure_download: (the blurred grid of the last local_exposure(), [32, gy, gx, 2] uint32 — count, sum of q; its
+        cell)."""
+        dims = (C.c_uint32 * 4)()
+        self._check(self._L.rsrt_local_exposure_download(self._ctx, None, 0, dims), "rsrt_local_exposure_download")
+        out = np.empty((dims[2], dims[1], dims[0], 2), np.uint32)
+        self._check(self._L.rsrt_local_exposure_download(self._ctx, _p(out), out.size, None), "rsrt_local_exposure_download")
+        return out, int(dims[3])
+
+    def local_exposure_reset(self):
+        """Drops the grid."""
+        self._check(self._L.rsrt_local_exposure_reset(self._ctx), "rsrt_local_exposure_reset")
+
+    @staticmethod
+    def _local_params(shadows, highlights, params):
+        q = dict(LOCAL_DEFAULTS, **params)
+        return LocalParams(q["shadows"] if shadows is None else shadows, q["highlights"] if highlights is None else highlights, q["key"],
+                           q["max_stops"], q.get("flags", 0), 0)
+
+    def _source_shape(self, source):
+        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
+        return (self.guide_height, self.guide_width) if up else (self.height, self.width)
+
+    def local_gain(self, source="mean", exposure=None, shadows=None, highlights=None, sample_total=None, **params):
+        """rsrt_local_gain_download: the gain display_local_srgb8 multiplies every pixel of `source` by at `exposure` (None: the
+        remembered one, else 1), [H, W] float32.  params: key, max_stops; LOCAL_DEFAULTS otherwise."""
+        p = self._local_params(shadows, highlights, params)
+        out = np.empty(self._source_shape(source), np.float32)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_local_gain_download(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+                                                     _p(out), out.size), "rsrt_local_gain_download")
+        return out
+
+    def display_local_srgb8(self, source="mean", exposure=None, shadows=None, highlights=None, bloom_intensity=0.0, sample_total=None, **params):
+        """rsrt_display_local_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1) with the local
+        gain of the last local_exposure() and, with bloom_intensity > 0, the last bloom() added before it: [H, W, 4] uint8, of the
+        guide's size for "upsampled".  shadows, highlights and params (key, max_stops): LOCAL_DEFAULTS otherwise."""
+        p = self._local_params(shadows, highlights, params)
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_display_local_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+                                                     bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
         return out
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------

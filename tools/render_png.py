@@ -1,11 +1,12 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
 (State.auto_exposure), print the metered exposure and average luminance and write the exposed display image; exposure=X: that exposure.
 With noise=X the exposure also puts the threshold in displayed units (auto: metered after the first 8 samples).  bloom=on or
 bloom=INTENSITY: State.bloom of the picture that is written, at its exposure (1 without exposure=), and the bloomed display image at the
-default or the given intensity."""
+default or the given intensity.  local=on or local=SHADOWS,HIGHLIGHTS: State.local_exposure of the picture that is written and the graded
+display image at its exposure, with the default or the given strengths and, with bloom=, the bloom added before the gain."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -18,7 +19,10 @@ if exposure is not None and exposure != "auto":
 bloom = next((a[len("bloom="):] for a in sys.argv[1:] if a.startswith("bloom=")), None)
 if bloom is not None:
     bloom = None if bloom == "off" else (R.state.BLOOM_DEFAULTS["intensity"] if bloom == "on" else float(bloom))
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom="))]
+local = next((a[len("local="):] for a in sys.argv[1:] if a.startswith("local=")), None)
+if local is not None:
+    local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
@@ -39,7 +43,12 @@ if exposure == "auto":
     r = st.auto_exposure(source)
     print("metered exposure %.6g, average luminance %.6g (%d pixels metered, %d skipped)" % (r["exposure"], r["average_luminance"], r["metered"], r["skipped"]))
     exposure = r["exposure"]
-if bloom is not None:
+if local is not None:
+    if bloom is not None:
+        st.bloom(source, exposure)
+    st.local_exposure(source)
+    host.write_png(out, st.display_local_srgb8(source, exposure, local[0], local[1], bloom_intensity=bloom or 0.0))
+elif bloom is not None:
     st.bloom(source, exposure)
     host.write_png(out, st.display_bloomed_srgb8(source, exposure, bloom))
 elif exposure is not None:
