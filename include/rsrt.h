@@ -622,6 +622,61 @@ rsrt_status rsrt_local_gain_download(rsrt_context *ctx, uint32_t source, uint32_
 rsrt_status rsrt_display_local_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *params,
                                      float bloom_intensity, uint8_t *host_rgba8, size_t n_bytes);
 
+/* -- depth of field: a circle-of-confusion pass and a lens-blur image (no reference counterpart) ---------------------------------
+ * The integrator traces the reference's pinhole camera, so everything is equally sharp at every distance.  rsrt_dof blurs one of the
+ * four images the library can hold as a thin lens focused on a plane would: per pixel a signed blur radius (the circle of confusion)
+ * from the first-hit distance in the pixel's AOV or guide record — negative in front of the focus plane, positive behind it, `aperture`
+ * times the picture's height for a point at infinity, at most max_radius pixels — and a disc gather over (2 max_radius + 1)^2 taps
+ * in which a tap behind the pixel spreads no wider than the pixel's own disc (the scatter-as-gather occlusion rule).  It is a blur
+ * of LINEAR, UNEXPOSED radiance: it runs after rsrt_denoise / rsrt_temporal_accumulate / rsrt_upsample and before the meter, bloom
+ * and local exposure, which take its output, the lens image, as their source RSRT_EXPOSURE_LENS.  The lens image has the size of the
+ * source it was built from.  The arithmetic is published in include/rsrt_dof.h and is bitwise reproducible.  With aperture 0, or
+ * everything on the focus plane, the lens image is the source's colour bit for bit.
+ *
+ * Sources RSRT_EXPOSURE_MEAN, _DENOISED and _TEMPORAL read the AOV buffer, which must have the accumulator's size;
+ * RSRT_EXPOSURE_UPSAMPLED reads the guide, which must have the upsampled image's size.  The lens image and its size stay valid until
+ * the next rsrt_dof, rsrt_dof_reset, a change of the accumulator's size (rsrt_accumulator_resize, a bind of another size or of NULL)
+ * or rsrt_context_destroy.  Whole frame only, like the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.
+ * Nothing here writes the accumulator, the AOV buffer, the guide, any history, the denoised or upsampled image, the exposure
+ * histogram, the bloom image or the local-exposure grid.  A refused call launches nothing and leaves the last lens image as it was.
+ * rsrt_dof_params defaults: focus_distance 1, aperture 0.01, max_radius 8, flags 0 (RSRT_DOF_* in include/rsrt_dof.h). */
+enum { RSRT_EXPOSURE_LENS = 4 }; /* the last rsrt_dof output: a source of the meter, bloom, local exposure and their displays */
+typedef struct rsrt_dof_params {
+    float focus_distance; /* finite, > 0: the depth along the optical axis that is sharp, in scene units */
+    float aperture;       /* finite, >= 0: the blur radius of a point at infinity as a fraction of the picture's height */
+    uint32_t max_radius;  /* 1 .. 16 (RSRT_DOF_MAX_RADIUS): the largest blur radius, in pixels */
+    uint32_t flags;       /* 0 */
+} rsrt_dof_params;
+/* Builds the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) seen through `camera` (the one the source and its records
+ * were rendered with) into device_out_rgba32f (device memory, W x H x 4 f32, 16-byte aligned, alpha 1) or, when that is NULL, into
+ * library-owned memory; 32 bytes of library-owned scratch a pixel either way.  Asynchronous on hip_stream, NULL = the context's
+ * stream, ordered after everything enqueued so far.  sample_total is ignored for all sources but RSRT_EXPOSURE_MEAN.
+ * RSRT_ERR_NOT_READY when the source image or its records do not exist; RSRT_ERR_INVALID_ARGUMENT for NULL camera or params, params
+ * rsrt_dof_params_ok refuses (focus_distance not finite and > 0, aperture not finite and >= 0, max_radius outside 1 .. 16, flags not
+ * 0), RSRT_EXPOSURE_LENS or an unknown source, sample_total 0 under RSRT_EXPOSURE_MEAN, records of another size than the source, a
+ * misaligned output pointer.
+ * Rust: pub fn rsrt_dof(ctx: *mut RsrtContext, source: u32, sample_total: u32, camera: *const RsrtCamera, params: *const RsrtDofParams,
+ *                       device_out_rgba32f: *mut c_void, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_dof(rsrt_context *ctx, uint32_t source, uint32_t sample_total, const rsrt_camera *camera, const rsrt_dof_params *params,
+                     void *device_out_rgba32f, void *hip_stream);
+/* Waits and copies the lens image to host_rgba as RGBA32F, alpha 1; *width and *height (either may be NULL) receive its size, which
+ * is all a call with host_rgba NULL and n_floats 0 asks for.  RSRT_ERR_NOT_READY without a lens image since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for another n_floats than 4 a pixel.
+ * Rust: pub fn rsrt_dof_download(ctx: *mut RsrtContext, host_rgba: *mut f32, n_floats: usize, width: *mut u32, height: *mut u32) -> i32; */
+rsrt_status rsrt_dof_download(rsrt_context *ctx, float *host_rgba, size_t n_floats, uint32_t *width, uint32_t *height);
+/* Waits and copies the signed blur radii of the last rsrt_dof, one f32 a pixel, so that the circle-of-confusion step can be held bit
+ * for bit.  Errors as for rsrt_dof_download, with n_floats one a pixel.
+ * Rust: pub fn rsrt_dof_coc_download(ctx: *mut RsrtContext, host_r: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_dof_coc_download(rsrt_context *ctx, float *host_r, size_t n_floats);
+/* Autofocus: the depth along the optical axis at pixel (x, y) of `source`'s records (rsrt_dof_depth, include/rsrt_dof.h), +inf on sky.
+ * Waits and copies one record; needs no image and no lens image.  RSRT_ERR_NOT_READY without the records; RSRT_ERR_INVALID_ARGUMENT
+ * for NULL camera or z_out, RSRT_EXPOSURE_LENS or an unknown source, records of another size than the accumulator (sources 0 .. 2),
+ * x or y outside the records.
+ * Rust: pub fn rsrt_dof_depth_at(ctx: *mut RsrtContext, source: u32, camera: *const RsrtCamera, x: u32, y: u32, z_out: *mut f32) -> i32; */
+rsrt_status rsrt_dof_depth_at(rsrt_context *ctx, uint32_t source, const rsrt_camera *camera, uint32_t x, uint32_t y, float *z_out);
+/* Rust: pub fn rsrt_dof_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_dof_reset(rsrt_context *ctx); /* drops the lens image */
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

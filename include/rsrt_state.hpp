@@ -12,6 +12,7 @@
 
 #include "rsrt.h"
 #include "rsrt_bloom.h"
+#include "rsrt_dof.h"
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
 #include "rsrt_local.h"
@@ -325,15 +326,14 @@ public:
         exposure_ = 0.0f;
         check_ctx(rsrt_exposure_reset(context(0)));
     }
-    // `source` through the display pass at `exposure` (0: the remembered one); of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    // `source` through the display pass at `exposure` (0: the remembered one); of the source's own size
     std::vector<uint8_t> display_exposed(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f)
     {
         if (exposure == 0.0f) {
             if (exposure_ == 0.0f) throw Error("display_exposed: no remembered exposure (auto_exposure first): RSRT_ERR_NOT_READY");
             exposure = exposure_;
         }
-        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
-        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        std::vector<uint8_t> out(source_pixels(source) * 4);
         check_ctx(rsrt_display_exposed_srgb8(context(0), source, sample_count_, exposure, out.data(), out.size()));
         return out;
     }
@@ -355,11 +355,10 @@ public:
     }
     void bloom_reset() { check_ctx(rsrt_bloom_reset(context(0))); } // drops the bloom image
     // `source` through the display pass at `exposure` (0: the remembered one, else 1 — what bloom() took) with `intensity` times the
-    // doubled bloom image added before the tone map; of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    // doubled bloom image added before the tone map; of the source's own size
     std::vector<uint8_t> display_bloomed(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, float intensity = RSRT_BLOOM_INTENSITY)
     {
-        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
-        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        std::vector<uint8_t> out(source_pixels(source) * 4);
         check_ctx(rsrt_display_bloomed_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), intensity, out.data(), out.size()));
         return out;
     }
@@ -386,21 +385,56 @@ public:
     // the gain display_local() multiplies every pixel of `source` by at `exposure` (0: the remembered one, else 1)
     std::vector<float> local_gain(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_local_params &p = local_defaults())
     {
-        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
-        std::vector<float> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_));
+        std::vector<float> out(source_pixels(source));
         check_ctx(rsrt_local_gain_download(context(0), source, sample_count_, exposure_or_one(exposure), &p, out.data(), out.size()));
         return out;
     }
     // `source` through the display pass at `exposure` (0: the remembered one, else 1) with the local gain of the last local_exposure()
-    // and, with bloom_intensity > 0, the last bloom() added before it; of the guide's size for RSRT_EXPOSURE_UPSAMPLED
+    // and, with bloom_intensity > 0, the last bloom() added before it; of the source's own size
     std::vector<uint8_t> display_local(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_local_params &p = local_defaults(),
                                        float bloom_intensity = 0.0f)
     {
-        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
-        std::vector<uint8_t> out((size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_) * 4);
+        std::vector<uint8_t> out(source_pixels(source) * 4);
         check_ctx(rsrt_display_local_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), &p, bloom_intensity, out.data(), out.size()));
         return out;
     }
+    // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------
+    static rsrt_dof_params dof_defaults() { return rsrt_dof_params{RSRT_DOF_FOCUS_DISTANCE, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS}; }
+    // the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) seen through the state's camera, built on the device; a
+    // focus_distance of 0 in p means the one focus_at() remembered, else the default.  The later passes take it as RSRT_EXPOSURE_LENS.
+    void depth_of_field(uint32_t source = RSRT_EXPOSURE_MEAN, rsrt_dof_params p = rsrt_dof_params{0.0f, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS})
+    {
+        if (p.focus_distance == 0.0f) p.focus_distance = focus_distance_ != 0.0f ? focus_distance_ : RSRT_DOF_FOCUS_DISTANCE;
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        check_ctx(rsrt_dof(context(0), source, sample_count_, &cam, &p, nullptr, nullptr));
+    }
+    // the last depth_of_field(): RGBA32F, alpha 1, of its source's size; the size where asked for
+    std::vector<float> dof_download(uint32_t *width = nullptr, uint32_t *height = nullptr)
+    {
+        std::vector<float> out(source_pixels(RSRT_EXPOSURE_LENS) * 4);
+        check_ctx(rsrt_dof_download(context(0), out.data(), out.size(), width, height));
+        return out;
+    }
+    std::vector<float> dof_coc() // the signed blur radii of the last depth_of_field(), in pixels (negative: near field)
+    {
+        std::vector<float> out(source_pixels(RSRT_EXPOSURE_LENS));
+        check_ctx(rsrt_dof_coc_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    // autofocus: the depth along the optical axis at pixel (x, y) of `source`'s records, remembered as the focus distance of later
+    // depth_of_field() calls; a sky pixel returns +inf and leaves the focus as it was
+    float focus_at(uint32_t x, uint32_t y, uint32_t source = RSRT_EXPOSURE_MEAN)
+    {
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        float z = 0.0f;
+        check_ctx(rsrt_dof_depth_at(context(0), source, &cam, x, y, &z));
+        if (rsrt_dof_finite(z) && z > 0.0f) focus_distance_ = z;
+        return z;
+    }
+    float focus_distance() const { return focus_distance_; } // the remembered focus distance (0: none)
+    void dof_reset() { check_ctx(rsrt_dof_reset(context(0))); } // drops the lens image
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
     // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass
@@ -506,6 +540,18 @@ private:
     bool have_hash_ = false;
     float exposure_ = 0.0f; // the last auto_exposure() (0: none since exposure_reset)
     float exposure_or_one(float exposure) const { return exposure != 0.0f ? exposure : (exposure_ != 0.0f ? exposure_ : 1.0f); }
+    float focus_distance_ = 0.0f; // the last focus_at() that hit a surface (0: none)
+    // the pixels of `source`: the guide's for RSRT_EXPOSURE_UPSAMPLED, what the library holds for RSRT_EXPOSURE_LENS, else the state's own
+    size_t source_pixels(uint32_t source)
+    {
+        if (source == RSRT_EXPOSURE_LENS) {
+            uint32_t w = 0, h = 0;
+            check_ctx(rsrt_dof_download(context(0), nullptr, 0, &w, &h));
+            return (size_t)w * h;
+        }
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
+        return (size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_);
+    }
 };
 
 } // namespace rsrt

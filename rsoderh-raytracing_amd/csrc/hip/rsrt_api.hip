@@ -512,7 +512,7 @@ struct ImageView {
     float total = 1.0f;
     size_t pixels() const { return (size_t)w * h; }
 };
-enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
+enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3, IMAGE_LENS = 4 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
 
 struct rsrt_context {
     int device = 0;
@@ -654,6 +654,11 @@ struct rsrt_context {
     SizedAlloc lc_grid;
     uint32_t lc_cell = 0;
     bool lc_have = false;
+    // depth of field (rt_dof.h): the prepared texels of the last rsrt_dof and, behind them, the library-owned lens image (a float4 a pixel
+    // each), one allocation that follows the size of the source the lens image was built from; and where the last rsrt_dof wrote (img
+    // NULL: no lens image since the last reset)
+    SizedAlloc df_buf;
+    ImageView df_last;
 };
 
 namespace {
@@ -899,7 +904,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -1024,6 +1029,8 @@ void accumulator_size_changed(rsrt_context *ctx)
     ctx->bl_have = false;
     release(ctx->lc_grid);
     ctx->lc_have = false;
+    release(ctx->df_buf);
+    ctx->df_last = ImageView{};
 }
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -1070,6 +1077,10 @@ rsrt_status resolve_image(rsrt_context *ctx, const char *what, const char *prefi
     case IMAGE_UPSAMPLED:
         if (!ctx->up_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno upsampled image (rsrt_upsample first)", prefix);
         *v = ctx->up_last;
+        return RSRT_OK;
+    case IMAGE_LENS:
+        if (!ctx->df_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno lens image (rsrt_dof first)", prefix);
+        *v = ctx->df_last;
         return RSRT_OK;
     default:
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
@@ -2438,3 +2449,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_exposure.h"
 #include "rt_bloom.h"
 #include "rt_local.h"
+#include "rt_dof.h"

@@ -38,7 +38,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_exposure_meter", "rsrt_exposure_download", "rsrt_exposure_reset", "rsrt_display_exposed_srgb8",
             "rsrt_bloom", "rsrt_bloom_download", "rsrt_bloom_reset", "rsrt_display_bloomed_srgb8",
             "rsrt_local_exposure", "rsrt_local_exposure_download", "rsrt_local_exposure_reset", "rsrt_local_gain_download",
-            "rsrt_display_local_srgb8"]
+            "rsrt_display_local_srgb8",
+            "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset"]
 
 
 class RsrtError(RuntimeError):
@@ -123,6 +124,17 @@ LOCAL_DEFAULTS = {"cell": 32, "shadows": 0.5, "highlights": 0.5, "key": 0.18, "m
 class LocalParams(C.Structure):
     _fields_ = [("shadows", C.c_float), ("highlights", C.c_float), ("key", C.c_float), ("max_stops", C.c_float), ("flags", C.c_uint32),
                 ("_pad", C.c_uint32)]
+
+
+# the depth-of-field pass (include/rsrt.h "depth of field", include/rsrt_dof.h): the sources a pass can read — the four images and the
+# lens image the pass leaves — its defaults and its parameters
+IMAGE_SOURCES = dict(EXPOSURE_SOURCES, lens=4)
+DOF_MAX_RADIUS = 16
+DOF_DEFAULTS = {"focus_distance": 1.0, "aperture": 0.01, "max_radius": 8, "flags": 0}
+
+
+class DofParams(C.Structure):
+    _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class TemporalParams(C.Structure):
@@ -255,6 +267,11 @@ def lib():
         L.rsrt_local_exposure_reset.argtypes = [C.c_void_p]
         L.rsrt_local_gain_download.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_local_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
+        L.rsrt_dof.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsrt_dof_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.rsrt_dof_coc_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_dof_depth_at.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_dof_reset.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -285,6 +302,7 @@ class State:
         self.guide_width = self.guide_height = 0  # the guide's size: what upsample() returns
         self._guide_bound = False
         self.exposure = None            # the last auto_exposure() (None: none since exposure_reset)
+        self.focus_distance = None      # the last focus_at() that hit a surface (None: depth_of_field takes DOF_DEFAULTS')
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -612,9 +630,9 @@ class State:
     # -- auto-exposure (include/rsrt.h "auto-exposure") -----------------------------------------------
     def exposure_meter(self, source="mean", sample_total=None, stream=None):
         """rsrt_exposure_meter: builds the luminance histogram of `source` ("mean": the accumulator over sample_total, default
-        sample_count; "denoised", "temporal", "upsampled") on the device.  Asynchronous."""
+        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) on the device.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_exposure_meter(self._ctx, EXPOSURE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
+        self._check(self._L.rsrt_exposure_meter(self._ctx, IMAGE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
                     "rsrt_exposure_meter")
 
     def exposure_download(self, **params):
@@ -644,15 +662,14 @@ class State:
 
     def display_exposed_srgb8(self, source="mean", exposure=None, sample_total=None):
         """rsrt_display_exposed_srgb8: `source` through the display pass at `exposure` (None: the remembered one; RsrtError with
-        RSRT_ERR_NOT_READY if there is none): [H, W, 4] uint8, of the guide's size for "upsampled"."""
+        RSRT_ERR_NOT_READY if there is none): [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens": its source's)."""
         if exposure is None:
             if self.exposure is None:
                 raise RsrtError("display_exposed_srgb8: no remembered exposure (auto_exposure first)", NOT_READY)
             exposure = self.exposure
-        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
-        out = np.empty((self.guide_height, self.guide_width, 4) if up else (self.height, self.width, 4), np.uint8)
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, exposure, _p(out), out.size),
+        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, exposure, _p(out), out.size),
                     "rsrt_display_exposed_srgb8")
         return out
 
@@ -662,12 +679,12 @@ class State:
 
     def bloom(self, source="mean", exposure=None, levels=None, threshold=None, karis=True, sample_total=None, stream=None):
         """rsrt_bloom: builds the bloom image of `source` ("mean": the accumulator over sample_total, default sample_count;
-        "denoised", "temporal", "upsampled") at `exposure` (None: the remembered one, else 1) on the device.  levels, threshold:
+        "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) at `exposure` (None: the remembered one, else 1) on the device.  levels, threshold:
         BLOOM_DEFAULTS otherwise; karis: the firefly weighting of the first downsample.  Asynchronous."""
         p = BloomParams(BLOOM_DEFAULTS["levels"] if levels is None else levels, BLOOM_KARIS if karis else 0,
                         BLOOM_DEFAULTS["threshold"] if threshold is None else threshold, 0.0)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_bloom(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_bloom(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                        C.c_void_p(stream) if stream else None), "rsrt_bloom")
 
     def bloom_download(self):
@@ -685,11 +702,10 @@ class State:
     def display_bloomed_srgb8(self, source="mean", exposure=None, intensity=None, sample_total=None):
         """rsrt_display_bloomed_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1 — what
         bloom() took) with `intensity` (BLOOM_DEFAULTS otherwise) times the doubled bloom image added before the tone map:
-        [H, W, 4] uint8, of the guide's size for "upsampled"."""
-        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
-        out = np.empty((self.guide_height, self.guide_width, 4) if up else (self.height, self.width, 4), np.uint8)
+        [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens": its source's)."""
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                        BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
                     "rsrt_display_bloomed_srgb8")
         return out
@@ -697,10 +713,10 @@ class State:
     # -- local exposure (include/rsrt.h "local exposure") ---------------------------------------------------
     def local_exposure(self, source="mean", cell=None, sample_total=None, stream=None):
         """rsrt_local_exposure: builds the blurred bilateral grid of `source` ("mean": the accumulator over sample_total, default
-        sample_count; "denoised", "temporal", "upsampled") on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
+        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
         otherwise).  The grid is of the unexposed image.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_exposure(self._ctx, EXPOSURE_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
+        self._check(self._L.rsrt_local_exposure(self._ctx, IMAGE_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
                                                 C.c_void_p(stream) if stream else None), "rsrt_local_exposure")
 
     def local_exposure_download(self):
@@ -723,8 +739,13 @@ class State:
                            q["max_stops"], q.get("flags", 0), 0)
 
     def _source_shape(self, source):
-        up = EXPOSURE_SOURCES.get(source, source) == EXPOSURE_SOURCES["upsampled"]
-        return (self.guide_height, self.guide_width) if up else (self.height, self.width)
+        """(H, W) of `source`: the guide's for "upsampled", what the library holds for "lens", else the state's own."""
+        source = IMAGE_SOURCES.get(source, source)
+        if source == IMAGE_SOURCES["lens"]:
+            w, h = C.c_uint32(), C.c_uint32()
+            self._check(self._L.rsrt_dof_download(self._ctx, None, 0, C.byref(w), C.byref(h)), "rsrt_dof_download")
+            return (h.value, w.value)
+        return (self.guide_height, self.guide_width) if source == IMAGE_SOURCES["upsampled"] else (self.height, self.width)
 
     def local_gain(self, source="mean", exposure=None, shadows=None, highlights=None, sample_total=None, **params):
         """rsrt_local_gain_download: the gain display_local_srgb8 multiplies every pixel of `source` by at `exposure` (None: the
@@ -732,20 +753,60 @@ class State:
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source), np.float32)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_gain_download(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_local_gain_download(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      _p(out), out.size), "rsrt_local_gain_download")
         return out
 
     def display_local_srgb8(self, source="mean", exposure=None, shadows=None, highlights=None, bloom_intensity=0.0, sample_total=None, **params):
         """rsrt_display_local_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1) with the local
         gain of the last local_exposure() and, with bloom_intensity > 0, the last bloom() added before it: [H, W, 4] uint8, of the
-        guide's size for "upsampled".  shadows, highlights and params (key, max_stops): LOCAL_DEFAULTS otherwise."""
+        source's own size.  shadows, highlights and params (key, max_stops): LOCAL_DEFAULTS otherwise."""
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_local_srgb8(self._ctx, EXPOSURE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_display_local_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
         return out
+
+    # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------
+    def depth_of_field(self, source="mean", focus_distance=None, aperture=None, max_radius=None, sample_total=None, stream=None, out_ptr=None):
+        """rsrt_dof: builds the lens image of `source` ("mean": the accumulator over sample_total, default sample_count; "denoised",
+        "temporal": with the AOV buffer; "upsampled": with the guide) seen through the state's camera, on the device (in out_ptr when
+        given).  focus_distance None: the one focus_at() remembered, else DOF_DEFAULTS'; aperture (the blur radius of a point at
+        infinity as a fraction of the picture's height) and max_radius (1 .. 16 pixels): DOF_DEFAULTS otherwise.  The later passes take
+        the result as their source "lens".  Asynchronous."""
+        d = DOF_DEFAULTS
+        if focus_distance is None:
+            focus_distance = d["focus_distance"] if self.focus_distance is None else self.focus_distance
+        p = DofParams(focus_distance, d["aperture"] if aperture is None else aperture, d["max_radius"] if max_radius is None else max_radius, 0)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_dof(self._ctx, IMAGE_SOURCES.get(source, source), n, _p(self.camera), C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
+                                     C.c_void_p(stream) if stream else None), "rsrt_dof")
+
+    def dof_download(self):
+        """rsrt_dof_download: the lens image of the last depth_of_field(), [H, W, 4] float32 of its source's size, alpha 1."""
+        out = np.empty(self._source_shape("lens") + (4,), np.float32)
+        self._check(self._L.rsrt_dof_download(self._ctx, _p(out), out.size, None, None), "rsrt_dof_download")
+        return out
+
+    def dof_coc(self):
+        """rsrt_dof_coc_download: the signed blur radii of the last depth_of_field() in pixels, [H, W] float32 (negative: near field)."""
+        out = np.empty(self._source_shape("lens"), np.float32)
+        self._check(self._L.rsrt_dof_coc_download(self._ctx, _p(out), out.size), "rsrt_dof_coc_download")
+        return out
+
+    def focus_at(self, x, y, source="mean"):
+        """Autofocus (rsrt_dof_depth_at): the depth along the optical axis at pixel (x, y) of `source`'s records, remembered as the focus
+        distance of later depth_of_field() calls.  A sky pixel returns inf and leaves the focus as it was."""
+        z = C.c_float()
+        self._check(self._L.rsrt_dof_depth_at(self._ctx, IMAGE_SOURCES.get(source, source), _p(self.camera), x, y, C.byref(z)), "rsrt_dof_depth_at")
+        if np.isfinite(z.value) and z.value > 0:
+            self.focus_distance = z.value
+        return z.value
+
+    def dof_reset(self):
+        """Drops the lens image (the remembered focus distance stays)."""
+        self._check(self._L.rsrt_dof_reset(self._ctx), "rsrt_dof_reset")
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):

@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -6,7 +6,11 @@ same samples and the default filter, the denoised display image instead; exposur
 With noise=X the exposure also puts the threshold in displayed units (auto: metered after the first 8 samples).  bloom=on or
 bloom=INTENSITY: State.bloom of the picture that is written, at its exposure (1 without exposure=), and the bloomed display image at the
 default or the given intensity.  local=on or local=SHADOWS,HIGHLIGHTS: State.local_exposure of the picture that is written and the graded
-display image at its exposure, with the default or the given strengths and, with bloom=, the bloom added before the gain."""
+display image at its exposure, with the default or the given strengths and, with bloom=, the bloom added before the gain.
+dof=FOCUS,APERTURE[,RADIUS]: State.depth_of_field of the picture (the AOV pass over the same samples gives the depths) focused at FOCUS
+scene units along the axis (auto: at the depth of the picture's centre, State.focus_at), with APERTURE the blur radius of a point at
+infinity as a fraction of the picture's height and at most RADIUS pixels (default 8); it runs before exposure=, bloom= and local=, which
+then meter, bloom and grade the lens image."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,7 +26,8 @@ if bloom is not None:
 local = next((a[len("local="):] for a in sys.argv[1:] if a.startswith("local=")), None)
 if local is not None:
     local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local="))]
+dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
@@ -31,13 +36,20 @@ if args[3].startswith("noise="):
     spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024, exposure=exposure,
                                 on_round=lambda r: print("samples %4d -> %4d: max tile error %.4f, mean %.4f, %d tiles above" % r, flush=True))
     print("stopped at", spp, "samples")
-    if denoise:
+    if denoise or dof:
         st.render_aov(0, spp)
 else:
-    st.render_samples(int(args[3]), aov=denoise)
+    st.render_samples(int(args[3]), aov=denoise or bool(dof))
 if denoise:
     st.denoise(download=False)
 source = "denoised" if denoise else "mean"
+if dof:
+    focus = st.focus_at(w // 2, h // 2) if dof[0] == "auto" else float(dof[0])
+    print("focus distance %.6g%s" % (focus, " (the centre is sky: the default focus)" if focus == float("inf") else ""))
+    st.depth_of_field(source, None if dof[0] == "auto" else focus, float(dof[1]), int(dof[2]) if len(dof) > 2 else None)
+    r = abs(st.dof_coc())
+    print("blur radius: mean %.3g px, %.1f %% of the pixels above half a pixel" % (r.mean(), 100.0 * (r > 0.5).mean()))
+    source = "lens"
 if exposure == "auto":
     st.exposure_reset()  # meter the picture that is written, whatever render_to_noise metered on the way
     r = st.auto_exposure(source)
@@ -53,6 +65,8 @@ elif bloom is not None:
     host.write_png(out, st.display_bloomed_srgb8(source, exposure, bloom))
 elif exposure is not None:
     host.write_png(out, st.display_exposed_srgb8(source, exposure))
+elif dof:
+    host.write_png(out, st.display_exposed_srgb8(source, 1.0))  # (exposure 1: the bytes of the plain display pass)
 else:
     host.write_png(out, st.denoised_display_srgb8() if denoise else st.display_srgb8())
 g = st.stats(); print(name, 'kernel ms', g['kernel_ms'], 'rays', g['ext_rays'] + g['shadow_rays'])
