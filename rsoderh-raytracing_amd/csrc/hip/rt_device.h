@@ -742,14 +742,17 @@ RT_DEV V3 sample_ggx_visible_half_vector(float sx, float sy, V3 wo, float alpha)
 }
 // bsdf_eval_local and bsdf_pdf_local (shader.wgsl:1053-1114) in one pass: they share h, D and G1(wo);
 // every expression is the one the two separate functions evaluate.
-RT_DEV void bsdf_eval_pdf_local(V3 wo, V3 wi, const BsdfMaterial &m, V3 &f, float &pdf)
+// (g1_o = g1_ggx(wo.z, m.alpha): a caller that evaluates twice at one vertex — the NEE direction and the sampled one — forms it once)
+// (ONE_D: the pdf's d_ggx(h.z) is the evaluation's D wherever saturate left h.z as it is — all but a normalised z a last place above 1, and
+// NaN — and is formed again only there; the flat kernel only, the walks have no register for the longer life of D: tests/test_code_object.py)
+template <bool ONE_D = false>
+RT_DEV void bsdf_eval_pdf_local(V3 wo, V3 wi, const BsdfMaterial &m, float g1_o, V3 &f, float &pdf)
 {
     if (wo.z <= 0.0f || wi.z <= 0.0f) { f = v3(0, 0, 0); pdf = 0.0f; return; }
     const V3 h = normalize(wo + wi);
-    const float g1_o = g1_ggx(wo.z, m.alpha);
+    const float ndh = saturate(h.z);
+    const float D = d_ggx(ndh, m.alpha);
     {
-        const float ndh = saturate(h.z);
-        const float D = d_ggx(ndh, m.alpha);
         const float G = g1_o * g1_ggx(wi.z, m.alpha);
         const V3 F = f_schlick(m.f0, dot(h, wo));
         const V3 fs = (D * G) / (4.0f * wo.z * wi.z) * F;
@@ -762,11 +765,18 @@ RT_DEV void bsdf_eval_pdf_local(V3 wo, V3 wi, const BsdfMaterial &m, V3 &f, floa
         float pdf_spec;
         if (wo_dot_h <= 0.0f) pdf_spec = 0.0f;
         else {
-            const float hv = (h.z <= 0.0f) ? 0.0f : d_ggx(h.z, m.alpha) * g1_o * fmax_(0.0f, wo_dot_h_signed) / wo.z;
+            float D_h = D;
+            if (!ONE_D || !(ndh == h.z)) D_h = d_ggx(h.z, m.alpha);
+            const float hv = (h.z <= 0.0f) ? 0.0f : D_h * g1_o * fmax_(0.0f, wo_dot_h_signed) / wo.z;
             pdf_spec = hv / (4.0f * wo_dot_h);
         }
         pdf = m.diff_prob * pdf_cos + m.spec_prob * pdf_spec;
     }
+}
+RT_DEV void bsdf_eval_pdf_local(V3 wo, V3 wi, const BsdfMaterial &m, V3 &f, float &pdf)
+{
+    if (wo.z <= 0.0f || wi.z <= 0.0f) { f = v3(0, 0, 0); pdf = 0.0f; return; }
+    bsdf_eval_pdf_local(wo, wi, m, g1_ggx(wo.z, m.alpha), f, pdf);
 }
 
 struct BsdfSample {
@@ -775,7 +785,9 @@ struct BsdfSample {
 };
 // `frame` = make_frame(n) and `wo` = to_frame_local(frame, -ray_dir): callers that already have them
 // (the NEE evaluation uses the same two) pass them in; the values are what the shader recomputes.
-RT_DEV BsdfSample bsdf_sample_in_frame(V3 ray_dir, V3 n, const Frame &frame, V3 wo, const BsdfMaterial &m, uint32_t &rng) // :1116-1202
+// (g1_o as in bsdf_eval_pdf_local; read only where wo.z > 0)
+template <bool ONE_D = false>
+RT_DEV BsdfSample bsdf_sample_in_frame(V3 ray_dir, V3 n, const Frame &frame, V3 wo, const BsdfMaterial &m, float g1_o, uint32_t &rng) // :1116-1202
 {
     V3 wo_world = -ray_dir;
     if (dot(n, wo_world) <= 0.0f) return BsdfSample{v3(0, 0, 0), v3(0, 0, 1), 0.0f};
@@ -799,10 +811,14 @@ RT_DEV BsdfSample bsdf_sample_in_frame(V3 ray_dir, V3 n, const Frame &frame, V3 
     RT_MARK2(14);
     V3 scattering;
     float pdf;
-    bsdf_eval_pdf_local(wo, wi, m, scattering, pdf);
+    bsdf_eval_pdf_local<ONE_D>(wo, wi, m, g1_o, scattering, pdf);
     V3 wi_world = to_frame_world(frame, wi);
     if (dot(n, wi_world) < 0.0f) return BsdfSample{v3(0, 0, 0), v3(0, 1, 0), 0.0f};
     return BsdfSample{wi_world, scattering, pdf};
+}
+RT_DEV BsdfSample bsdf_sample_in_frame(V3 ray_dir, V3 n, const Frame &frame, V3 wo, const BsdfMaterial &m, uint32_t &rng)
+{
+    return bsdf_sample_in_frame(ray_dir, n, frame, wo, m, wo.z > 0.0f ? g1_ggx(wo.z, m.alpha) : 0.0f, rng);
 }
 RT_DEV BsdfSample bsdf_sample(V3 ray_dir, V3 n, const BsdfMaterial &m, uint32_t &rng)
 {

@@ -532,19 +532,24 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 const Frame frame = make_frame(surf.normal); // shader.wgsl:1252 and :1133 build the same frame
                 const V3 wo = to_frame_local(frame, -d);
                 V3 nee = v3(0.0f, 0.0f, 0.0f);
+                // Flat kernel: G1(wo) is the same number in the NEE evaluation and in the evaluation of the sampled direction (same operands), so it
+                // is formed once for both, and either evaluation forms its D once (rt_device.h, ONE_D): a square root, three IEEE divisions and an
+                // exact reciprocal less a vertex.  (Not for the walks: the longer live ranges push them into scratch — tests/test_code_object.py.)
+                const float g1_o = kRngHot ? g1_ggx(wo.z, mat.alpha) : 0.0f;
                 if (want_shadow) { // what :1247-1249 adds if the shadow ray comes back unoccluded
                     RT_MARK2(5);
                     DBG_WAVE_TICK(23); DBG_ADD(24, 1);
                     const V3 wi = to_frame_local(frame, es.direction);
                     V3 scattering;
                     float pdf_bsdf;
-                    bsdf_eval_pdf_local(wo, wi, mat, scattering, pdf_bsdf);
+                    if (kRngHot) bsdf_eval_pdf_local<true>(wo, wi, mat, g1_o, scattering, pdf_bsdf);
+                    else bsdf_eval_pdf_local(wo, wi, mat, scattering, pdf_bsdf);
                     const float w = power_heuristic(es.pdf, pdf_bsdf);
                     nee = T * w * es.radiance * scattering * cos_nee / es.pdf;
                 }
                 RT_MARK2(6);
                 SHADE_STAMP(13);
-                const BsdfSample bs = bsdf_sample_in_frame(d, surf.normal, frame, wo, mat, rng);
+                const BsdfSample bs = kRngHot ? bsdf_sample_in_frame<true>(d, surf.normal, frame, wo, mat, g1_o, rng) : bsdf_sample_in_frame(d, surf.normal, frame, wo, mat, rng);
                 RT_MARK2(15);
                 SHADE_STAMP(14);
                 bool finished = false, nee_counts = want_shadow;
