@@ -134,6 +134,23 @@ rsrt_status rsrt_upload_environment(rsrt_context *ctx, uint32_t slot, uint32_t w
  * that kept the default {1, self, 1/N}.  rsrt_upload_environment with alias == NULL uploads the texels and calls this. */
 rsrt_status rsrt_environment_build_alias(rsrt_context *ctx, uint32_t slot, rsrt_alias_entry *host_out, size_t n_entries,
                                          uint32_t *leftover_out);
+/* A procedural daylight sky written straight into `slot`, ON THE DEVICE: Preetham's analytic sky with a sun disc (the model, its
+ * parameters' defaults and every bit of its arithmetic are published in include/rsrt_sky.h; rsrt_sky_params is in rsrt_types.h).
+ * One kernel fills the width x height texels (alpha 0, as uploaded maps have), the device builder above makes the alias table;
+ * neither texels nor table cross the bus.  The texels equal rsrt_sky_fill's (rsrt_host.h) bit for bit, so the slot renders exactly
+ * as if they and the host builder's table had been uploaded.  The contract is rsrt_upload_environment's: slots 0 .. 63, a filled
+ * slot is replaced whatever the two sizes, every call — a refused one included — drops the temporal history first thing, the
+ * accumulator is never touched, and a REFUSED call (NULL params, params rsrt_sky_params_ok refuses: a non-finite field, sun_elevation
+ * outside 1 .. 90 degrees, turbidity outside 2 .. 10, a negative ground_albedo, scale, sun_illuminance or sun_radius, sun_radius >
+ * 0.1, flags not 0; a zero size; more than 2^31 - 1 texels; slot > 63: all RSRT_ERR_INVALID_ARGUMENT) leaves every slot as it was.
+ * Moving the sun is one more call with another sun_azimuth / sun_elevation.
+ * Rust: pub fn rsrt_environment_sky(ctx: *mut RsrtContext, slot: u32, width: u32, height: u32, params: *const RsrtSkyParams) -> i32; */
+rsrt_status rsrt_environment_sky(rsrt_context *ctx, uint32_t slot, uint32_t width, uint32_t height, const rsrt_sky_params *params);
+/* Waits and copies the texels of `slot` to the host, width*height*4 f32, for a sky and an uploaded map alike: the colours as they
+ * went in, alpha 0 (the alpha an upload carried is ignored, see above).  RSRT_ERR_NOT_READY for an empty slot,
+ * RSRT_ERR_INVALID_ARGUMENT for NULL or another n_floats.
+ * Rust: pub fn rsrt_environment_download(ctx: *mut RsrtContext, slot: u32, host_rgba: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_environment_download(rsrt_context *ctx, uint32_t slot, float *host_rgba, size_t n_floats);
 
 /* build_bvh (src/bvh.rs:13-337) ON THE DEVICE (csrc/hip/rt_bvh_device.h): the arguments and outputs of the host
  * builder rsrt_build_bvh (rsrt_host.h) — host arrays in, host arrays out: primitives_out holds n_spheres + n_planes + n_triangles

@@ -18,6 +18,8 @@
  *   rsrt_write_png/_pfm      image output (the reference only presents to a window)
  *   rsrt_synth_environment   stand-in for the two HDRIs the checkout lacks (state.rs:119-122;
  *                            .MISSING_LARGE_BLOBS) — deterministic formula, DESIGN.md §env
+ *   rsrt_sky_fill            the procedural daylight sky of include/rsrt_sky.h on the CPU (no reference counterpart;
+ *                            rsrt_environment_sky in rsrt.h fills a slot with the same bits on the device), DESIGN.md §19
  */
 #ifndef RSRT_HOST_H
 #define RSRT_HOST_H
@@ -76,6 +78,11 @@ int rsrt_alias_table_build(uint32_t width, uint32_t height, const float *rgb, rs
 
 /* Deterministic synthetic equirectangular sky (gradient + sun lobe); rgba_out: w*h*4, alpha 0. */
 int rsrt_synth_environment(uint32_t width, uint32_t height, float *rgba_out);
+
+/* The daylight sky of include/rsrt_sky.h (Preetham's, with a sun disc) as an equirectangular map; rgba_out: w*h*4, alpha 0.  Returns
+ * non-zero for NULL arguments, a zero size or parameters rsrt_sky_params_ok refuses, and then writes nothing.
+ * Rust: pub fn rsrt_sky_fill(width: u32, height: u32, params: *const RsrtSkyParams, rgba_out: *mut f32) -> i32; */
+int rsrt_sky_fill(uint32_t width, uint32_t height, const rsrt_sky_params *params, float *rgba_out);
 
 /* Radiance RGBE (.hdr): rgb_out = malloc'ed width*height*3 f32, rows top to bottom; free with rsrt_free.
  * value = mantissa * 2^(e-136), (0,0,0) when e == 0 — the `image` 0.25 hdr decoder's rule. */

@@ -8,6 +8,7 @@
 #include <functional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "rsrt.h"
@@ -16,6 +17,7 @@
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
 #include "rsrt_local.h"
+#include "rsrt_sky.h"
 
 namespace rsrt {
 
@@ -61,6 +63,16 @@ struct Environment {
         e.build_alias();
         return e;
     }
+    // the procedural daylight sky (rsrt_sky.h) on the CPU with the host alias table: what State::environment_sky builds on the device
+    static Environment sky(uint32_t w, uint32_t h, const rsrt_sky_params &p)
+    {
+        Environment e;
+        e.width = w; e.height = h;
+        e.rgba.resize((size_t)w * h * 4);
+        if (rsrt_sky_fill(w, h, &p, e.rgba.data()) != 0) throw Error("rsrt_sky_fill refused the size or the parameters");
+        e.build_alias();
+        return e;
+    }
     static Environment from_hdr(const std::string &path)
     {
         Environment e;
@@ -99,9 +111,11 @@ public:
                                           c.n_planes, rsrt_scene_vertices(s), c.n_vertices, rsrt_scene_normals(s), c.n_normals,
                                           rsrt_scene_triangles(s), c.n_triangles, rsrt_scene_primitives(s), c.n_primitives, rsrt_scene_bvh_nodes(s),
                                           c.n_bvh_nodes));
-            for (size_t i = 0; i < environments.size(); i++)
+            for (size_t i = 0; i < environments.size(); i++) {
                 check(rsrt_multi_upload_environment(m_, (uint32_t)i, environments[i]->width, environments[i]->height, environments[i]->rgba.data(),
                                                     environments[i]->alias.data()));
+                remember_environment((uint32_t)i, environments[i]->width, environments[i]->height);
+            }
             camera_ = scene.camera();
             resize(width, height);
         } catch (...) {
@@ -435,6 +449,30 @@ public:
     }
     float focus_distance() const { return focus_distance_; } // the remembered focus distance (0: none)
     void dof_reset() { check_ctx(rsrt_dof_reset(context(0))); } // drops the lens image
+    // -- the procedural sky (rsrt.h rsrt_environment_sky, rsrt_sky.h) -----------------------------------------------------------
+    static rsrt_sky_params sky_defaults()
+    {
+        return rsrt_sky_params{RSRT_SKY_SUN_AZIMUTH, RSRT_SKY_SUN_ELEVATION, RSRT_SKY_TURBIDITY, {RSRT_SKY_GROUND_ALBEDO, RSRT_SKY_GROUND_ALBEDO, RSRT_SKY_GROUND_ALBEDO},
+                               RSRT_SKY_SCALE, RSRT_SKY_SUN_ILLUMINANCE, RSRT_SKY_SUN_RADIUS, RSRT_SKY_FLAGS};
+    }
+    // fills environment `slot` with the sky of p and builds its alias table, on every device of the State (each makes the same bits);
+    // replaces what the slot held and, like an upload, drops the temporal history
+    void environment_sky(uint32_t slot, uint32_t width = 2048, uint32_t height = 1024, const rsrt_sky_params &p = sky_defaults())
+    {
+        for (uint32_t i = 0; i < device_count(); i++)
+            if (rsrt_environment_sky(context(i), slot, width, height, &p) != RSRT_OK) throw Error(rsrt_last_error(context(i)));
+        remember_environment(slot, width, height);
+    }
+    // the texels of environment `slot` (a sky or an upload), width * height * 4 f32 with alpha 0, from device 0; the size where asked for
+    std::vector<float> environment_download(uint32_t slot, uint32_t *width = nullptr, uint32_t *height = nullptr)
+    {
+        const uint32_t w = slot < env_sizes_.size() ? env_sizes_[slot].first : 0u, h = slot < env_sizes_.size() ? env_sizes_[slot].second : 0u;
+        std::vector<float> out((size_t)w * h * 4);
+        check_ctx(rsrt_environment_download(context(0), slot, out.data(), out.size()));
+        if (width) *width = w;
+        if (height) *height = h;
+        return out;
+    }
     // -- the temporal pass (rsrt.h "temporal pass"): one device, like the denoiser ---------------------------------
     static rsrt_temporal_params temporal_defaults() { return rsrt_temporal_params{32u, 0.05f, 0.9f}; }
     // one displayed frame: clear the accumulator and the AOV buffer, render samples [k, k + n) of the current camera with the AOV pass
@@ -529,6 +567,12 @@ private:
         bytes.append(reinterpret_cast<const char *>(&environment_index), sizeof environment_index);
         return std::hash<std::string>()(bytes);
     }
+    void remember_environment(uint32_t slot, uint32_t width, uint32_t height)
+    {
+        if (env_sizes_.size() <= slot) env_sizes_.resize(slot + 1, {0u, 0u});
+        env_sizes_[slot] = {width, height};
+    }
+    std::vector<std::pair<uint32_t, uint32_t>> env_sizes_; // slot -> the size of what the constructor or environment_sky put there
     rsrt_multi *m_ = nullptr;
     rsrt_camera_desc camera_{};
     uint32_t width_ = 0, height_ = 0, sample_count_ = 0, aov_sample_count_ = 0;

@@ -103,6 +103,20 @@ typedef struct rsrt_plane_desc {
     uint32_t material_id;
 } rsrt_plane_desc;
 
+/* The procedural daylight sky (rsrt_environment_sky in rsrt.h, rsrt_sky_fill in rsrt_host.h; the model is include/rsrt_sky.h): 40
+ * bytes.  Angles in radians; the azimuth is the equirectangular map's own phi (atan2(z, x) of the direction), the elevation is
+ * measured from the horizon towards +y.  Defaults: RSRT_SKY_* in include/rsrt_sky.h. */
+typedef struct rsrt_sky_params {
+    float sun_azimuth;
+    float sun_elevation;   /* 1 .. 90 degrees */
+    float turbidity;       /* 2 .. 10 */
+    float ground_albedo[3];
+    float scale;           /* multiplies everything */
+    float sun_illuminance; /* klx above the atmosphere; 0: no disc */
+    float sun_radius;      /* radians, at most 0.1 */
+    uint32_t flags;        /* must be 0 */
+} rsrt_sky_params;
+
 #ifdef __cplusplus
 }
 #endif

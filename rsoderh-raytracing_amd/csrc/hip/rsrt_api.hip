@@ -2450,3 +2450,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_bloom.h"
 #include "rt_local.h"
 #include "rt_dof.h"
+#include "rt_sky.h"

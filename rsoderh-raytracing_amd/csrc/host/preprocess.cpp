@@ -1,10 +1,11 @@
-// preprocess.cpp — alias table, plane / camera uniforms, synthetic environment.
+// preprocess.cpp — alias table, plane / camera uniforms, synthetic environment, procedural sky.
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "../../../include/rsrt_detmath.h"
 #include "../../../include/rsrt_host.h"
+#include "../../../include/rsrt_sky.h"
 #include "host_math.h"
 
 using namespace rsrt_host;
@@ -156,6 +157,26 @@ extern "C" int rsrt_synth_environment(uint32_t width, uint32_t height, float *rg
             o[0] = r + sun * 1.0f;
             o[1] = g + sun * 0.95f;
             o[2] = b + sun * 0.85f;
+            o[3] = 0.0f;
+        }
+    }
+    return 0;
+}
+
+// The daylight sky (include/rsrt_sky.h): the constants once, a row's and a column's shares once each, then the per-texel function —
+// the order rt_sky_fill_kernel (csrc/hip/rt_sky.h) works in, and the same bits.
+extern "C" int rsrt_sky_fill(uint32_t width, uint32_t height, const rsrt_sky_params *params, float *rgba_out)
+{
+    if (!rgba_out || !params || width == 0 || height == 0 || !rsrt_sky_params_ok(params)) return 1;
+    rsrt_sky_constants k;
+    rsrt_sky_prepare(params, height, &k);
+    std::vector<rsrt_sky_col> cols(width);
+    for (uint32_t x = 0; x < width; x++) cols[x] = rsrt_sky_col_of(x, width);
+    for (uint32_t y = 0; y < height; y++) {
+        const rsrt_sky_row row = rsrt_sky_row_of(&k, y, height);
+        for (uint32_t x = 0; x < width; x++) {
+            float *o = rgba_out + 4 * ((size_t)y * width + x);
+            rsrt_sky_texel(&k, row, cols[x], o);
             o[3] = 0.0f;
         }
     }

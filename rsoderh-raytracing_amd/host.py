@@ -32,6 +32,8 @@ def lib():
         L.rsrt_build_bvh.restype = C.c_int
         L.rsrt_alias_table_build.restype = C.c_int
         L.rsrt_synth_environment.restype = C.c_int
+        L.rsrt_sky_fill.restype = C.c_int
+        L.rsrt_sky_fill.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rsrt_load_hdr.restype = C.c_int
         L.rsrt_load_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         L.rsrt_free.argtypes = [C.c_void_p]
@@ -170,6 +172,17 @@ def synth_environment(width, height):
     return out
 
 
+def sky_fill(width, height, **params):
+    """rsrt_sky_fill: the procedural daylight sky of include/rsrt_sky.h on the CPU, [H, W, 4] float32, alpha 0 — the texels
+    State.environment_sky makes on the device, bit for bit.  params: state.SKY_DEFAULTS' names; refused ones raise ValueError."""
+    from .state import SkyParams  # (state imports nothing from here)
+    p = SkyParams.of(**params)
+    out = np.zeros((height, width, 4), np.float32)
+    if width <= 0 or height <= 0 or lib().rsrt_sky_fill(width, height, C.byref(p), _p(out)) != 0:
+        raise ValueError("rsrt_sky_fill refused: a zero size, or parameters rsrt_sky_params_ok (include/rsrt_sky.h) does not accept")
+    return out
+
+
 class Environment:
     """One HDRI + its alias table, as `EnvironmentMaps::new` prepares it (src/environments.rs:19-64)."""
 
@@ -184,6 +197,10 @@ class Environment:
     def synthetic(cls, width=2048, height=1024):
         return cls(synth_environment(width, height))
 
+    @classmethod
+    def sky(cls, width=2048, height=1024, **params):
+        """The procedural daylight sky (sky_fill) with the host alias table: what State.environment_sky builds on the device."""
+        return cls(sky_fill(width, height, **params))
 
     @classmethod
     def load_hdr(cls, path):

@@ -39,7 +39,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_bloom", "rsrt_bloom_download", "rsrt_bloom_reset", "rsrt_display_bloomed_srgb8",
             "rsrt_local_exposure", "rsrt_local_exposure_download", "rsrt_local_exposure_reset", "rsrt_local_gain_download",
             "rsrt_display_local_srgb8",
-            "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset"]
+            "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset",
+            "rsrt_environment_sky", "rsrt_environment_download"]
 
 
 class RsrtError(RuntimeError):
@@ -135,6 +136,27 @@ DOF_DEFAULTS = {"focus_distance": 1.0, "aperture": 0.01, "max_radius": 8, "flags
 
 class DofParams(C.Structure):
     _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# the procedural daylight sky (include/rsrt.h rsrt_environment_sky, include/rsrt_sky.h): its defaults (RSRT_SKY_*) and its parameters.
+# Angles in radians; the elevation's range is 1 .. 90 degrees, the turbidity's 2 .. 10
+SKY_DEFAULTS = {"sun_azimuth": 0.0, "sun_elevation": 0.78539816339744830962, "turbidity": 3.0, "ground_albedo": (0.2, 0.2, 0.2), "scale": 1.0 / 64,
+                "sun_illuminance": 128.0, "sun_radius": 0.00465, "flags": 0}
+
+
+class SkyParams(C.Structure):
+    _fields_ = [("sun_azimuth", C.c_float), ("sun_elevation", C.c_float), ("turbidity", C.c_float), ("ground_albedo", C.c_float * 3),
+                ("scale", C.c_float), ("sun_illuminance", C.c_float), ("sun_radius", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, **params):
+        """SKY_DEFAULTS with `params` over them; an unknown name is a TypeError."""
+        unknown = set(params) - set(SKY_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown sky parameter(s): " + ", ".join(sorted(unknown)))
+        p = dict(SKY_DEFAULTS, **params)
+        return cls(p["sun_azimuth"], p["sun_elevation"], p["turbidity"], (C.c_float * 3)(*p["ground_albedo"]), p["scale"], p["sun_illuminance"],
+                   p["sun_radius"], p["flags"])
 
 
 class TemporalParams(C.Structure):
@@ -272,6 +294,8 @@ def lib():
         L.rsrt_dof_coc_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_dof_depth_at.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_dof_reset.argtypes = [C.c_void_p]
+        L.rsrt_environment_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_environment_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -303,6 +327,7 @@ class State:
         self._guide_bound = False
         self.exposure = None            # the last auto_exposure() (None: none since exposure_reset)
         self.focus_distance = None      # the last focus_at() that hit a surface (None: depth_of_field takes DOF_DEFAULTS')
+        self._env_sizes = {}            # slot -> (width, height) of what upload_environment / environment_sky put there
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -351,6 +376,25 @@ class State:
         assert rgba.shape == (env.height, env.width, 4) and alias.dtype.itemsize == 16 and len(alias) == env.width * env.height
         self._check(self._L.rsrt_upload_environment(self._ctx, slot, env.width, env.height, _p(rgba), _p(alias)),
                     "rsrt_upload_environment")
+        self._env_sizes[slot] = (env.width, env.height)
+
+    def environment_sky(self, slot, width=2048, height=1024, **params):
+        """rsrt_environment_sky: fills `slot` with the procedural daylight sky of `params` (SKY_DEFAULTS otherwise: sun_azimuth,
+        sun_elevation in radians, turbidity, ground_albedo, scale, sun_illuminance, sun_radius) and builds its alias table, all on the
+        device.  Like upload_environment it replaces what the slot held, drops the temporal history and leaves the accumulator alone
+        (clear() restarts a progressive picture); a refused call changes no slot.  host.Environment.sky gives the same texels on the
+        CPU."""
+        p = SkyParams.of(**params)
+        self._check(self._L.rsrt_environment_sky(self._ctx, slot, width, height, C.byref(p)), "rsrt_environment_sky")
+        self._env_sizes[slot] = (width, height)
+
+    def environment_download(self, slot, width=None, height=None):
+        """rsrt_environment_download: the texels of `slot`, [H, W, 4] float32 with alpha 0, whether a sky or an upload filled it.  The
+        size is the one this State put there; give width and height for a slot filled behind its back."""
+        w, h = (width, height) if width and height else self._env_sizes.get(slot, (0, 0))
+        out = np.empty((h, w, 4), np.float32)
+        self._check(self._L.rsrt_environment_download(self._ctx, slot, _p(out), out.size), "rsrt_environment_download")
+        return out
 
     def set_partition(self, rank, world_size, tile_w=16, tile_h=16):
         self._check(self._L.rsrt_set_partition(self._ctx, rank, world_size, tile_w, tile_h), "rsrt_set_partition")

@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -10,7 +10,10 @@ display image at its exposure, with the default or the given strengths and, with
 dof=FOCUS,APERTURE[,RADIUS]: State.depth_of_field of the picture (the AOV pass over the same samples gives the depths) focused at FOCUS
 scene units along the axis (auto: at the depth of the picture's centre, State.focus_at), with APERTURE the blur radius of a point at
 infinity as a fraction of the picture's height and at most RADIUS pixels (default 8); it runs before exposure=, bloom= and local=, which
-then meter, bloom and grade the lens image."""
+then meter, bloom and grade the lens image.
+sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]: environment 0 is the procedural daylight sky (State.environment_sky, 2048 x 1024, built on the
+device: no map is prepared on the host) with the sun at that elevation and azimuth in degrees, instead of the synthetic map; it
+composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -27,10 +30,18 @@ local = next((a[len("local="):] for a in sys.argv[1:] if a.startswith("local="))
 if local is not None:
     local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
 dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof="))]
+sky = next((a[len("sky="):].split(",") for a in sys.argv[1:] if a.startswith("sky=")), None)
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "sky="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
-st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
+if sky:
+    import math
+    st = R.State.new(sc, [], w, h); st.max_bounces = mb
+    turbidity = float(sky[2]) if len(sky) > 2 else R.state.SKY_DEFAULTS["turbidity"]
+    st.environment_sky(0, 2048, 1024, sun_elevation=math.radians(float(sky[0])), sun_azimuth=math.radians(float(sky[1])), turbidity=turbidity)
+    print("sky: sun at elevation %g degrees, azimuth %g degrees, turbidity %g (2048x1024, built on the device)" % (float(sky[0]), float(sky[1]), turbidity))
+else:
+    st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
 if args[3].startswith("noise="):
     target = args[3][len("noise="):].split(",")
     spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024, exposure=exposure,
