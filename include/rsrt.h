@@ -747,6 +747,11 @@ rsrt_status rsrt_get_walk_counters(rsrt_context *ctx, uint64_t *out, uint32_t n)
  * out[2] = of those, how many the bare v_rcp_f32 gets wrong (shows the comparison is live), out[3] = smallest
  * failing bit pattern or UINT64_MAX. */
 rsrt_status rsrt_selftest_numerics(rsrt_context *ctx, uint64_t out[4]);
+/* Exhaustive device self-test of rsrt_sincosf (rsrt_detmath.h), the fused form the render kernels take the sine and cosine
+ * of one angle with, against rsrt_sinf and rsrt_cosf, as bits, over all 2^32 f32 bit patterns (~0.2 s).  out[0] = inputs where
+ * either result differs (must be 0), out[1] = inputs checked (2^32), out[2] = 0, out[3] = smallest failing bit pattern or
+ * UINT64_MAX. */
+rsrt_status rsrt_selftest_sincos(rsrt_context *ctx, uint64_t out[4]);
 
 /* Library / device description, for logs: "librsrt <version>; <device name>; <CUs> CUs". */
 const char *rsrt_describe(rsrt_context *ctx);

@@ -93,6 +93,30 @@ RSRT_HD float rsrt_cosf(float x)
     return neg ? -v : v;
 }
 
+/* sin and cos of ONE angle in one pass: *s has the bits of rsrt_sinf(x) and *c the bits of rsrt_cosf(x) for every float
+ * (NaN, +-inf, |x| > 8192, +-0 and subnormals included; tests/test_sincos.py, rsrt_selftest_sincos).  The two functions above
+ * perform the same reduction on the same operands and each evaluates one of the two polynomials, the other function the other
+ * one: here the reduction and either polynomial are evaluated once, and every f32 operation is one of theirs on the same
+ * operands.  After j += j & 1 the octant j & 7 is 0, 2, 4 or 6: bit 2 is the "j > 3" of both functions (both signs flip), and
+ * bit 1 is what remains after their j -= 4, where "j == 1 || j == 2" and the cosine's "j > 1" are both j == 2 (the polynomials
+ * change places, the cosine's sign flips).  Plain selects, no data-dependent branch beyond the range check. */
+RSRT_HD void rsrt_sincosf(float x, float *s, float *c)
+{
+    float ax = x < 0.0f ? -x : x;
+    if (!(ax <= 8192.0f)) { *s = x - x; *c = x - x; return; }
+    uint32_t j = (uint32_t)(ax * RSRT_FOPI);
+    j += (j & 1u);
+    float y = (float)j;
+    float r = ((ax - y * RSRT_DP1) - y * RSRT_DP2) - y * RSRT_DP3;
+    float z = r * r;
+    const float ps = rsrt_sin_poly(r, z), pc = rsrt_cos_poly(z);
+    const bool half = (j & 4u) != 0u, swap = (j & 2u) != 0u;
+    const bool sneg = (x < 0.0f) != half, cneg = half != swap;
+    const float sv = swap ? pc : ps, cv = swap ? ps : pc;
+    *s = sneg ? -sv : sv;
+    *c = cneg ? -cv : cv;
+}
+
 #define RSRT_PIF 3.14159265358979323846f
 #define RSRT_PIO2F 1.57079632679489661923f
 #define RSRT_PIO4F 0.78539816339744830962f

@@ -4,6 +4,7 @@
 // src/state.rs:775-794), plus the batched render the C-ABI adds.  Errors become rsrt::Error (the
 // reference's anyhow::Error / unwrap at init).
 #pragma once
+#include <array>
 #include <cstring>
 #include <functional>
 #include <stdexcept>
@@ -549,6 +550,13 @@ public:
         rsrt_stats s;
         check(rsrt_multi_get_stats(m_, &s));
         return s;
+    }
+    // rsrt_selftest_sincos on the first device: {mismatches (must be 0), inputs checked (2^32), 0, first failing pattern or UINT64_MAX}
+    std::array<uint64_t, 4> selftest_sincos()
+    {
+        std::array<uint64_t, 4> out{};
+        check_ctx(rsrt_selftest_sincos(context(0), out.data()));
+        return out;
     }
     rsrt_context *context(uint32_t i = 0) { return rsrt_multi_context(m_, i); }
 

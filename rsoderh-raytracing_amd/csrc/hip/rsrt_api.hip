@@ -139,7 +139,8 @@ __device__ __forceinline__ void start_path(const RenderParams &P, uint32_t px, u
     salt_rng(rng, pixel_index);
     salt_rng(rng, sample);
     float angle = random_uniform(rng) * 2.0f * 3.1415926f; // random_in_circle_uniform :627-631
-    float cx = rsrt_cosf(angle), cy = rsrt_sinf(angle);
+    float cx, cy;
+    rt_sincos(angle, cy, cx);
     float rad = rsrt_sqrtf(random_uniform(rng));
     float fx = (float)px + cx * rad, fy = (float)py + cy * rad;
     float sx = ((fx / (float)P.width) * 2.0f - 1.0f) * 1.0f;
@@ -2318,7 +2319,26 @@ __global__ void rt_selftest_rcp_kernel(unsigned long long *out)
     atomicAdd(&out[2], raw_differs);
 }
 
-rsrt_status rsrt_selftest_numerics(rsrt_context *ctx, uint64_t out[4])
+// Exhaustive check of rsrt_sincosf against rsrt_sinf and rsrt_cosf, as bits, all 2^32 bit patterns.
+__global__ void rt_selftest_sincos_kernel(unsigned long long *out)
+{
+    unsigned long long bad = 0, checked = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (1ull << 32); i += stride) {
+        const float x = as_f((uint32_t)i);
+        float s, c;
+        rsrt_sincosf(x, &s, &c);
+        checked++;
+        if (as_u(s) != as_u(rsrt_sinf(x)) || as_u(c) != as_u(rsrt_cosf(x))) {
+            bad++;
+            atomicMin(&out[3], (unsigned long long)i);
+        }
+    }
+    atomicAdd(&out[0], bad);
+    atomicAdd(&out[1], checked);
+}
+
+static rsrt_status run_selftest(rsrt_context *ctx, void (*kernel)(unsigned long long *), uint64_t out[4])
 {
     if (!ctx || !out) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
@@ -2327,7 +2347,7 @@ rsrt_status rsrt_selftest_numerics(rsrt_context *ctx, uint64_t out[4])
     HIP_TRY(ctx, hipMalloc(&d, sizeof h));
     hipError_t e = hipMemcpy(d, h, sizeof h, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(rt_selftest_rcp_kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream, d);
+        hipLaunchKernelGGL(kernel, dim3(ctx->cus * 8), dim3(256), 0, ctx->stream, d);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -2337,6 +2357,9 @@ rsrt_status rsrt_selftest_numerics(rsrt_context *ctx, uint64_t out[4])
     for (int i = 0; i < 4; i++) out[i] = h[i];
     return RSRT_OK;
 }
+
+rsrt_status rsrt_selftest_numerics(rsrt_context *ctx, uint64_t out[4]) { return run_selftest(ctx, rt_selftest_rcp_kernel, out); }
+rsrt_status rsrt_selftest_sincos(rsrt_context *ctx, uint64_t out[4]) { return run_selftest(ctx, rt_selftest_sincos_kernel, out); }
 
 rsrt_status rsrt_get_debug_counters(rsrt_context *ctx, uint64_t out[32])
 {

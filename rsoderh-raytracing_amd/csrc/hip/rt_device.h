@@ -486,18 +486,35 @@ RT_DEV void direction_to_equirectangular_uv(V3 d, float &u, float &v) // :710-71
     u = rsrt_atan2f(d.z, d.x) * RT_INV_PI * 0.5f + 0.5f;
     v = 0.5f - rsrt_asinf(d.y) * RT_INV_PI;
 }
-RT_DEV V3 equirectangular_uv_to_direction(float u, float v) // :718-732
+RT_DEV V3 equirectangular_uv_to_direction(float u, float v, float &sin_theta) // :718-732
 {
     float phi = (2.0f * u - 1.0f) * RT_PI;
     float theta = RT_PI * v;
-    float st = rsrt_sinf(theta), ct = rsrt_cosf(theta);
-    return v3(st * rsrt_cosf(phi), ct, st * rsrt_sinf(phi));
+    float st, ct, sp, cp; // (either angle feeds a sine and a cosine: one reduction and one pair of polynomials each, rsrt_sincosf)
+    rt_sincos(theta, st, ct);
+    rt_sincos(phi, sp, cp);
+    sin_theta = st;
+    return v3(st * cp, ct, st * sp);
 }
-RT_DEV float environment_pixel_solid_angle(float v, const DevEnv &e) // :739-749
+RT_DEV V3 equirectangular_uv_to_direction(float u, float v)
+{
+    float sin_theta;
+    return equirectangular_uv_to_direction(u, v, sin_theta);
+}
+// (sin_theta = rsrt_sinf(RT_PI * v), which a caller that has just turned the same v into a direction holds already:
+// equirectangular_uv_to_direction forms theta by the same expression from the same v, so the operands and therefore the bits are the same)
+struct SinTheta {
+    float value;
+};
+RT_DEV float environment_pixel_solid_angle(SinTheta sin_theta, const DevEnv &e) // :739-749
+{
+    float sin_t = fmax_(1.0e-6f, sin_theta.value);
+    return e.dphi_dtheta * sin_t; // (d_phi * d_theta) * sin_t
+}
+RT_DEV float environment_pixel_solid_angle(float v, const DevEnv &e)
 {
     float theta = RT_PI * v;
-    float sin_t = fmax_(1.0e-6f, rsrt_sinf(theta));
-    return e.dphi_dtheta * sin_t; // (d_phi * d_theta) * sin_t
+    return environment_pixel_solid_angle(SinTheta{rsrt_sinf(theta)}, e);
 }
 // Environment gathers (texels, alias entries): 64 MiB of tables read at random, 128 bytes fetched per 16-byte record, default cache
 // policy (non-temporal gathers were measured in round 2, profiles/r02_l2_sweep.txt: L2 hit rate up, run time +3 .. +10 %)
@@ -623,12 +640,16 @@ RT_DEV EnvironmentSample sample_environment_finish(const DevEnv &e, uint32_t &rn
     float u = ((float)x + jx) / e.wf;
     float v = ((float)y + jy) / e.hf;
     EnvironmentSample s;
-    s.direction = equirectangular_uv_to_direction(u, v);
+    float sin_theta;
+    s.direction = equirectangular_uv_to_direction(u, v, sin_theta);
     s.radiance = sample_env_bilinear(e, u, v);
     float pmf;
     if (PACKED) pmf = (pick == index) ? as_f(entry.z) : as_f(entry.w); // .w: the pmf of the alias target (rt_env_pack_alias_kernel)
     else pmf = (pick == index) ? as_f(entry.z) : as_f(env_alias(e, pick).z);
-    s.pdf = pmf / environment_pixel_solid_angle(v, e);
+    // (the flat kernel keeps the sine of the same RT_PI * v that the direction was made of; the walks form it again — one more live
+    // register puts the wide walk's global form <0, 256, 160, 5> into scratch, 12 bytes: tests/test_code_object.py)
+    if (PACKED) s.pdf = pmf / environment_pixel_solid_angle(SinTheta{sin_theta}, e);
+    else s.pdf = pmf / environment_pixel_solid_angle(v, e);
     return s;
 }
 RT_DEV EnvironmentSample sample_environment(const DevEnv &e, uint32_t &rng)
@@ -717,15 +738,22 @@ RT_DEV float bsdf_pdf_local(V3 wo, V3 wi, const BsdfMaterial &m) // :1104-1114 w
     }
     return m.diff_prob * pdf_cos + m.spec_prob * pdf_spec;
 }
-RT_DEV V3 sample_cosine_hemisphere(float sx, float sy) // :892-901
+// (sin_phi, cos_phi: rt_sincos of phi = RT_TWO_PI * sy — bsdf_sample_in_frame forms the pair once for whichever lobe runs)
+RT_DEV V3 sample_cosine_hemisphere(float sx, float sin_phi, float cos_phi) // :892-901
 {
     float r = rsrt_sqrtf(sx);
-    float phi = RT_TWO_PI * sy;
-    float x = r * rsrt_cosf(phi), y = r * rsrt_sinf(phi);
+    float x = r * cos_phi, y = r * sin_phi;
     float z = rsrt_sqrtf(fmax_(0.0f, 1.0f - x * x - y * y));
     return v3(x, y, z);
 }
-RT_DEV V3 sample_ggx_visible_half_vector(float sx, float sy, V3 wo, float alpha) // :962-1009
+RT_DEV V3 sample_cosine_hemisphere(float sx, float sy)
+{
+    float sin_phi, cos_phi;
+    rt_sincos(RT_TWO_PI * sy, sin_phi, cos_phi);
+    return sample_cosine_hemisphere(sx, sin_phi, cos_phi);
+}
+// (sin_az, cos_az: rt_sincos of az = RT_TWO_PI * sy, likewise)
+RT_DEV V3 sample_ggx_visible_half_vector(float sx, float sin_az, float cos_az, V3 wo, float alpha) // :962-1009
 {
     V3 vs = normalize(wo * v3(alpha, alpha, 1.0f));
     float len2 = dot2(vs.x, vs.y, vs.x, vs.y);
@@ -733,12 +761,17 @@ RT_DEV V3 sample_ggx_visible_half_vector(float sx, float sy, V3 wo, float alpha)
     V3 tx = (len2 > 0.0f) ? alt : v3(1, 0, 0);
     V3 ty = cross(vs, tx);
     float radius = rsrt_sqrtf(sx);
-    float az = RT_TWO_PI * sy;
-    float dx = radius * rsrt_cosf(az), dy = radius * rsrt_sinf(az);
+    float dx = radius * cos_az, dy = radius * sin_az;
     float a = rsrt_sqrtf(fmax_(0.0f, 1.0f - dx * dx));
     dy = (1.0f - vs.z) * a + vs.z * dy; // lerp_f32(a, dy, vs.z)
     V3 hs = dx * tx + dy * ty + rsrt_sqrtf(fmax_(0.0f, 1.0f - dx * dx - dy * dy)) * vs;
     return normalize(v3(alpha * hs.x, alpha * hs.y, fmax_(0.0f, hs.z)));
+}
+RT_DEV V3 sample_ggx_visible_half_vector(float sx, float sy, V3 wo, float alpha)
+{
+    float sin_az, cos_az;
+    rt_sincos(RT_TWO_PI * sy, sin_az, cos_az);
+    return sample_ggx_visible_half_vector(sx, sin_az, cos_az, wo, alpha);
 }
 // bsdf_eval_local and bsdf_pdf_local (shader.wgsl:1053-1114) in one pass: they share h, D and G1(wo);
 // every expression is the one the two separate functions evaluate.
@@ -794,16 +827,19 @@ RT_DEV BsdfSample bsdf_sample_in_frame(V3 ray_dir, V3 n, const Frame &frame, V3 
     if (wo.z <= 0.0f) return BsdfSample{v3(0, 0, 0), v3(0, 1, 0), 0.0f};
     V3 wi;
     float s = random_uniform(rng);
+    // Either lobe draws s1 as its second number and takes the sine and cosine of RT_TWO_PI * s1: drawn and formed once, ahead of the
+    // branch, for the lobe that runs (a wave that holds both lobes — the usual case — issued the pair twice).  Same draws in the same order.
+    float s1 = random_uniform(rng);
+    float sin_az, cos_az;
+    rt_sincos(RT_TWO_PI * s1, sin_az, cos_az);
     if (s < m.diff_prob) {
         RT_MARK2(12);
         float s0 = s / fmax_(m.diff_prob, 1.e-6f);
-        float s1 = random_uniform(rng);
-        wi = sample_cosine_hemisphere(s0, s1);
+        wi = sample_cosine_hemisphere(s0, sin_az, cos_az);
     } else {
         RT_MARK2(13);
         float s0 = (s - m.diff_prob) / fmax_(m.spec_prob, 1.e-6f);
-        float s1 = random_uniform(rng);
-        V3 h = sample_ggx_visible_half_vector(s0, s1, wo, m.alpha);
+        V3 h = sample_ggx_visible_half_vector(s0, sin_az, cos_az, wo, m.alpha);
         V3 i = -wo;
         wi = i - (2.0f * dot(h, i)) * h; // reflect(-wo, h)
         if (wi.z <= 0.0f) return BsdfSample{v3(1, 0, 0), v3(1, 0, 0), 0.0f};

@@ -135,6 +135,18 @@ RT_DEV V3 rt_rcp3(V3 d)
     return V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
 }
 
+// sin and cos of ONE angle: rsrt_sincosf (include/rsrt_detmath.h) gives the bits of rsrt_sinf and rsrt_cosf with one range reduction and
+// either polynomial evaluated once, selects instead of the two functions' divergent polynomial branches — some thirty VALU instructions
+// less a pair (profiles/sincos_ab.txt).
+RT_DEV void rt_sincos(float x, float &s, float &c)
+{
+#ifdef RT_FAST_NUMERICS
+    s = __sinf(x); c = __cosf(x);
+#else
+    rsrt_sincosf(x, &s, &c);
+#endif
+}
+
 RT_DEV float length(V3 a) { return rsrt_sqrtf(dot(a, a)); }
 RT_DEV V3 normalize(V3 a) { return a * rt_rcp(rsrt_sqrtf(dot(a, a))); }
 RT_DEV float inverse_sqrt(float x) { return rt_rcp(rsrt_sqrtf(x)); }

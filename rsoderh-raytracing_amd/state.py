@@ -25,7 +25,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_upload_environment", "rsrt_set_partition", "rsrt_accumulator_resize", "rsrt_accumulator_bind",
             "rsrt_accumulator_clear", "rsrt_accumulator_download", "rsrt_resolve_mean_f16", "rsrt_debug_view_f16", "rsrt_render",
             "rsrt_synchronize", "rsrt_get_stats", "rsrt_cast_rays", "rsrt_describe", "rsrt_get_debug_counters", "rsrt_get_region_counters", "rsrt_get_walk_counters", "rsrt_display_srgb8",
-            "rsrt_selftest_numerics", "rsrt_build_id", "rsrt_wide_tree_build", "rsrt_build_bvh_device",
+            "rsrt_selftest_numerics", "rsrt_selftest_sincos", "rsrt_build_id", "rsrt_wide_tree_build", "rsrt_build_bvh_device",
             "rsrt_partition_owner", "rsrt_partition_mask", "rsrt_partition_tiles", "rsrt_comm_available", "rsrt_comm_unique_id", "rsrt_comm_init", "rsrt_comm_reduce", "rsrt_comm_set_mode", "rsrt_comm_destroy",
             "rsrt_multi_create", "rsrt_multi_destroy", "rsrt_multi_last_error", "rsrt_multi_size", "rsrt_multi_context",
             "rsrt_multi_upload_scene", "rsrt_multi_upload_environment", "rsrt_multi_resize", "rsrt_multi_clear", "rsrt_multi_render",
@@ -223,6 +223,7 @@ def lib():
         L.rsrt_get_region_counters.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_get_walk_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.rsrt_selftest_numerics.argtypes = [C.c_void_p, C.c_void_p]
+        L.rsrt_selftest_sincos.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_cast_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_partition_owner.restype = C.c_uint32
         L.rsrt_partition_owner.argtypes = [C.c_uint32] * 7
@@ -956,6 +957,12 @@ class State:
         out = np.zeros(4, np.uint64)
         self._check(self._L.rsrt_selftest_numerics(self._ctx, _p(out)), "rsrt_selftest_numerics")
         return {"mismatches": int(out[0]), "short_path_inputs": int(out[1]), "bare_rcp_wrong": int(out[2]), "first_bad": int(out[3])}
+
+    def selftest_sincos(self):
+        """Exhaustive device check of rsrt_sincosf against rsrt_sinf / rsrt_cosf (all 2^32 inputs): dict of the words of rsrt_selftest_sincos."""
+        out = np.zeros(4, np.uint64)
+        self._check(self._L.rsrt_selftest_sincos(self._ctx, _p(out)), "rsrt_selftest_sincos")
+        return {"mismatches": int(out[0]), "checked": int(out[1]), "first_bad": int(out[3])}
 
     def build_bvh_device(self, spheres, plane_descs, vertices, triangles):
         """build_bvh on the device (rsrt_build_bvh_device): (primitives, nodes, depth, device milliseconds) — the host
