@@ -90,7 +90,7 @@ typedef struct rsrt_stats {
 rsrt_status rsrt_context_create(int device_index, rsrt_context **out);
 void rsrt_context_destroy(rsrt_context *ctx);
 /* Message of the last failing call on ctx; with ctx == NULL, of the last failing
- * rsrt_context_create on this thread. Never NULL. */
+ * rsrt_context_create or rsrt_scene_image_build on this thread. Never NULL. */
 const char *rsrt_last_error(const rsrt_context *ctx);
 
 /* -- scene: bind group 2, the eight storage buffers (state.rs:394-458) -----------------------
@@ -715,14 +715,47 @@ typedef struct rsrt_hit {
 rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n_rays, const float *origins_xyz, const float *directions_xyz,
                            uint32_t mode, uint32_t flags, rsrt_hit *out);
 
-/* The wide walk's tree (csrc/hip/rt_device.h, trace_wide) for a BVH, built on the HOST exactly as rsrt_upload_scene builds it
- * for the device (no GPU needed; tests/test_wide_tree.py walks it on the CPU): the binary tree collapsed into 4-wide nodes, node 0
+/* The scene's device image, built on the HOST exactly as rsrt_upload_scene builds it (csrc/hip/rt_scene_image.h, build_scene_image;
+ * no context, no GPU: tests/test_scene_image.py reads it on the CPU).  The arrays are rsrt_upload_scene's and are checked the same way;
+ * flat_oriented: whether the flat loop gets its per-octant leaf tables (what RSRT_FLAT_ORIENTED sets for a context, 1 by default).
+ * image_out (may be NULL): 4 floats per float4; *n_float4: capacity in, count out; info_out (may be NULL): where each section lies
+ * and every scalar the upload derives.  RSRT_ERR_INVALID_ARGUMENT: an array, an index or the tree's shape is refused (the reasons
+ * rsrt_upload_scene gives; a tree deeper than the traversal stack is not among them here: stack_entries reports it), or image_out
+ * is too small (*n_float4 then holds the count). */
+typedef struct rsrt_scene_image_info {
+    /* where each section begins, in float4s from the start of the image (rt_device.h DevScene names the sections); the LDS image is
+     * nodes .. flat_leaves with its tables, flat_rank and what follows stay in global memory */
+    uint64_t nodes, escape, prims, tri_normals, materials, fb_spheres, fb_planes, flat_leaves, flat_rank, pnodes, prim_rank, wnodes;
+    uint64_t n_float4;          /* the whole image */
+    uint64_t traversal_head_f4; /* nodes | escape links: what a mid-size scene's tree walks keep in LDS */
+    uint32_t n_nodes, n_prims, n_tris, n_materials, n_spheres, n_planes, n_leaves, n_pnodes, n_wnodes;
+    uint32_t tri_mask_lo, tri_mask_hi, plane_mask_lo, plane_mask_hi;
+    uint32_t flat_ok, flat_ostride, typed_leaves, wide_ok, wide_deep, coop_ok;
+    uint32_t stack_entries; /* tree depth + 1 */
+    uint32_t lds_float4s;   /* float4s of the LDS image, 0: it does not fit small_image_bytes */
+    float cull_min[8][3], cull_max[8][3];
+    uint32_t cull_mask[8], cull_always, n_cull;
+    uint32_t top_elems;  /* elements of the fixed-order walk's top block (the head of pnodes) */
+    uint32_t wimg_nodes; /* wide nodes a mid-size scene may stage in LDS (all of them; 0 without a wide tree) */
+    uint32_t small_image_bytes, hybrid_room_f4; /* the library's LDS room: a whole image's bytes, a walk's head in float4s */
+    uint32_t _pad;
+} rsrt_scene_image_info;
+rsrt_status rsrt_scene_image_build(const rsrt_material *materials, uint32_t n_materials, const rsrt_sphere *spheres, uint32_t n_spheres,
+                                   const rsrt_plane *planes, uint32_t n_planes, const rsrt_vec3 *vertices, uint32_t n_vertices,
+                                   const rsrt_vec3 *normals, uint32_t n_normals, const rsrt_triangle *triangles, uint32_t n_triangles,
+                                   const rsrt_primitive_info *primitives, uint32_t n_primitives, const rsrt_bvh_node *bvh_nodes,
+                                   uint32_t n_bvh_nodes, uint32_t flat_oriented, float *image_out, size_t *n_float4,
+                                   rsrt_scene_image_info *info_out);
+
+/* The wide walk's tree (csrc/hip/rt_device.h, trace_wide) for a BVH, built on the HOST by the builder of the scene image
+ * (csrc/hip/rt_scene_image.h, build_wide_tree; the image's wnodes section holds the same records; no GPU needed;
+ * tests/test_wide_tree.py walks it on the CPU): the binary tree collapsed into 4-wide nodes, node 0
  * the root, a node's interior children consecutive, groups of siblings in the order their parents are expanded (largest box first).  wnodes_out (may be NULL): 32 floats per wide node, 8 x {x, y, z, word} — slot k's exact box is {[2k].xyz,
  * [2k + 1].xyz}; the words are the node's: [0] first interior child's node index (interior children come first and are consecutive)
  * | interior-slot mask << 26, [1] first record of the node's leaf children, [2] / [3] which of the 32 records from there are
  * triangles / planes, [4 + k] slot k's records as a mask from there (0: not a leaf); *n_wnodes: capacity in, count out; old_of_new (may be NULL):
  * for every record index the walk uses (whole leaves are reordered so that a wide node's leaf records are contiguous), the
- * index into `primitives` as given.  RSRT_ERR_INVALID_ARGUMENT: the BVH does not qualify (boxes that do not nest, leaves of
+ * index into `primitives` as given.  RSRT_ERR_INVALID_ARGUMENT: the tree's shape is one rsrt_upload_scene refuses, or the BVH does not qualify (boxes that do not nest, leaves of
  * more than 8 records or that share records, a wide tree of more than 25 levels: the walk's eight stack registers + sixteen overflow words) and keeps the fixed-order walk. */
 rsrt_status rsrt_wide_tree_build(const rsrt_primitive_info *primitives, uint32_t n_primitives, const rsrt_bvh_node *bvh_nodes, uint32_t n_bvh_nodes,
                                  float *wnodes_out, uint32_t *n_wnodes, uint32_t *old_of_new);

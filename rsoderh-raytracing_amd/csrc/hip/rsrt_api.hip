@@ -175,6 +175,7 @@ static constexpr size_t kSmallImageBytes = 24 * 1024;
 static constexpr uint32_t kCoopRoomF4 = (uint32_t)((160 * 1024 - (size_t)(RT_COOP_BLOCK / RT_WAVE) * 4u * pool_wave_lds_dwords(6, RT_COOP_POOL)) / sizeof(float4));
 #include "rt_alias_device.h"
 #include "rt_bvh_device.h"
+#include "rt_scene_image.h" // (host only: the scene's device image, from the constants of the headers above)
 
 // total = textureLoad(cumulative) + sample, once per sample in order (shader.wgsl:1367-1371)
 __global__ __launch_bounds__(RT_BLOCK) void rt_resolve_kernel(RenderParams P, float4 *accum)
@@ -687,188 +688,6 @@ rsrt_status fail(rsrt_context *ctx, rsrt_status st, const char *fmt, ...)
 struct DeviceGuard {
     explicit DeviceGuard(int dev) { (void)hipSetDevice(dev); }
 };
-
-inline float fmaxh(float a, float b) { return a < b ? b : a; }
-inline float fminh(float a, float b) { return b < a ? b : a; }
-inline float saturateh(float x) { return fminh(fmaxh(x, 0.0f), 1.0f); }
-inline float4 f4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-inline float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
-
-// record of one primitive (4 float4), see rt_device.h
-void make_sphere_record(const rsrt_sphere &s, float4 *r)
-{
-    r[0] = f4(s.pos[0], s.pos[1], s.pos[2], u2f(PRIM_SPHERE | (s.material_id << 2)));
-    r[1] = f4(s.radius, s.radius * s.radius, 0, 0);
-    r[2] = r[3] = f4(0, 0, 0, 0);
-}
-void make_plane_record(const rsrt_plane &p, float4 *r)
-{
-    r[0] = f4(p.pos[0], p.pos[1], p.pos[2], u2f(PRIM_PLANE | (p.material_id << 2)));
-    r[1] = f4(p.normal[0], p.normal[1], p.normal[2], 0);
-    r[2] = f4(p.base_change_matrix[0][0], p.base_change_matrix[1][0], p.base_change_matrix[2][0], 0); // row x
-    r[3] = f4(p.base_change_matrix[0][2], p.base_change_matrix[1][2], p.base_change_matrix[2][2], 0); // row z
-}
-void make_triangle_record(const rsrt_triangle &t, uint32_t index, const rsrt_vec3 *v, float4 *r)
-{
-    const float *a = v[t.vertex_0].v, *b = v[t.vertex_1].v, *c = v[t.vertex_2].v;
-    r[0] = f4(a[0], a[1], a[2], u2f(PRIM_TRIANGLE | (t.material_id << 2)));
-    r[1] = f4(b[0] - a[0], b[1] - a[1], b[2] - a[2], u2f(index)); // edge_0, shader.wgsl:415
-    r[2] = f4(c[0] - a[0], c[1] - a[1], c[2] - a[2], 0);          // edge_1, :416
-    r[3] = f4(0, 0, 0, 0);
-}
-// Do two primitive records put the same numbers into their intersection test (type and geometry words; not the material, not a
-// triangle's normal index)?  Then every ray gets the same t from both.
-bool same_test(const float4 *a, const float4 *b)
-{
-    uint32_t ta, tb;
-    memcpy(&ta, &a[0].w, 4); memcpy(&tb, &b[0].w, 4);
-    if ((ta & 3u) != (tb & 3u) || memcmp(&a[0], &b[0], 12) != 0) return false;
-    if ((ta & 3u) == PRIM_TRIANGLE) return memcmp(&a[1], &b[1], 12) == 0 && memcmp(&a[2], &b[2], 12) == 0;
-    return memcmp(a + 1, b + 1, 3 * sizeof(float4)) == 0;
-}
-// make_bsdf_material / surface_f0 / surface_kd / lobe probabilities (shader.wgsl:850-881, :1147-1148)
-void make_material_record(const rsrt_material &m, float4 *r)
-{
-    const float t = saturateh(m.metallic);
-    float f0[3], kd[3];
-    for (int k = 0; k < 3; k++) f0[k] = (1.0f - t) * 0.04f + t * m.color[k];
-    const float maxf0 = fmaxh(f0[0], fmaxh(f0[1], f0[2]));
-    for (int k = 0; k < 3; k++) kd[k] = (m.color[k] * (1.0f - t)) * (1.0f - maxf0);
-    const float alpha = fmaxh(0.001f, m.roughness * m.roughness);
-    const float ps = saturateh(0.2126f * f0[0] + 0.7152f * f0[1] + 0.0722f * f0[2]);
-    r[0] = f4(m.color[0], m.color[1], m.color[2], m.metallic);
-    r[1] = f4(f0[0], f0[1], f0[2], alpha);
-    r[2] = f4(m.emission[0], m.emission[1], m.emission[2], ps);
-    r[3] = f4(kd[0], kd[1], kd[2], 1.0f - ps);
-}
-
-// ---- wide walk (rt_device.h, trace_wide): the binary tree collapsed into 4-wide nodes, laid out hottest-first (build_wide_tree)
-struct WideNode { uint32_t ch[4]; uint32_t n_ch, n_int, first_child; }; // binary nodes of the children (interior ones first), index of the first interior child's wide node
-// false: the scene does not qualify (see rsrt_upload_scene).  prims_out / nodes_out: `prims` with whole leaves reordered so that
-// the records of a wide node's leaf children are contiguous, and `nodes` with the leaves' first indices pointing there;
-// old_of_new (may be NULL): for every new record index the old one.
-bool build_wide_tree(const rsrt_bvh_node *nodes, uint32_t n_nodes, const rsrt_primitive_info *prims, uint32_t n_prims, std::vector<WideNode> &wide,
-                     std::vector<rsrt_primitive_info> &prims_out, std::vector<rsrt_bvh_node> &nodes_out, std::vector<uint32_t> *old_of_new, uint32_t *wide_depth = nullptr)
-{
-    wide.clear();
-    bool ok = n_nodes >= 3 && nodes[0].primitives_len == 0;
-    {
-        std::vector<uint8_t> covered(n_prims, 0);
-        for (uint32_t i = 0; i < n_nodes && ok; i++) {
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len > 8) ok = false;
-            for (uint32_t k = 0; k < nd.primitives_len && ok; k++) {
-                uint8_t &c = covered[nd.primitives_or_second_child_index + k];
-                ok = c == 0;
-                c = 1;
-            }
-            if (nd.primitives_len == 0)
-                for (uint32_t c : {i + 1u, nd.primitives_or_second_child_index})
-                    for (int k = 0; k < 3; k++)
-                        ok = ok && nodes[c].bounds_min[k] >= nd.bounds_min[k] && nodes[c].bounds_max[k] <= nd.bounds_max[k];
-        }
-        for (uint32_t p = 0; p < n_prims; p++) ok = ok && covered[p]; // the permutation below must be total
-    }
-    if (!ok) return false;
-    auto area = [&](uint32_t i) {
-        const double dx = (double)nodes[i].bounds_max[0] - nodes[i].bounds_min[0], dy = (double)nodes[i].bounds_max[1] - nodes[i].bounds_min[1],
-                     dz = (double)nodes[i].bounds_max[2] - nodes[i].bounds_min[2];
-        const double a = dx * dy + dy * dz + dz * dx;
-        return a == a ? a : 0.0;
-    };
-    // Array order = the order in which nodes are ALLOCATED, and a node's interior children are allocated together, when the node is
-    // expanded (child k = first child + k).  Nodes are expanded largest box first (a ray meets a node about as often as its box is large, and
-    // a child's box lies inside its parent's), so that the array's head — the part the kernel stages in LDS — is the part of the tree the
-    // rays visit most.
-    std::vector<uint32_t> queue{0u}, level{0u}; // binary roots of the wide nodes, in array order
-    uint32_t wdepth = 1;
-    const bool by_area = true; // (breadth-first instead: the first version, 0-1.5 % slower, profiles/r03_walk_bounds.txt)
-    std::vector<std::pair<double, uint32_t>> heap{{area(0), 0u}}; // (box area, array index) of the nodes still to expand
-    size_t bfs_next = 0;
-    while (by_area ? !heap.empty() : bfs_next < queue.size()) {
-        size_t qi;
-        if (by_area) {
-            std::pop_heap(heap.begin(), heap.end(), [](const std::pair<double, uint32_t> &a, const std::pair<double, uint32_t> &b) { return a.first < b.first || (a.first == b.first && a.second > b.second); });
-            qi = heap.back().second;
-            heap.pop_back();
-        } else {
-            qi = bfs_next++;
-        }
-        const uint32_t r = queue[qi];
-        std::vector<uint32_t> ch{r + 1u, nodes[r].primitives_or_second_child_index};
-        while (ch.size() < 4) { // open the interior child with the largest box
-            int best = -1;
-            for (size_t k = 0; k < ch.size(); k++)
-                if (nodes[ch[k]].primitives_len == 0 && (best < 0 || area(ch[k]) > area(ch[best]))) best = (int)k;
-            if (best < 0) break;
-            const uint32_t c = ch[best];
-            ch[best] = c + 1u;
-            ch.insert(ch.begin() + best + 1, nodes[c].primitives_or_second_child_index);
-        }
-        WideNode w{};
-        for (uint32_t c : ch) if (nodes[c].primitives_len == 0) w.ch[w.n_ch++] = c; // interior children first ...
-        w.n_int = w.n_ch;
-        for (uint32_t c : ch) if (nodes[c].primitives_len != 0) w.ch[w.n_ch++] = c; // ... then the leaves
-        w.first_child = (uint32_t)queue.size(); // consecutive: allocated here and now
-        for (uint32_t k = 0; k < w.n_int; k++) {
-            const uint32_t idx = (uint32_t)queue.size();
-            queue.push_back(w.ch[k]);
-            level.push_back(level[qi] + 1u);
-            wdepth = std::max(wdepth, level[qi] + 2u);
-            if (by_area) {
-                heap.push_back({area(w.ch[k]), idx});
-                std::push_heap(heap.begin(), heap.end(), [](const std::pair<double, uint32_t> &a, const std::pair<double, uint32_t> &b) { return a.first < b.first || (a.first == b.first && a.second > b.second); });
-            }
-        }
-        if (wide.size() < queue.size()) wide.resize(queue.size());
-        wide[qi] = w;
-    }
-    wide.resize(queue.size());
-    if (wdepth > RT_WSTACK + RT_WSPILL + 1u || wide.size() >= (1u << 27)) { wide.clear(); return false; } // (deeper than the walk's stack: registers + overflow columns)
-    if (wide_depth) *wide_depth = wdepth;
-    // whole leaves, in the order the wide nodes list them
-    prims_out.resize(n_prims);
-    nodes_out.assign(nodes, nodes + n_nodes);
-    if (old_of_new) old_of_new->resize(n_prims);
-    uint32_t at = 0;
-    for (const WideNode &w : wide)
-        for (uint32_t k = w.n_int; k < w.n_ch; k++) {
-            const rsrt_bvh_node &lf = nodes[w.ch[k]];
-            for (uint32_t j = 0; j < lf.primitives_len; j++) {
-                prims_out[at + j] = prims[lf.primitives_or_second_child_index + j];
-                if (old_of_new) (*old_of_new)[at + j] = lf.primitives_or_second_child_index + j;
-            }
-            nodes_out[w.ch[k]].primitives_or_second_child_index = at;
-            at += lf.primitives_len;
-        }
-    return true;
-}
-// the device records of the wide nodes (8 float4 each; rt_device.h, DevScene::wnodes) from the PERMUTED nodes / primitives
-void fill_wide_nodes(const std::vector<WideNode> &wide, const rsrt_bvh_node *nodes, const rsrt_primitive_info *prims, float4 *out)
-{
-    for (size_t wi = 0; wi < wide.size(); wi++) {
-        const WideNode &w = wide[wi];
-        float4 *q = out + 8 * wi;
-        uint32_t words[8] = {0, 0, 0, 0, 0, 0, 0, 0}; // see DevScene::wnodes
-        words[0] = w.first_child | (((1u << w.n_int) - 1u) << 26);
-        if (w.n_ch > w.n_int) words[1] = nodes[w.ch[w.n_int]].primitives_or_second_child_index; // the leaves' records are contiguous from here
-        for (uint32_t k = 0; k < 4; k++) {
-            if (k >= w.n_ch) { q[2 * k] = q[2 * k + 1] = f4(0, 0, 0, 0); continue; } // (an empty slot's box may "hit": no mask names it)
-            const rsrt_bvh_node &nd = nodes[w.ch[k]]; // the child's EXACT box
-            q[2 * k] = f4(nd.bounds_min[0], nd.bounds_min[1], nd.bounds_min[2], 0);
-            q[2 * k + 1] = f4(nd.bounds_max[0], nd.bounds_max[1], nd.bounds_max[2], 0);
-            if (k < w.n_int) continue;
-            const uint32_t off = nd.primitives_or_second_child_index - words[1]; // < 32: four leaves of at most eight records
-            words[4 + k] = ((1u << nd.primitives_len) - 1u) << off;
-            for (uint32_t j = 0; j < nd.primitives_len; j++) {
-                const uint32_t ty = prims[nd.primitives_or_second_child_index + j].primitive_type;
-                if (ty >= 2) words[2] |= 1u << (off + j);
-                else if (ty == 1) words[3] |= 1u << (off + j);
-            }
-        }
-        for (int k = 0; k < 8; k++) q[k].w = u2f(words[k]);
-    }
-}
 
 // Orders `stream` after everything this context has enqueued so far (no-op on the same stream).
 rsrt_status begin_work(rsrt_context *ctx, hipStream_t stream)
@@ -1408,453 +1227,64 @@ const char *rsrt_build_id(void) { return RSRT_BUILD_ID; }
 
 const char *rsrt_describe(rsrt_context *ctx) { return ctx ? ctx->description.c_str() : "librsrt 0.1"; }
 
+// validate_scene, then build_scene_image (rt_scene_image.h) with the library's LDS room; a refusal's reason goes to ctx (NULL: to this thread's)
+static rsrt_status checked_scene_image(rsrt_context *ctx, const SceneInputs &in, bool flat_oriented, SceneImage &out)
+{
+    uint32_t depth = 0;
+    out.error = validate_scene(in, &depth);
+    if (out.error.empty()) out = build_scene_image(in, depth, flat_oriented, kSmallImageBytes, kHybridRoomF4);
+    return out.error.empty() ? RSRT_OK : fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s", out.error.c_str());
+}
+
 rsrt_status rsrt_upload_scene(rsrt_context *ctx, const rsrt_material *materials, uint32_t n_materials, const rsrt_sphere *spheres,
                               uint32_t n_spheres, const rsrt_plane *planes, uint32_t n_planes, const rsrt_vec3 *vertices,
                               uint32_t n_vertices, const rsrt_vec3 *normals, uint32_t n_normals, const rsrt_triangle *triangles,
-                              uint32_t n_triangles, const rsrt_primitive_info *primitives_in, uint32_t n_primitives,
-                              const rsrt_bvh_node *nodes_in, uint32_t n_nodes)
+                              uint32_t n_triangles, const rsrt_primitive_info *primitives, uint32_t n_primitives,
+                              const rsrt_bvh_node *nodes, uint32_t n_nodes)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     ctx->tp_frames = 0; // the temporal history belongs to the old scene
-    const rsrt_primitive_info *primitives = primitives_in; // (re-pointed below at a copy with whole leaves reordered, when the wide walk is built)
-    const rsrt_bvh_node *nodes = nodes_in;
-    if (n_nodes == 0 || !nodes) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh_nodes is empty");
-    if (n_nodes >= RT_END) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh_nodes: %u nodes exceed the 25-bit traversal cursor", n_nodes);
-    if ((n_materials && !materials) || (n_spheres && !spheres) || (n_planes && !planes) || (n_vertices && !vertices) ||
-        (n_normals && !normals) || (n_triangles && !triangles) || (n_primitives && !primitives))
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "a non-empty array has a NULL pointer");
-    if (n_materials >= (1u << 30)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "too many materials");
-    // ---- validate every index the kernels will follow
-    for (uint32_t i = 0; i < n_spheres; i++)
-        if (spheres[i].material_id >= n_materials) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "sphere %u: material_id %u out of range", i, spheres[i].material_id);
-    for (uint32_t i = 0; i < n_planes; i++)
-        if (planes[i].material_id >= n_materials) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "plane %u: material_id %u out of range", i, planes[i].material_id);
-    for (uint32_t i = 0; i < n_triangles; i++) {
-        const rsrt_triangle &t = triangles[i];
-        if (t.material_id >= n_materials) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "triangle %u: material_id %u out of range", i, t.material_id);
-        if (t.vertex_0 >= n_vertices || t.vertex_1 >= n_vertices || t.vertex_2 >= n_vertices)
-            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "triangle %u: vertex index out of range", i);
-        if (t.normal_0 >= n_normals || t.normal_1 >= n_normals || t.normal_2 >= n_normals)
-            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "triangle %u: normal index out of range", i);
-    }
-    for (uint32_t i = 0; i < n_primitives; i++) {
-        const rsrt_primitive_info &p = primitives[i];
-        uint32_t lim = p.primitive_type == 0 ? n_spheres : (p.primitive_type == 1 ? n_planes : (p.primitive_type == 2 ? n_triangles : 0));
-        if (p.index >= lim) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "primitive %u: type %u index %u out of range", i, p.primitive_type, p.index);
-    }
-    // tree shape: pre-order layout (children after their parent) => traversal terminates
-    uint32_t depth = 0;
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> st; // node, depth
-        std::vector<uint8_t> seen(n_nodes, 0);
-        st.push_back({0u, 0u});
-        while (!st.empty()) {
-            auto [i, d] = st.back();
-            st.pop_back();
-            if (seen[i]) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh node %u reachable twice", i);
-            seen[i] = 1;
-            depth = std::max(depth, d);
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len > 0) {
-                if (nd.primitives_len > 0xffffu || (uint64_t)nd.primitives_or_second_child_index + nd.primitives_len > n_primitives)
-                    return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh leaf %u: primitive range out of bounds", i);
-            } else {
-                uint32_t second = nd.primitives_or_second_child_index;
-                if (nd.split_axis > 2 || i + 1 >= n_nodes || second <= i + 1 || second >= n_nodes)
-                    return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh interior node %u: bad child index / axis", i);
-                st.push_back({second, d + 1});
-                st.push_back({i + 1, d + 1});
-            }
-        }
-        for (uint32_t i = 0; i < n_nodes; i++) // (the tables built below are indexed by every node)
-            if (!seen[i]) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh node %u is not reachable from the root", i);
-    }
-    // ---- wide walk (rt_device.h, trace_wide): the binary tree collapsed into 4-wide nodes, a node's interior children consecutive.  Needs what makes
-    // skipping binary nodes exact — every child box inside its parent's — plus leaves of <= 8 records that share none (the
-    // records of a wide node's leaf children are made contiguous by moving whole leaves: `primitives` and the leaves' first
-    // indices are re-pointed at permuted copies, and everything below is built from those; a record's index is internal to
-    // the device image, ties are decided by the visiting ranks computed from the tree) and a wide tree of at most
-    // RT_WSTACK + RT_WSPILL + 1 levels (the walk's stack: eight registers and sixteen overflow words).
-    std::vector<WideNode> wide;
-    std::vector<rsrt_primitive_info> prims_perm;
-    std::vector<rsrt_bvh_node> nodes_perm;
-    uint32_t wide_depth = 0;
-    const bool wide_ok = build_wide_tree(nodes, n_nodes, primitives, n_primitives, wide, prims_perm, nodes_perm, nullptr, &wide_depth);
-    if (wide_ok) {
-        primitives = prims_perm.data();
-        nodes = nodes_perm.data();
-    }
-    // ---- threaded traversal links: escape[octant][node] (rt_device.h, trace_threaded)
-    std::vector<uint32_t> escape(8ull * n_nodes, RT_END);
-    for (uint32_t q = 0; q < 8; q++) {
-        std::vector<std::pair<uint32_t, uint32_t>> st; // node, its escape
-        st.push_back({0u, RT_END});
-        while (!st.empty()) {
-            auto [i, esc] = st.back();
-            st.pop_back();
-            escape[(size_t)q * n_nodes + i] = esc;
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len == 0) {
-                const bool far_first = (q >> nd.split_axis) & 1u; // sign(inv_dir[axis]) < 0: second child is nearer
-                const uint32_t first = i + 1, second = nd.primitives_or_second_child_index;
-                const uint32_t near_c = far_first ? second : first, far_c = far_first ? first : second;
-                st.push_back({near_c, far_c});
-                st.push_back({far_c, esc});
-            }
-        }
-    }
-    const size_t esc_f4 = (8ull * n_nodes + 3) / 4;
-    // ---- flat small-scene traversal (rt_device.h, trace_flat): leaf list, record masks, per-octant visiting ranks
-    std::vector<uint32_t> leaf_nodes;
-    // ... at most 64 records of each kind (a hit is carried as a 6-bit record index + 2-bit source in the idle cursor
-    // bits), few enough leaves that testing every leaf box beats the tree walk, and (below) nested boxes and leaves
-    // that share no record: the rank table gives every record ONE position in the visiting order
-    bool flat_ok = n_primitives <= 64 && n_spheres <= 64 && n_planes <= 64;
-    {
-        std::vector<uint8_t> covered(n_primitives, 0);
-        for (uint32_t i = 0; i < n_nodes && flat_ok; i++)
-            for (uint32_t k = 0; k < nodes[i].primitives_len && flat_ok; k++) {
-                uint8_t &c = covered[nodes[i].primitives_or_second_child_index + k];
-                flat_ok = c == 0;
-                c = 1;
-            }
-    }
-    for (uint32_t i = 0; i < n_nodes; i++) {
-        const rsrt_bvh_node &nd = nodes[i];
-        if (nd.primitives_len != 0) { leaf_nodes.push_back(i); continue; }
-        for (uint32_t c : {i + 1u, nd.primitives_or_second_child_index}) // every child box inside its parent's
-            for (int k = 0; k < 3; k++)
-                flat_ok = flat_ok && nodes[c].bounds_min[k] >= nd.bounds_min[k] && nodes[c].bounds_max[k] <= nd.bounds_max[k];
-    }
-    flat_ok = flat_ok && leaf_nodes.size() <= 32;
-    std::vector<uint32_t> flat_rank(8 * 16, 0u);
-    uint64_t tri_mask = 0, plane_mask = 0;
-    if (flat_ok) {
-        for (uint32_t p = 0; p < n_primitives; p++) {
-            if (primitives[p].primitive_type >= 2) tri_mask |= 1ull << p;
-            else if (primitives[p].primitive_type == 1) plane_mask |= 1ull << p;
-        }
-        for (uint32_t q = 0; q < 8; q++) { // the reference's near-child-first walk for this sign octant, every box "hit"
-            std::vector<uint32_t> st{0u};
-            uint32_t pos = 0;
-            while (!st.empty()) {
-                const uint32_t i = st.back();
-                st.pop_back();
-                const rsrt_bvh_node &nd = nodes[i];
-                if (nd.primitives_len != 0) {
-                    for (uint32_t k = 0; k < nd.primitives_len; k++, pos++) {
-                        const uint32_t rec = nd.primitives_or_second_child_index + k;
-                        flat_rank[q * 16 + (rec >> 2)] |= pos << (8 * (rec & 3));
-                    }
-                } else {
-                    const bool far_first = (q >> nd.split_axis) & 1u;
-                    const uint32_t first = i + 1, second = nd.primitives_or_second_child_index;
-                    st.push_back(far_first ? first : second); // far child: visited after the near one
-                    st.push_back(far_first ? second : first);
-                }
-            }
-        }
-    }
-    const size_t flat_f4 = flat_ok ? 2 * leaf_nodes.size() : 0, rank_f4 = flat_ok ? 32 : 0;
-    // The leaf boxes once more for each ray-sign octant q (bit 0 x, bit 1 y, bit 2 z, as trace_flat computes it), corners in slab
-    // order: {near.xyz, mask lo}{far.xyz, mask hi}, near = the max corner on the axes whose bit is set.  Tables are 2 x an odd
-    // number of float4s apart, so the eight octants' copies of one leaf lie in eight different 16-byte cells of LDS's 256-byte bank
-    // row (a ds_read_b128 of a wave of mixed octants has no bank conflict).  Only where the image with them still fits beside the
-    // path pools: a scene they would push out of LDS keeps the loop that orders the values itself.
-    const size_t ostride_f4 = 2 * (leaf_nodes.size() | 1);
-    const size_t oflat_f4 = flat_ok && ctx->flat_oriented ? 8 * ostride_f4 : 0;
-    const size_t base_f4 = 2ull * n_nodes + 4ull * n_primitives + 3ull * n_triangles + 4ull * n_materials + 4ull * n_spheres + 4ull * n_planes + esc_f4 + flat_f4;
-    const bool flat_oriented = oflat_f4 != 0 && (base_f4 + oflat_f4) * sizeof(float4) <= kSmallImageBytes;
-    // ---- fixed-order traversal (rt_device.h, trace_preorder): per-octant visiting rank of EVERY primitive record — the
-    // position at which the reference's near-child-first walk meets it — which decides equal t whatever order the records
-    // are really tested in; and the skip links of the pre-order node array (next node once an interior node is missed).
-    std::vector<uint32_t> prim_rank(8ull * n_primitives, 0xffffffffu); // (a record that several leaves share keeps the rank of its FIRST visit: the reference's strict < keeps the first of equals)
-    for (uint32_t q = 0; q < 8; q++) {
-        std::vector<uint32_t> st{0u};
-        uint32_t pos = 0;
-        while (!st.empty()) {
-            const uint32_t i = st.back();
-            st.pop_back();
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len != 0) {
-                for (uint32_t k = 0; k < nd.primitives_len; k++, pos++) {
-                    uint32_t &rk = prim_rank[(size_t)q * n_primitives + nd.primitives_or_second_child_index + k];
-                    rk = std::min(rk, pos);
-                }
-            } else {
-                const bool far_first = (q >> nd.split_axis) & 1u;
-                const uint32_t first = i + 1, second = nd.primitives_or_second_child_index;
-                st.push_back(far_first ? first : second);
-                st.push_back(far_first ? second : first);
-            }
-        }
-    }
-    // The walk's node array ("pnodes").  Every interior node carries BOTH its links explicitly — where to go when its box
-    // is hit (its first child) and when it is missed (the pre-order successor of its subtree) — and a leaf is followed by
-    // its successor, so the array may be laid out in any order.  It is laid out in two levels: first a TOP BLOCK, the
-    // nodes a ray is most likely to meet (greedy by box surface area from the root: a child's box lies inside its
-    // parent's, so the set is closed under "parent of"), in their pre-order; then everything else, in pre-order.  The
-    // kernel keeps the top block in LDS (one copy per CU) and reads the rest from global memory: on the 15,488-triangle
-    // grid scene 1,400 of 8,731 nodes take ~80 % of the box tests.  Where a leaf's successor is not the next array
-    // element (a subtree leaves or re-enters the top block) a JUMP element is inserted: an interior-type record whose
-    // two links are equal and whose box is never tested.
-    struct PNode { uint32_t old; uint32_t jump_to; }; // old == UINT32_MAX: a jump element to old node `jump_to` (n_nodes = end)
-    std::vector<uint32_t> succ(n_nodes, n_nodes); // pre-order successor of node i's subtree
-    {
-        std::vector<std::pair<uint32_t, uint32_t>> st; // node, what follows its subtree
-        st.push_back({0u, n_nodes});
-        while (!st.empty()) {
-            auto [i, after] = st.back();
-            st.pop_back();
-            succ[i] = after;
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len == 0) {
-                st.push_back({i + 1, nd.primitives_or_second_child_index}); // the first child's subtree ends where the second child begins
-                st.push_back({nd.primitives_or_second_child_index, after});
-            }
-        }
-    }
-    const uint32_t kTopMax = kHybridRoomF4 / 2u; // top-block elements that fit beside sixteen path pools (32 B each)
-    std::vector<PNode> plist;
-    uint32_t top_elems = 0;
-    for (uint32_t want = std::min<uint32_t>(n_nodes, kTopMax);; want = want * 7 / 8) {
-        std::vector<uint8_t> in_top(n_nodes, 0);
-        { // greedy by surface area
-            auto area = [&](uint32_t i) {
-                const double dx = (double)nodes[i].bounds_max[0] - nodes[i].bounds_min[0], dy = (double)nodes[i].bounds_max[1] - nodes[i].bounds_min[1],
-                             dz = (double)nodes[i].bounds_max[2] - nodes[i].bounds_min[2];
-                const double a = dx * dy + dy * dz + dz * dx;
-                return a == a ? a : 0.0;
-            };
-            std::vector<std::pair<double, uint32_t>> heap;
-            heap.push_back({area(0), 0u});
-            uint32_t taken = 0;
-            while (!heap.empty() && taken < want) {
-                std::pop_heap(heap.begin(), heap.end());
-                const uint32_t i = heap.back().second;
-                heap.pop_back();
-                in_top[i] = 1;
-                taken++;
-                if (nodes[i].primitives_len == 0)
-                    for (uint32_t c : {i + 1u, nodes[i].primitives_or_second_child_index}) {
-                        heap.push_back({area(c), c});
-                        std::push_heap(heap.begin(), heap.end());
-                    }
-            }
-        }
-        plist.clear();
-        for (int pass = 0; pass < 2; pass++) { // top block, then the rest; both in pre-order (= index order)
-            std::vector<uint32_t> order;
-            for (uint32_t i = 0; i < n_nodes; i++)
-                if ((in_top[i] != 0) == (pass == 0)) order.push_back(i);
-            for (size_t k = 0; k < order.size(); k++) {
-                const uint32_t i = order[k];
-                plist.push_back({i, 0u});
-                const uint32_t follows = k + 1 < order.size() ? order[k + 1] : 0xffffffffu; // (the rest's first element never follows the top block's last)
-                if (nodes[i].primitives_len != 0 && succ[i] != follows) plist.push_back({0xffffffffu, succ[i]});
-            }
-            if (pass == 0) top_elems = (uint32_t)plist.size();
-        }
-        if (top_elems <= kTopMax || want <= 1) break;
-    }
-    const uint32_t n_pnodes = (uint32_t)plist.size();
-    if (n_pnodes >= RT_END) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh_nodes: %u traversal elements exceed the 25-bit cursor", n_pnodes);
-    std::vector<uint32_t> new_id(n_nodes + 1, n_pnodes); // old node -> element; [n_nodes] = end
-    for (uint32_t e = 0; e < n_pnodes; e++)
-        if (plist[e].old != 0xffffffffu) new_id[plist[e].old] = e;
-    const size_t pnode_f4 = 2ull * n_pnodes, prank_f4 = (8ull * n_primitives + 3) / 4, wnode_f4 = 8ull * wide.size();
-    // the wide walks' LDS image: the head of the wide-node array (hottest first), as far as the room beside the launch's pools goes (hybrid_stage)
-    const uint32_t wimg_nodes = wide_ok ? (uint32_t)wide.size() : 0u;
-    // ---- build the device image: nodes | prims | escape links | tri normals | materials | fb spheres | fb planes
-    const size_t n_f4 = base_f4 + (flat_oriented ? oflat_f4 : 0);
-    std::vector<float4> img(n_f4 + rank_f4 + pnode_f4 + prank_f4 + wnode_f4); // what follows the LDS image: flat ranks | pre-order nodes | record ranks | wide nodes
-    float4 *p = img.data();
-    float4 *p_nodes = p;
-    bool typed_leaves = true;
-    for (uint32_t i = 0; i < n_nodes; i++) typed_leaves = typed_leaves && nodes[i].primitives_len <= 8;
-    for (uint32_t i = 0; i < n_nodes; i++, p += 2) {
-        const rsrt_bvh_node &nd = nodes[i];
-        p[0] = f4(nd.bounds_min[0], nd.bounds_min[1], nd.bounds_min[2], u2f(nd.primitives_or_second_child_index));
-        uint32_t hi = nd.split_axis; // interior: split axis; leaf (when every leaf has <= 8 primitives): triangle mask | plane mask << 8
-        if (nd.primitives_len != 0) {
-            hi = 0;
-            if (typed_leaves)
-                for (uint32_t k = 0; k < nd.primitives_len; k++) {
-                    const uint32_t ty = primitives[nd.primitives_or_second_child_index + k].primitive_type;
-                    if (ty >= 2) hi |= 1u << k;
-                    else if (ty == 1) hi |= 1u << (8 + k);
-                }
-        }
-        p[1] = f4(nd.bounds_max[0], nd.bounds_max[1], nd.bounds_max[2], u2f(nd.primitives_len | (hi << 16)));
-    }
-    float4 *p_esc = p;
-    memcpy(p_esc, escape.data(), escape.size() * sizeof(uint32_t));
-    p += esc_f4;
-    const size_t traversal_head_f4 = (size_t)(p - img.data()); // nodes | escape links: what the hybrid view keeps in LDS
-    float4 *p_prims = p;
-    for (uint32_t i = 0; i < n_primitives; i++, p += 4) {
-        const rsrt_primitive_info &pi = primitives[i];
-        if (pi.primitive_type == 0) make_sphere_record(spheres[pi.index], p);
-        else if (pi.primitive_type == 1) make_plane_record(planes[pi.index], p);
-        else make_triangle_record(triangles[pi.index], pi.index, vertices, p);
-    }
-    float4 *p_trin = p;
-    for (uint32_t i = 0; i < n_triangles; i++, p += 3) {
-        const float *a = normals[triangles[i].normal_0].v, *b = normals[triangles[i].normal_1].v, *c = normals[triangles[i].normal_2].v;
-        p[0] = f4(a[0], a[1], a[2], b[0]);
-        p[1] = f4(b[1], b[2], c[0], c[1]);
-        p[2] = f4(c[2], 0, 0, 0);
-    }
-    float4 *p_mats = p;
-    for (uint32_t i = 0; i < n_materials; i++, p += 4) make_material_record(materials[i], p);
-    float4 *p_fbs = p;
-    for (uint32_t i = 0; i < n_spheres; i++, p += 4) make_sphere_record(spheres[i], p);
-    float4 *p_fbp = p;
-    for (uint32_t i = 0; i < n_planes; i++, p += 4) make_plane_record(planes[i], p);
-    float4 *p_flat = p;
-    if (flat_ok) {
-        for (uint32_t i : leaf_nodes) {
-            const rsrt_bvh_node &nd = nodes[i];
-            uint64_t lm = (nd.primitives_len >= 64 ? ~0ull : ((1ull << nd.primitives_len) - 1ull)) << nd.primitives_or_second_child_index;
-            // A record whose geometry is bit for bit that of an EARLIER record of the same leaf can never win: it gives the very
-            // same t, and the reference keeps the first of equals (strict <, a leaf's records in index order whatever the
-            // octant).  It is left out of the leaf's mask — house.toml lists its ground plane twice.
-            for (uint32_t b = 1; b < nd.primitives_len; b++)
-                for (uint32_t a = 0; a < b; a++)
-                    if (same_test(p_prims + 4 * (nd.primitives_or_second_child_index + a), p_prims + 4 * (nd.primitives_or_second_child_index + b))) {
-                        lm &= ~(1ull << (nd.primitives_or_second_child_index + b));
-                        break;
-                    }
-            p[0] = f4(nd.bounds_min[0], nd.bounds_min[1], nd.bounds_min[2], u2f((uint32_t)lm));
-            p[1] = f4(nd.bounds_max[0], nd.bounds_max[1], nd.bounds_max[2], u2f((uint32_t)(lm >> 32)));
-            p += 2;
-        }
-        if (flat_oriented) {
-            for (uint32_t q = 0; q < 8; q++)
-                for (size_t k = 0; k < leaf_nodes.size(); k++) {
-                    const float4 lo = p_flat[2 * k], hi = p_flat[2 * k + 1];
-                    float4 *c = p + q * ostride_f4 + 2 * k;
-                    c[0] = f4(q & 1u ? hi.x : lo.x, q & 2u ? hi.y : lo.y, q & 4u ? hi.z : lo.z, lo.w);
-                    c[1] = f4(q & 1u ? lo.x : hi.x, q & 2u ? lo.y : hi.y, q & 4u ? lo.z : hi.z, hi.w);
-                }
-            p += oflat_f4;
-        }
-        memcpy(p, flat_rank.data(), flat_rank.size() * sizeof(uint32_t));
-    }
-    // The cooperative walk (rt_coop.h) folds an extension ray's hits with an atomic minimum and sends a ray that sees two records at the same
-    // closest t through the exact walk once more.  A record that repeats an EARLIER record of its leaf bit for bit gives that record's t to every
-    // ray and can never win (the reference keeps the first of equals; a leaf's records are met in index order whatever the octant): it is
-    // marked in a word no test reads (r2.w) and counts as a miss there, so that doubled geometry does not make every hit a tie.
-    {
-        std::vector<uint32_t> twins;
-        for (uint32_t i = 0; i < n_nodes; i++) {
-            const rsrt_bvh_node &nd = nodes[i];
-            for (uint32_t b = 1; b < nd.primitives_len; b++)
-                for (uint32_t a = 0; a < b; a++)
-                    if (same_test(p_prims + 4 * (nd.primitives_or_second_child_index + a), p_prims + 4 * (nd.primitives_or_second_child_index + b))) {
-                        twins.push_back(nd.primitives_or_second_child_index + b);
-                        break;
-                    }
-        }
-        for (uint32_t r : twins) p_prims[4 * r + 2].w = u2f(1u); // (afterwards: same_test compares these words too)
-    }
-    float4 *p_pnodes = img.data() + n_f4 + rank_f4;
-    for (uint32_t e = 0; e < n_pnodes; e++) {
-        if (plist[e].old == 0xffffffffu) { // jump element: both links equal, box never looked at
-            const uint32_t to = new_id[plist[e].jump_to];
-            p_pnodes[2 * e] = f4(0, 0, 0, u2f(to));
-            p_pnodes[2 * e + 1] = f4(0, 0, 0, u2f(to));
-            continue;
-        }
-        const uint32_t i = plist[e].old;
-        p_pnodes[2 * e] = p_nodes[2 * i];
-        p_pnodes[2 * e + 1] = p_nodes[2 * i + 1];
-        if (nodes[i].primitives_len == 0) { // interior: {min, link when hit}{max, link when missed}
-            p_pnodes[2 * e].w = u2f(new_id[i + 1]);
-            p_pnodes[2 * e + 1].w = u2f(new_id[succ[i]]);
-        } else { // leaf: first record | leaf flag; length | triangle mask << 16 | plane mask << 24 (as in `nodes`)
-            p_pnodes[2 * e].w = u2f(nodes[i].primitives_or_second_child_index | 0x80000000u);
-        }
-    }
-    if (n_primitives) memcpy(p_pnodes + pnode_f4, prim_rank.data(), prim_rank.size() * sizeof(uint32_t));
-    fill_wide_nodes(wide, nodes, primitives, p_pnodes + pnode_f4 + prank_f4);
+    const SceneInputs in{materials, n_materials, spheres, n_spheres, planes, n_planes, vertices, n_vertices, normals, n_normals,
+                         triangles, n_triangles, primitives, n_primitives, nodes, n_nodes};
+    SceneImage built;
+    if (rsrt_status st = checked_scene_image(ctx, in, ctx->flat_oriented, built)) return st; // (every refusal but one: the device is not touched yet)
+    const rsrt_scene_image_info &im = built.info;
 
     { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
     if (ctx->scene_blob) { (void)hipFree(ctx->scene_blob); ctx->scene_blob = nullptr; }
     ctx->scene_ready = false;
-    HIP_TRY(ctx, hipMalloc(&ctx->scene_blob, img.size() * sizeof(float4)));
-    HIP_TRY(ctx, hipMemcpy(ctx->scene_blob, img.data(), img.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMalloc(&ctx->scene_blob, built.image.size() * sizeof(float4)));
+    HIP_TRY(ctx, hipMemcpy(ctx->scene_blob, built.image.data(), built.image.size() * sizeof(float4), hipMemcpyHostToDevice));
+    const float4 *blob = ctx->scene_blob;
     DevScene &sc = ctx->scene;
-    sc.nodes = ctx->scene_blob + (p_nodes - img.data());
-    sc.prims = ctx->scene_blob + (p_prims - img.data());
-    sc.tri_normals = ctx->scene_blob + (p_trin - img.data());
-    sc.materials = ctx->scene_blob + (p_mats - img.data());
-    sc.fb_spheres = ctx->scene_blob + (p_fbs - img.data());
-    sc.fb_planes = ctx->scene_blob + (p_fbp - img.data());
-    sc.escape = ctx->scene_blob + (p_esc - img.data());
-    sc.flat_leaves = ctx->scene_blob + (p_flat - img.data());
-    sc.flat_ostride = flat_oriented ? (uint32_t)ostride_f4 : 0u;
-    sc.flat_rank = reinterpret_cast<const uint32_t *>(ctx->scene_blob + n_f4);
-    sc.pnodes = ctx->scene_blob + n_f4 + rank_f4;
-    sc.n_pnodes = n_pnodes;
-    sc.prim_rank = reinterpret_cast<const uint32_t *>(ctx->scene_blob + n_f4 + rank_f4 + pnode_f4);
-    sc.wnodes = ctx->scene_blob + n_f4 + rank_f4 + pnode_f4 + prank_f4;
-    sc.n_wnodes = (uint32_t)wide.size();
-    sc.wide_ok = wide_ok ? 1u : 0u;
-    sc.wide_deep = (wide_ok && wide_depth > RT_WSTACK + 1u) ? 1u : 0u;
-    sc.coop_ok = (wide_ok && n_primitives < RT_COOP_MAX_RECORDS && wide.size() < RT_COOP_MAX_NODES) ? 1u : 0u; // (build_wide_tree already bounds the depth at 25 wide levels)
+    sc.nodes = blob + im.nodes; sc.escape = blob + im.escape; sc.prims = blob + im.prims; sc.tri_normals = blob + im.tri_normals;
+    sc.materials = blob + im.materials; sc.fb_spheres = blob + im.fb_spheres; sc.fb_planes = blob + im.fb_planes;
+    sc.flat_leaves = blob + im.flat_leaves; sc.pnodes = blob + im.pnodes; sc.wnodes = blob + im.wnodes;
+    sc.flat_rank = reinterpret_cast<const uint32_t *>(blob + im.flat_rank);
+    sc.prim_rank = reinterpret_cast<const uint32_t *>(blob + im.prim_rank);
+    sc.n_nodes = im.n_nodes; sc.n_prims = im.n_prims; sc.n_tris = im.n_tris; sc.n_materials = im.n_materials;
+    sc.n_spheres = im.n_spheres; sc.n_planes = im.n_planes; sc.n_leaves = im.n_leaves; sc.n_pnodes = im.n_pnodes; sc.n_wnodes = im.n_wnodes;
+    sc.tri_mask_lo = im.tri_mask_lo; sc.tri_mask_hi = im.tri_mask_hi; sc.plane_mask_lo = im.plane_mask_lo; sc.plane_mask_hi = im.plane_mask_hi;
+    sc.flat_ok = im.flat_ok; sc.flat_ostride = im.flat_ostride; sc.typed_leaves = im.typed_leaves;
+    sc.wide_ok = im.wide_ok; sc.wide_deep = im.wide_deep; sc.coop_ok = im.coop_ok;
+    memcpy(sc.cull_min, im.cull_min, sizeof sc.cull_min);
+    memcpy(sc.cull_max, im.cull_max, sizeof sc.cull_max);
+    memcpy(sc.cull_mask, im.cull_mask, sizeof sc.cull_mask);
+    sc.cull_always = im.cull_always; sc.n_cull = im.n_cull;
+    sc.stack_entries = im.stack_entries;
     sc.lds_wnodes = 0u; // (set per launch, hybrid_stage)
-    ctx->wimg_nodes = wimg_nodes;
-    sc.flat_ok = flat_ok ? 1u : 0u;
-    sc.n_cull = 0; sc.cull_always = 0xffffffffu;
-    if (flat_ok) { // the interior nodes two levels below the root and the leaves under each (rt_device.h, RT_FLAT_CULL)
-        std::vector<uint32_t> leaf_index(n_nodes, 0u);
-        for (size_t k = 0; k < leaf_nodes.size(); k++) leaf_index[leaf_nodes[k]] = (uint32_t)k;
-        std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}}; // node, depth
-        uint32_t always = 0u;
-        const uint32_t cull_depth = 2u; // (1 / 2 / 3 below the root measured alike, profiles/r03_fusion_ab.txt)
-        while (!st.empty()) {
-            auto [i, d] = st.back();
-            st.pop_back();
-            const rsrt_bvh_node &nd = nodes[i];
-            if (nd.primitives_len != 0) { always |= 1u << leaf_index[i]; continue; }
-            if (d == cull_depth && sc.n_cull < 8) {
-                uint32_t m = 0;
-                std::vector<uint32_t> sub{i};
-                while (!sub.empty()) {
-                    const uint32_t j = sub.back();
-                    sub.pop_back();
-                    if (nodes[j].primitives_len != 0) m |= 1u << leaf_index[j];
-                    else { sub.push_back(j + 1); sub.push_back(nodes[j].primitives_or_second_child_index); }
-                }
-                for (int k = 0; k < 3; k++) { sc.cull_min[sc.n_cull][k] = nd.bounds_min[k]; sc.cull_max[sc.n_cull][k] = nd.bounds_max[k]; }
-                sc.cull_mask[sc.n_cull++] = m;
-                continue;
-            }
-            st.push_back({i + 1, d + 1});
-            st.push_back({nd.primitives_or_second_child_index, d + 1});
-        }
-        sc.cull_always = always;
-    }
-    sc.n_leaves = (uint32_t)leaf_nodes.size();
-    sc.tri_mask_lo = (uint32_t)tri_mask; sc.tri_mask_hi = (uint32_t)(tri_mask >> 32);
-    sc.plane_mask_lo = (uint32_t)plane_mask; sc.plane_mask_hi = (uint32_t)(plane_mask >> 32);
-    sc.n_nodes = n_nodes; sc.n_prims = n_primitives; sc.n_tris = n_triangles; sc.n_materials = n_materials;
-    sc.n_spheres = n_spheres; sc.n_planes = n_planes;
-    sc.stack_entries = depth + 1;
-    sc.typed_leaves = typed_leaves ? 1u : 0u;
     const size_t stack_bytes = (size_t)sc.stack_entries * RT_BLOCK * sizeof(uint32_t);
-    if (stack_bytes > 128 * 1024) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh depth %u exceeds the supported traversal stack", depth);
-    sc.lds_float4s = (n_f4 * sizeof(float4) <= kSmallImageBytes) ? (uint32_t)n_f4 : 0u; // whole image in LDS only while it leaves room for the path pools
+    if (stack_bytes > 128 * 1024) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bvh depth %u exceeds the supported traversal stack", sc.stack_entries - 1u); // (the one refusal that leaves the context without a scene)
+    sc.lds_float4s = im.lds_float4s; // whole image in LDS only while it leaves room for the path pools
     sc.lds_hybrid = 0;
     sc.lds_src = sc.nodes; // the image starts with the nodes
     ctx->hybrid_head_f4 = ctx->hybrid_pnode_f4 = 0;
+    ctx->wimg_nodes = 0;
     if (sc.lds_float4s == 0) { // mid-size: what every box step touches goes to LDS, one big workgroup per CU shares the copy
-        if (traversal_head_f4 * sizeof(float4) <= 40 * 1024) ctx->hybrid_head_f4 = (uint32_t)traversal_head_f4; // nodes + escape links (tree walks; the render call checks the room beside its pools)
-        ctx->hybrid_pnode_f4 = 2u * top_elems; // the top block of the fixed-order walk's nodes (all of them when the scene is mid-size)
-    } else {
-        ctx->wimg_nodes = 0; // (a small scene runs from its whole image)
+        if (im.traversal_head_f4 * sizeof(float4) <= 40 * 1024) ctx->hybrid_head_f4 = (uint32_t)im.traversal_head_f4; // nodes + escape links (tree walks; the render call checks the room beside its pools)
+        ctx->hybrid_pnode_f4 = 2u * im.top_elems; // the top block of the fixed-order walk's nodes (all of them when the scene is mid-size)
+        ctx->wimg_nodes = im.wimg_nodes; // the head of the wide-node array, as far as the room beside the launch's pools goes (hybrid_stage); a small scene runs from its whole image
     }
     memset(ctx->blocks_per_cu, 0, sizeof ctx->blocks_per_cu); // the kernels' dynamic LDS size depends on the scene: occupancy is asked for again
     ctx->scene_ready = true;
@@ -1956,18 +1386,39 @@ rsrt_status rsrt_build_bvh_device(rsrt_context *ctx, const rsrt_sphere *spheres,
     return RSRT_OK;
 }
 
-// The wide walk's tree for a BVH, on the host (no GPU needed): what rsrt_upload_scene builds for the device, exposed so that a CPU
-// test can walk it.  wnodes_out: 32 floats per wide node (DevScene::wnodes); *n_wnodes: capacity in, count out; old_of_new: for
-// every record index the walk uses, the index into `primitives` as given.  RSRT_ERR_INVALID_ARGUMENT: the scene does not qualify.
+// The scene's device image on the host (no context, no GPU needed): what rsrt_upload_scene copies to the device and the layout it
+// fills DevScene from (rt_scene_image.h), exposed so that a CPU test can read every table.  include/rsrt.h has the arguments.
+rsrt_status rsrt_scene_image_build(const rsrt_material *materials, uint32_t n_materials, const rsrt_sphere *spheres, uint32_t n_spheres,
+                                   const rsrt_plane *planes, uint32_t n_planes, const rsrt_vec3 *vertices, uint32_t n_vertices,
+                                   const rsrt_vec3 *normals, uint32_t n_normals, const rsrt_triangle *triangles, uint32_t n_triangles,
+                                   const rsrt_primitive_info *primitives, uint32_t n_primitives, const rsrt_bvh_node *nodes, uint32_t n_nodes,
+                                   uint32_t flat_oriented, float *image_out, size_t *n_float4, rsrt_scene_image_info *info_out)
+{
+    if (!n_float4) return RSRT_ERR_INVALID_ARGUMENT;
+    const SceneInputs in{materials, n_materials, spheres, n_spheres, planes, n_planes, vertices, n_vertices, normals, n_normals,
+                         triangles, n_triangles, primitives, n_primitives, nodes, n_nodes};
+    SceneImage built;
+    if (rsrt_status st = checked_scene_image(nullptr, in, flat_oriented != 0, built)) return st; // (rsrt_last_error(NULL) has the reason)
+    const size_t cap = *n_float4;
+    *n_float4 = built.image.size();
+    if (info_out) *info_out = built.info;
+    if (image_out) {
+        if (cap < built.image.size()) return fail(nullptr, RSRT_ERR_INVALID_ARGUMENT, "image_out holds %zu float4s, the image has %zu", cap, built.image.size());
+        memcpy(image_out, built.image.data(), built.image.size() * sizeof(float4));
+    }
+    return RSRT_OK;
+}
+
+// The wide walk's tree for a BVH, on the host (no GPU needed): the wnodes section of the scene image on its own, with the permutation
+// of the records, exposed so that a CPU test can walk it.  wnodes_out: 32 floats per wide node (DevScene::wnodes); *n_wnodes:
+// capacity in, count out; old_of_new: for every record index the walk uses, the index into `primitives` as given.
+// RSRT_ERR_INVALID_ARGUMENT: the scene does not qualify.
 rsrt_status rsrt_wide_tree_build(const rsrt_primitive_info *primitives, uint32_t n_primitives, const rsrt_bvh_node *nodes, uint32_t n_nodes,
                                  float *wnodes_out, uint32_t *n_wnodes, uint32_t *old_of_new)
 {
     if (!primitives || !nodes || !n_wnodes || n_nodes == 0) return RSRT_ERR_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < n_nodes; i++) { // (the checks of rsrt_upload_scene that keep the builder's indexing in bounds)
-        const rsrt_bvh_node &nd = nodes[i];
-        if (nd.primitives_len > 0) { if ((uint64_t)nd.primitives_or_second_child_index + nd.primitives_len > n_primitives) return RSRT_ERR_INVALID_ARGUMENT; }
-        else if (i + 1 >= n_nodes || nd.primitives_or_second_child_index <= i + 1 || nd.primitives_or_second_child_index >= n_nodes) return RSRT_ERR_INVALID_ARGUMENT;
-    }
+    uint32_t depth = 0;
+    if (!validate_tree(nodes, n_nodes, n_primitives, &depth).empty()) return RSRT_ERR_INVALID_ARGUMENT;
     std::vector<WideNode> wide;
     std::vector<rsrt_primitive_info> pp;
     std::vector<rsrt_bvh_node> np;

@@ -75,7 +75,7 @@ struct DevScene {
     uint32_t cull_mask[8], cull_always, n_cull;
     // fixed-order traversal (trace_preorder): its own node array — interior {min, link when hit}{max, link when missed},
     // leaf {min, first record | 1 << 31}{max, len | masks}, successor = next element — laid out top block first
-    // (rsrt_upload_scene); [8 octants][n_prims] visiting ranks
+    // (rt_scene_image.h, build_pnode_list); [8 octants][n_prims] visiting ranks
     const float4 *pnodes;
     uint32_t n_pnodes;
     const uint32_t *prim_rank;
@@ -1365,7 +1365,7 @@ RT_DEV void trace_flat(DBG_DECL const View &S, const DevScene &sc, V3 o, V3 d, V
 // tested in.  So the walk can take the ONE order that needs no side table: the node array's own pre-order.
 //   interior node, box hit    -> its first child           } both links are IN the node record (index words of its two
 //   interior node, box missed -> its subtree's successor   } float4s), so the array can be laid out in any order:
-//   leaf                      -> the next array element     the hottest nodes first, kept in LDS (rsrt_upload_scene)
+//   leaf                      -> the next array element     the hottest nodes first, kept in LDS (rt_scene_image.h)
 // Two 16-byte loads per step instead of three (no escape link), no octant-dependent addressing, and for a scene of any
 // size the top of the tree — where most box tests happen — is served by LDS instead of the vector L1, which is what
 // bounds the all-global walk (profiles/r02_bvh_*); same boxes, same primitives, same winner as cast_ray_bvh

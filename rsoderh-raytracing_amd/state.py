@@ -25,7 +25,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_upload_environment", "rsrt_set_partition", "rsrt_accumulator_resize", "rsrt_accumulator_bind",
             "rsrt_accumulator_clear", "rsrt_accumulator_download", "rsrt_resolve_mean_f16", "rsrt_debug_view_f16", "rsrt_render",
             "rsrt_synchronize", "rsrt_get_stats", "rsrt_cast_rays", "rsrt_describe", "rsrt_get_debug_counters", "rsrt_get_region_counters", "rsrt_get_walk_counters", "rsrt_display_srgb8",
-            "rsrt_selftest_numerics", "rsrt_selftest_sincos", "rsrt_build_id", "rsrt_wide_tree_build", "rsrt_build_bvh_device",
+            "rsrt_selftest_numerics", "rsrt_selftest_sincos", "rsrt_build_id", "rsrt_wide_tree_build", "rsrt_scene_image_build", "rsrt_build_bvh_device",
             "rsrt_partition_owner", "rsrt_partition_mask", "rsrt_partition_tiles", "rsrt_comm_available", "rsrt_comm_unique_id", "rsrt_comm_init", "rsrt_comm_reduce", "rsrt_comm_set_mode", "rsrt_comm_destroy",
             "rsrt_multi_create", "rsrt_multi_destroy", "rsrt_multi_last_error", "rsrt_multi_size", "rsrt_multi_context",
             "rsrt_multi_upload_scene", "rsrt_multi_upload_environment", "rsrt_multi_resize", "rsrt_multi_clear", "rsrt_multi_render",
@@ -168,6 +168,18 @@ class DenoiseParams(C.Structure):
                 ("sigma_depth", C.c_float)]
 
 
+class SceneImageInfo(C.Structure):
+    """rsrt_scene_image_info (include/rsrt.h): where each section of the scene's device image lies, in float4s, and the scalars
+    rsrt_upload_scene derives with it.  lib().rsrt_scene_image_build fills one on the CPU, without a context."""
+    _fields_ = ([(n, C.c_uint64) for n in ("nodes", "escape", "prims", "tri_normals", "materials", "fb_spheres", "fb_planes", "flat_leaves",
+                                            "flat_rank", "pnodes", "prim_rank", "wnodes", "n_float4", "traversal_head_f4")] +
+                [(n, C.c_uint32) for n in ("n_nodes", "n_prims", "n_tris", "n_materials", "n_spheres", "n_planes", "n_leaves", "n_pnodes",
+                                            "n_wnodes", "tri_mask_lo", "tri_mask_hi", "plane_mask_lo", "plane_mask_hi", "flat_ok", "flat_ostride",
+                                            "typed_leaves", "wide_ok", "wide_deep", "coop_ok", "stack_entries", "lds_float4s")] +
+                [("cull_min", C.c_float * 3 * 8), ("cull_max", C.c_float * 3 * 8), ("cull_mask", C.c_uint32 * 8)] +
+                [(n, C.c_uint32) for n in ("cull_always", "n_cull", "top_elems", "wimg_nodes", "small_image_bytes", "hybrid_room_f4", "_pad")])
+
+
 def build_id():
     """rsrt_build_id(): which kernel sources the loaded librsrt.so was compiled from."""
     return lib().rsrt_build_id().decode()
@@ -225,6 +237,7 @@ def lib():
         L.rsrt_selftest_numerics.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_selftest_sincos.argtypes = [C.c_void_p, C.c_void_p]
         L.rsrt_cast_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_scene_image_build.argtypes = [C.c_void_p, C.c_uint32] * 8 + [C.c_uint32, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(SceneImageInfo)]
         L.rsrt_partition_owner.restype = C.c_uint32
         L.rsrt_partition_owner.argtypes = [C.c_uint32] * 7
         L.rsrt_partition_mask.argtypes = [C.c_uint32] * 6 + [C.c_void_p, C.c_void_p]

@@ -1,4 +1,4 @@
-"""The flat traversal's per-octant leaf tables (rsrt_api.hip upload, rt_device.h trace_flat): each leaf box stored once per ray-sign
+"""The flat traversal's per-octant leaf tables (rt_scene_image.h build_scene_image, rt_device.h trace_flat): each leaf box stored once per ray-sign
 octant with its corners in slab order, so the leaf loop needs no min / max to order a box's slab values.
 
 CPU: the oriented slab decision equals the min / max one bit for bit on adversarial (box, ray) pairs, and the table layout (which
@@ -10,7 +10,7 @@ import pytest
 
 F = np.float32
 RT_INFINITY = F(1.70141183460469231732e+38)
-SMALL_IMAGE_BYTES = 24 * 1024  # (rsrt_api.hip kSmallImageBytes: the whole image goes to LDS up to this size)
+SMALL_IMAGE_BYTES = 24 * 1024  # (rsrt_api.hip kSmallImageBytes: the whole image goes to LDS up to this size; test_scene_image.py holds it against what the library reports)
 
 
 def minmax_miss(lo, hi, o, inv):
@@ -40,7 +40,7 @@ def orient(lo, hi, q):
 
 
 def build_tables(lo, hi, lo_mask, hi_mask):
-    """Python statement of the upload's table builder: [8 octants][stride] float4, leaf k at 2k: {near.xyz, mask lo}{far.xyz, mask hi}."""
+    """Python statement of build_scene_image's table builder (test_scene_image.py compares the two): [8 octants][stride] float4, leaf k at 2k: {near.xyz, mask lo}{far.xyz, mask hi}."""
     n = len(lo)
     stride = 2 * (n | 1)
     t = np.zeros((8 * stride, 4), np.float32)
@@ -137,7 +137,7 @@ def test_table_builder_puts_each_corner_in_place():
 
 
 def image_f4(sc, tables):
-    """float4s of the scene's LDS image (rsrt_api.hip upload): what decides whether the tables fit."""
+    """float4s of the scene's LDS image (rt_scene_image.h build_scene_image): what decides whether the tables fit."""
     nn = len(sc.bvh_nodes)
     leaves = int((sc.bvh_nodes["primitives_len"] > 0).sum())
     f4 = (2 * nn + 4 * len(sc.primitives) + 3 * len(sc.triangles) + 4 * len(sc.materials) + 4 * len(sc.spheres) + 4 * len(sc.planes)

@@ -86,7 +86,7 @@ def test_materials_of_one_lobe(colour, diff_prob):
 
 # ---------------------------------------------------------------------------------------------------- GEN's fused trace
 def cull_groups(sc):
-    """rsrt_upload_scene's two-level cull of a scene the flat loop takes: (always, [(box min, box max, leaf mask)]) — the leaves above
+    """The scene image's two-level cull (rt_scene_image.h fill_cull_groups; test_scene_image.py compares the two) of a scene the flat loop takes: (always, [(box min, box max, leaf mask)]) — the leaves above
     the cull depth, and the interior nodes two levels below the root with the leaves under each; leaves numbered in node order."""
     nodes = sc.bvh_nodes
     leaf_index = {i: k for k, i in enumerate(i for i in range(len(nodes)) if nodes[i]["primitives_len"] > 0)}
