@@ -694,6 +694,101 @@ rsrt_status rsrt_dof_depth_at(rsrt_context *ctx, uint32_t source, const rsrt_cam
 /* Rust: pub fn rsrt_dof_reset(ctx: *mut RsrtContext) -> i32; */
 rsrt_status rsrt_dof_reset(rsrt_context *ctx); /* drops the lens image */
 
+/* -- white balance and colour grading: a chroma meter, a LUT display (no reference counterpart) ----------------------------------
+ * The meter removes the picture's dependence on the environment's scale; nothing so far removes its dependence on the environment's
+ * COLOUR: a low sun or a warm HDRI puts a cast over all of it, and the display ends in one hard-wired ACES -> sRGB step with nowhere to
+ * put a look.  rsrt_white_meter builds, on the device and in integers, a 64 x 64 histogram of the log-chromaticity (log2 G/R, log2
+ * G/B; 16 bins an octave, -2 .. +2 octaves; word 4096 counts the pixels without three positive channels) of one of the five images
+ * the library can hold; rsrt_white_download turns it into a white point — per-channel gains that take the mode of the histogram,
+ * found by a gated mean shift, to grey at constant luminance.  rsrt_colour_lut_build bakes an ASC CDL (slope, offset, power,
+ * saturation) into an n^3 LUT on the device, rsrt_colour_lut_upload takes any LUT; the LUT's domain is the tone-mapped colour,
+ * square-root encoded on both sides.  rsrt_display_colour_srgb8 is the graded display pass (local exposure and bloom optional) with
+ * the white point multiplied in before the tone map and the LUT, read by tetrahedral interpolation, behind it.  The arithmetic is
+ * published in include/rsrt_colour.h and is bitwise reproducible.  The gains are per channel in the working RGB: no chromatic
+ * adaptation in a cone space is made, and the integrator knows nothing of the white point.
+ *
+ * The library keeps NO white point: adaptation over time goes through `previous` and `blend` (the State classes remember the last
+ * value).  The histogram stays valid until the next rsrt_white_meter, rsrt_white_reset or rsrt_context_destroy; the LUT until the next
+ * rsrt_colour_lut_build or _upload, rsrt_colour_lut_reset or rsrt_context_destroy; neither depends on the accumulator's size.  Whole
+ * frame only: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.  Nothing here writes the accumulator, the AOV buffer,
+ * the guide, any history, the denoised, upsampled or lens image, the exposure histogram, the bloom image or the local-exposure grid.
+ * A refused call launches nothing and leaves the last histogram and LUT as they were.
+ * rsrt_white_params defaults: gate 12, iterations 3, min_permille 50, strength 1, max_stops 2, blend 1, previous {0, 0, 0}, flags 0;
+ * rsrt_cdl_params defaults: the identity; the default LUT size is 33 (RSRT_WHITE_*, RSRT_CDL_*, RSRT_COLOUR_* in
+ * include/rsrt_colour.h). */
+typedef struct rsrt_white_params {
+    uint32_t gate;          /* 1 .. 31: half the width of the mean shift's window, in bins (1/16 octave) */
+    uint32_t iterations;    /* 0 .. 8 mean-shift steps */
+    uint32_t min_permille;  /* 0 .. 1000: no estimate when fewer than this share of all pixels lies in the final window */
+    float strength;         /* 0 .. 1: how much of the cast the gains remove */
+    float max_stops;        /* 0 .. 4: the most octaves a channel's gain moves, either way, before the luminance is put back */
+    float blend;            /* 0 .. 1: how far the white point moves from `previous` towards the target */
+    float previous[3];      /* all 0: none, the white point is the target; otherwise every channel finite and > 0 */
+    uint32_t flags;         /* 0 */
+} rsrt_white_params;
+typedef struct rsrt_white_result {
+    float white[3];         /* what to display with */
+    float target[3];        /* the gains of this histogram alone */
+    float illuminant[3];    /* the estimated cast, green 1 */
+    float eu, ev;           /* log2 G/R and log2 G/B of the estimate, octaves */
+    uint32_t gated;         /* pixels in the final window */
+    uint32_t counted, skipped; /* pixels in the 4096 bins; pixels without three positive channels */
+    uint32_t estimated;     /* 1: an estimate; 0: none (white = target = previous, or {1, 1, 1}) */
+    uint32_t _pad;
+} rsrt_white_result;
+typedef struct rsrt_cdl_params {
+    float slope[3];   /* 0 .. 16 */
+    float offset[3];  /* -1 .. 1 */
+    float power[3];   /* 0.25 .. 4 */
+    float saturation; /* 0 .. 4 */
+    uint32_t flags;   /* 0 */
+    uint32_t _pad;
+} rsrt_cdl_params;
+typedef struct rsrt_colour_params {
+    float white[3];     /* finite, > 0: multiplied in before the tone map */
+    float lut_strength; /* 0 .. 1: 0 skips the LUT, which then need not exist */
+    uint32_t flags;     /* 0 */
+    uint32_t _pad[3];
+} rsrt_colour_params;
+/* Builds the chroma histogram of `source` (RSRT_EXPOSURE_MEAN .. RSRT_EXPOSURE_LENS) in a library-owned buffer (one launch;
+ * asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far).  Sources, sample_total and errors
+ * as for rsrt_exposure_meter.
+ * Rust: pub fn rsrt_white_meter(ctx: *mut RsrtContext, source: u32, sample_total: u32, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_white_meter(rsrt_context *ctx, uint32_t source, uint32_t sample_total, void *hip_stream);
+/* Waits, copies the last histogram's 4097 words to host_hist and fills *out from it (rsrt_white_from_histogram, on the host).
+ * host_hist may be NULL (n_words is then ignored), out may be NULL.  RSRT_ERR_NOT_READY without a histogram since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for NULL params, params rsrt_white_params_ok refuses, n_words != 4097 with a non-NULL host_hist.
+ * Rust: pub fn rsrt_white_download(ctx: *mut RsrtContext, params: *const RsrtWhiteParams, host_hist: *mut u32, n_words: usize,
+ *                                  out: *mut RsrtWhiteResult) -> i32; */
+rsrt_status rsrt_white_download(rsrt_context *ctx, const rsrt_white_params *params, uint32_t *host_hist, size_t n_words, rsrt_white_result *out);
+/* Rust: pub fn rsrt_white_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_white_reset(rsrt_context *ctx); /* drops the histogram */
+/* Bakes the n^3 LUT of `cdl` on the device (rsrt_colour_lut_node per node; 16 bytes a node: 575 KB at n = 33); asynchronous on
+ * hip_stream.  RSRT_ERR_INVALID_ARGUMENT for an n other than 2, 3, 17, 33, 65, NULL cdl or one rsrt_cdl_params_ok refuses.
+ * Rust: pub fn rsrt_colour_lut_build(ctx: *mut RsrtContext, n: u32, cdl: *const RsrtCdlParams, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_colour_lut_build(rsrt_context *ctx, uint32_t n, const rsrt_cdl_params *cdl, void *hip_stream);
+/* Takes a LUT from the host: 3 * n^3 floats, rgb a node, red fastest, in the encoded domain.  RSRT_ERR_INVALID_ARGUMENT for an n
+ * other than 2, 3, 17, 33, 65, NULL, another n_floats, or any value that is not finite and in [0, 1].
+ * Rust: pub fn rsrt_colour_lut_upload(ctx: *mut RsrtContext, n: u32, host_rgb: *const f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_colour_lut_upload(rsrt_context *ctx, uint32_t n, const float *host_rgb, size_t n_floats);
+/* Waits and copies the LUT's 3 * n^3 floats to host_rgb; *n_out (may be NULL) receives n, which is all a call with host_rgb NULL
+ * and n_floats 0 asks for.  RSRT_ERR_NOT_READY without a LUT; RSRT_ERR_INVALID_ARGUMENT for another n_floats.
+ * Rust: pub fn rsrt_colour_lut_download(ctx: *mut RsrtContext, host_rgb: *mut f32, n_floats: usize, n_out: *mut u32) -> i32; */
+rsrt_status rsrt_colour_lut_download(rsrt_context *ctx, float *host_rgb, size_t n_floats, uint32_t *n_out);
+/* Rust: pub fn rsrt_colour_lut_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_colour_lut_reset(rsrt_context *ctx); /* drops the LUT */
+/* `source` through the colour display pass: rsrt_display_pixel_colour per pixel (include/rsrt_colour.h), RGBA8, alpha 255.  `local`
+ * may be NULL: the local gain is then 1 and no grid is needed.  With bloom_intensity 0 no bloom image is needed, with lut_strength 0
+ * no LUT.  With white {1, 1, 1} and lut_strength 0 the bytes are rsrt_display_local_srgb8's or, with a NULL local, those of
+ * rsrt_display_bloomed_srgb8 / rsrt_display_exposed_srgb8.  Errors as for rsrt_display_local_srgb8 (a NULL local is none), and
+ * RSRT_ERR_INVALID_ARGUMENT for NULL colour or one rsrt_colour_params_ok refuses (white not finite and > 0, lut_strength outside
+ * [0, 1], flags), RSRT_ERR_NOT_READY with lut_strength > 0 and no LUT.
+ * Rust: pub fn rsrt_display_colour_srgb8(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                        local: *const RsrtLocalParams, bloom_intensity: f32, colour: *const RsrtColourParams,
+ *                                        host_rgba8: *mut u8, n_bytes: usize) -> i32; */
+rsrt_status rsrt_display_colour_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                                      float bloom_intensity, const rsrt_colour_params *colour, uint8_t *host_rgba8, size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

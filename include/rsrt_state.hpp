@@ -14,6 +14,7 @@
 
 #include "rsrt.h"
 #include "rsrt_bloom.h"
+#include "rsrt_colour.h"
 #include "rsrt_dof.h"
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
@@ -413,6 +414,74 @@ public:
         check_ctx(rsrt_display_local_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), &p, bloom_intensity, out.data(), out.size()));
         return out;
     }
+    // -- white balance and colour grading (rsrt.h "white balance and colour grading"): one device, like the denoiser ----
+    static rsrt_white_params white_defaults()
+    {
+        return rsrt_white_params{RSRT_WHITE_GATE, RSRT_WHITE_ITERATIONS, RSRT_WHITE_MIN_PERMILLE, RSRT_WHITE_STRENGTH, RSRT_WHITE_MAX_STOPS, RSRT_WHITE_BLEND,
+                                 {0.0f, 0.0f, 0.0f}, 0u};
+    }
+    static rsrt_cdl_params cdl_defaults()
+    {
+        return rsrt_cdl_params{{RSRT_CDL_SLOPE, RSRT_CDL_SLOPE, RSRT_CDL_SLOPE}, {RSRT_CDL_OFFSET, RSRT_CDL_OFFSET, RSRT_CDL_OFFSET},
+                               {RSRT_CDL_POWER, RSRT_CDL_POWER, RSRT_CDL_POWER}, RSRT_CDL_SATURATION, 0u, 0u};
+    }
+    // the chroma histogram of `source` (RSRT_EXPOSURE_MEAN: the accumulator over sample_count() samples), built on the device
+    void white_meter(uint32_t source = RSRT_EXPOSURE_MEAN) { check_ctx(rsrt_white_meter(context(0), source, sample_count_, nullptr)); }
+    // the last white_meter(): its 4097 words (64 x 64 bins, the skipped pixels) and, when given, the white point of it under p
+    std::vector<uint32_t> white_download(const rsrt_white_params &p = white_defaults(), rsrt_white_result *result = nullptr)
+    {
+        std::vector<uint32_t> hist(RSRT_WHITE_WORDS);
+        check_ctx(rsrt_white_download(context(0), &p, hist.data(), hist.size(), result));
+        return hist;
+    }
+    // meters `source`, downloads with the remembered white point as `previous` and remembers the new one: the first call takes the
+    // target, later ones move a fraction `blend` of the way to it
+    rsrt_white_result auto_white_balance(uint32_t source = RSRT_EXPOSURE_MEAN, float blend = 1.0f, rsrt_white_params p = white_defaults())
+    {
+        white_meter(source);
+        p.blend = blend;
+        for (int i = 0; i < 3; i++) p.previous[i] = white_[i];
+        rsrt_white_result r;
+        white_download(p, &r);
+        for (int i = 0; i < 3; i++) white_[i] = r.white[i];
+        return r;
+    }
+    std::array<float, 3> white() const { return white_; } // the remembered white point (all 0: none)
+    void white_reset() // forgets the remembered white point and drops the histogram
+    {
+        white_ = {0.0f, 0.0f, 0.0f};
+        check_ctx(rsrt_white_reset(context(0)));
+    }
+    // bakes the CDL into a size^3 LUT on the device
+    void colour_lut(const rsrt_cdl_params &cdl = cdl_defaults(), uint32_t size = RSRT_COLOUR_LUT_SIZE)
+    {
+        check_ctx(rsrt_colour_lut_build(context(0), size, &cdl, nullptr));
+    }
+    // a LUT from the host: 3 * n^3 floats, red fastest, encoded rgb in [0, 1]
+    void colour_lut_upload(uint32_t n, const std::vector<float> &rgb) { check_ctx(rsrt_colour_lut_upload(context(0), n, rgb.data(), rgb.size())); }
+    std::vector<float> colour_lut_download(uint32_t *n_out = nullptr)
+    {
+        uint32_t n = 0;
+        check_ctx(rsrt_colour_lut_download(context(0), nullptr, 0, &n));
+        std::vector<float> out((size_t)n * n * n * 3);
+        check_ctx(rsrt_colour_lut_download(context(0), out.data(), out.size(), n_out));
+        return out;
+    }
+    void colour_lut_reset() { check_ctx(rsrt_colour_lut_reset(context(0))); } // drops the LUT
+    // `source` through the colour display at `exposure` (0: the remembered one, else 1): `white` (NULL: the remembered white point, else
+    // 1) before the tone map, the LUT behind it at lut_strength (negative: 1 with a LUT, 0 without); local: NULL for no local grade,
+    // else the last local_exposure()'s gain under it; with bloom_intensity > 0 the last bloom() is added.  Of the source's own size
+    std::vector<uint8_t> display_colour(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const float *white = nullptr, float lut_strength = -1.0f,
+                                        const rsrt_local_params *local = nullptr, float bloom_intensity = 0.0f)
+    {
+        const bool remembered = white_[0] != 0.0f;
+        rsrt_colour_params c{{1.0f, 1.0f, 1.0f}, lut_strength, 0u, {0u, 0u, 0u}};
+        for (int i = 0; i < 3; i++) c.white[i] = white ? white[i] : (remembered ? white_[i] : 1.0f);
+        if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
+        std::vector<uint8_t> out(source_pixels(source) * 4);
+        check_ctx(rsrt_display_colour_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, out.data(), out.size()));
+        return out;
+    }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------
     static rsrt_dof_params dof_defaults() { return rsrt_dof_params{RSRT_DOF_FOCUS_DISTANCE, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS}; }
     // the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) seen through the state's camera, built on the device; a
@@ -591,6 +660,7 @@ private:
     size_t last_hash_ = 0;
     bool have_hash_ = false;
     float exposure_ = 0.0f; // the last auto_exposure() (0: none since exposure_reset)
+    std::array<float, 3> white_ = {0.0f, 0.0f, 0.0f}; // the last auto_white_balance() (all 0: none since white_reset)
     float exposure_or_one(float exposure) const { return exposure != 0.0f ? exposure : (exposure_ != 0.0f ? exposure_ : 1.0f); }
     float focus_distance_ = 0.0f; // the last focus_at() that hit a surface (0: none)
     // the pixels of `source`: the guide's for RSRT_EXPOSURE_UPSAMPLED, what the library holds for RSRT_EXPOSURE_LENS, else the state's own

@@ -661,6 +661,15 @@ struct rsrt_context {
     // NULL: no lens image since the last reset)
     SizedAlloc df_buf;
     ImageView df_last;
+    // white balance and colour grading (rt_colour.h): two chroma histograms, kept as the exposure meter keeps its two, and the colour LUT
+    // (cl_cap float4 nodes of room; cl_n the LUT's size, 0: none).  Neither follows the accumulator's size: accumulator_size_changed()
+    // leaves them.  The library keeps no white point.
+    uint32_t *wb_hist = nullptr;
+    uint32_t wb_cur = 0;
+    bool wb_have = false, wb_dirty = false;
+    float4 *cl_lut = nullptr;
+    size_t cl_cap = 0;
+    uint32_t cl_n = 0;
 };
 
 namespace {
@@ -724,7 +733,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h, rt_colour.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -1204,6 +1213,8 @@ void rsrt_context_destroy(rsrt_context *ctx)
     release(ctx->up_out);
     (void)hipFree(ctx->ns_tiles);
     (void)hipFree(ctx->ex_hist);
+    (void)hipFree(ctx->wb_hist);
+    (void)hipFree(ctx->cl_lut);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);
         (void)hipFree(L.cold_state);
@@ -1925,3 +1936,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_local.h"
 #include "rt_dof.h"
 #include "rt_sky.h"
+#include "rt_colour.h"

@@ -40,7 +40,9 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_local_exposure", "rsrt_local_exposure_download", "rsrt_local_exposure_reset", "rsrt_local_gain_download",
             "rsrt_display_local_srgb8",
             "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset",
-            "rsrt_environment_sky", "rsrt_environment_download"]
+            "rsrt_environment_sky", "rsrt_environment_download",
+            "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
+            "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -136,6 +138,40 @@ DOF_DEFAULTS = {"focus_distance": 1.0, "aperture": 0.01, "max_radius": 8, "flags
 
 class DofParams(C.Structure):
     _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# white balance and colour grading (include/rsrt.h "white balance and colour grading", include/rsrt_colour.h): the meter's defaults,
+# the identity CDL, the LUT sizes and the parameter blocks
+WHITE_WORDS = 4097
+WHITE_DEFAULTS = {"gate": 12, "iterations": 3, "min_permille": 50, "strength": 1.0, "max_stops": 2.0, "blend": 1.0, "previous": (0.0, 0.0, 0.0)}
+CDL_DEFAULTS = {"slope": 1.0, "offset": 0.0, "power": 1.0, "saturation": 1.0}
+COLOUR_LUT_SIZES = (2, 3, 17, 33, 65)
+
+
+class WhiteParams(C.Structure):
+    _fields_ = [("gate", C.c_uint32), ("iterations", C.c_uint32), ("min_permille", C.c_uint32), ("strength", C.c_float), ("max_stops", C.c_float),
+                ("blend", C.c_float), ("previous", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+class WhiteResult(C.Structure):
+    _fields_ = [("white", C.c_float * 3), ("target", C.c_float * 3), ("illuminant", C.c_float * 3), ("eu", C.c_float), ("ev", C.c_float),
+                ("gated", C.c_uint32), ("counted", C.c_uint32), ("skipped", C.c_uint32), ("estimated", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class CdlParams(C.Structure):
+    _fields_ = [("slope", C.c_float * 3), ("offset", C.c_float * 3), ("power", C.c_float * 3), ("saturation", C.c_float), ("flags", C.c_uint32),
+                ("_pad", C.c_uint32)]
+
+    @classmethod
+    def of(cls, slope=None, offset=None, power=None, saturation=None, flags=0):
+        """CDL_DEFAULTS where None; slope, offset and power are one number for all channels or three."""
+        q = {"slope": slope, "offset": offset, "power": power}
+        three = lambda k: (C.c_float * 3)(*np.broadcast_to(np.asarray(CDL_DEFAULTS[k] if q[k] is None else q[k], np.float32), (3,)))  # noqa: E731
+        return cls(three("slope"), three("offset"), three("power"), CDL_DEFAULTS["saturation"] if saturation is None else saturation, flags, 0)
+
+
+class ColourParams(C.Structure):
+    _fields_ = [("white", C.c_float * 3), ("lut_strength", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 3)]
 
 
 # the procedural daylight sky (include/rsrt.h rsrt_environment_sky, include/rsrt_sky.h): its defaults (RSRT_SKY_*) and its parameters.
@@ -310,6 +346,14 @@ def lib():
         L.rsrt_dof_reset.argtypes = [C.c_void_p]
         L.rsrt_environment_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_environment_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.rsrt_white_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_white_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_white_reset.argtypes = [C.c_void_p]
+        L.rsrt_colour_lut_build.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_colour_lut_upload.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+        L.rsrt_colour_lut_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_colour_lut_reset.argtypes = [C.c_void_p]
+        L.rsrt_display_colour_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -340,6 +384,7 @@ class State:
         self.guide_width = self.guide_height = 0  # the guide's size: what upsample() returns
         self._guide_bound = False
         self.exposure = None            # the last auto_exposure() (None: none since exposure_reset)
+        self.white = None               # the last auto_white_balance()'s white point (None: none since white_reset)
         self.focus_distance = None      # the last focus_at() that hit a surface (None: depth_of_field takes DOF_DEFAULTS')
         self._env_sizes = {}            # slot -> (width, height) of what upload_environment / environment_sky put there
 
@@ -824,6 +869,85 @@ class State:
         n = self.sample_count if sample_total is None else sample_total
         self._check(self._L.rsrt_display_local_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
+        return out
+
+    # -- white balance and colour grading (include/rsrt.h "white balance and colour grading") ---------------
+    def white_meter(self, source="mean", sample_total=None, stream=None):
+        """rsrt_white_meter: builds the chroma histogram of `source` ("mean": the accumulator over sample_total, default sample_count;
+        "denoised", "temporal", "upsampled", "lens") on the device.  Asynchronous."""
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_white_meter(self._ctx, IMAGE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
+
+    def white_download(self, **params):
+        """rsrt_white_download of the last white_meter(): (histogram, 4097 uint32: 64 x 64 bins, v-major, and the skipped pixels; result
+        dict with white, target, illuminant (3 floats each), eu, ev, gated, counted, skipped, estimated).  params: rsrt_white_params
+        fields, WHITE_DEFAULTS otherwise."""
+        q = dict(WHITE_DEFAULTS, **params)
+        p = WhiteParams(q["gate"], q["iterations"], q["min_permille"], q["strength"], q["max_stops"], q["blend"], (C.c_float * 3)(*q["previous"]),
+                        q.get("flags", 0))
+        hist = np.zeros(WHITE_WORDS, np.uint32)
+        r = WhiteResult()
+        self._check(self._L.rsrt_white_download(self._ctx, C.byref(p), _p(hist), hist.size, C.byref(r)), "rsrt_white_download")
+        return hist, {"white": tuple(r.white), "target": tuple(r.target), "illuminant": tuple(r.illuminant), "eu": r.eu, "ev": r.ev, "gated": r.gated,
+                      "counted": r.counted, "skipped": r.skipped, "estimated": bool(r.estimated)}
+
+    def auto_white_balance(self, source="mean", blend=1.0, **params):
+        """Meters `source`, downloads with the remembered white point as `previous` and remembers the new one (self.white): the first
+        call takes the target, later ones move a fraction `blend` of the way to it.  Returns the result dict."""
+        self.white_meter(source)
+        _, r = self.white_download(blend=blend, previous=self.white or (0.0, 0.0, 0.0), **params)
+        self.white = r["white"]
+        return r
+
+    def white_reset(self):
+        """Forgets the remembered white point and drops the histogram."""
+        self.white = None
+        self._check(self._L.rsrt_white_reset(self._ctx), "rsrt_white_reset")
+
+    def colour_lut(self, slope=None, offset=None, power=None, saturation=None, size=33, stream=None):
+        """rsrt_colour_lut_build: bakes the ASC CDL (slope, offset, power: one number or three; saturation; CDL_DEFAULTS otherwise) into
+        a size^3 LUT on the device.  Asynchronous."""
+        p = CdlParams.of(slope, offset, power, saturation)
+        self._check(self._L.rsrt_colour_lut_build(self._ctx, size, C.byref(p), C.c_void_p(stream) if stream else None), "rsrt_colour_lut_build")
+
+    def colour_lut_upload(self, nodes):
+        """rsrt_colour_lut_upload: nodes [n, n, n, 3] float32 (blue, green, red index; encoded rgb in [0, 1])."""
+        nodes = np.ascontiguousarray(nodes, np.float32)
+        self._check(self._L.rsrt_colour_lut_upload(self._ctx, nodes.shape[0] if nodes.ndim else 0, _p(nodes), nodes.size), "rsrt_colour_lut_upload")
+
+    def colour_lut_download(self):
+        """rsrt_colour_lut_download: the LUT, [n, n, n, 3] float32 (blue, green, red index)."""
+        n = C.c_uint32()
+        self._check(self._L.rsrt_colour_lut_download(self._ctx, None, 0, C.byref(n)), "rsrt_colour_lut_download")
+        out = np.empty((n.value, n.value, n.value, 3), np.float32)
+        self._check(self._L.rsrt_colour_lut_download(self._ctx, _p(out), out.size, None), "rsrt_colour_lut_download")
+        return out
+
+    def colour_lut_reset(self):
+        """Drops the LUT."""
+        self._check(self._L.rsrt_colour_lut_reset(self._ctx), "rsrt_colour_lut_reset")
+
+    def _has_colour_lut(self):
+        return self._L.rsrt_colour_lut_download(self._ctx, None, 0, None) == 0
+
+    def display_colour_srgb8(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
+                             sample_total=None, **params):
+        """rsrt_display_colour_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1) with `white`
+        (None: the remembered white point, else (1, 1, 1)) multiplied in before the tone map and the LUT behind it at `lut_strength`
+        (None: 1 with a LUT, 0 without).  shadows, highlights: both None for no local grade, otherwise the last local_exposure()'s gain
+        with them (LOCAL_DEFAULTS for the one left None; params: key, max_stops); bloom_intensity > 0 adds the last bloom().
+        [H, W, 4] uint8, of the source's own size."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        if white is None:
+            white = (1.0, 1.0, 1.0) if self.white is None else self.white
+        if lut_strength is None:
+            lut_strength = 1.0 if self._has_colour_lut() else 0.0
+        c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+                                                      C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), _p(out), out.size),
+                    "rsrt_display_colour_srgb8")
         return out
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------

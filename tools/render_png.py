@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -13,7 +13,11 @@ infinity as a fraction of the picture's height and at most RADIUS pixels (defaul
 then meter, bloom and grade the lens image.
 sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]: environment 0 is the procedural daylight sky (State.environment_sky, 2048 x 1024, built on the
 device: no map is prepared on the host) with the sun at that elevation and azimuth in degrees, instead of the synthetic map; it
-composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it."""
+composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it.
+wb=auto: meter the chroma of the picture that is written (State.auto_white_balance), print the white point and multiply it in before the
+tone map; wb=R,G,B: those gains.  cdl=SLOPE,OFFSET,POWER,SAT: bake that ASC CDL into a 33^3 LUT on the device (State.colour_lut) and read
+the tone-mapped picture through it.  Either one sends the picture through the colour display (State.display_colour_srgb8), which
+composes with exposure= (1 without), bloom=, local=, dof= and sky=:  house 960 540 64 8 out.png sky=8,120 exposure=auto wb=auto"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -31,7 +35,11 @@ if local is not None:
     local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
 dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
 sky = next((a[len("sky="):].split(",") for a in sys.argv[1:] if a.startswith("sky=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "sky="))]
+wb = next((a[len("wb="):] for a in sys.argv[1:] if a.startswith("wb=")), None)
+if wb is not None and wb != "auto":
+    wb = tuple(float(v) for v in wb.split(","))
+cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "sky=", "wb=", "cdl="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
@@ -66,7 +74,22 @@ if exposure == "auto":
     r = st.auto_exposure(source)
     print("metered exposure %.6g, average luminance %.6g (%d pixels metered, %d skipped)" % (r["exposure"], r["average_luminance"], r["metered"], r["skipped"]))
     exposure = r["exposure"]
-if local is not None:
+if wb is not None or cdl is not None:
+    if wb == "auto":
+        r = st.auto_white_balance(source)
+        print("white point %.4f %.4f %.4f (illuminant %.4f 1 %.4f; %d of %d pixels in the window%s)" % (r["white"] + (r["illuminant"][0], r["illuminant"][2], r["gated"],
+              r["counted"] + r["skipped"], "" if r["estimated"] else ": too few, no estimate")))
+        wb = r["white"]
+    if cdl is not None:
+        st.colour_lut(*cdl)
+    if bloom is not None:
+        st.bloom(source, exposure)
+    if local is not None:
+        st.local_exposure(source)
+        strengths = {"shadows": R.state.LOCAL_DEFAULTS["shadows"] if local[0] is None else local[0], "highlights": local[1]}
+    host.write_png(out, st.display_colour_srgb8(source, 1.0 if exposure is None else exposure, wb or (1.0, 1.0, 1.0), 1.0 if cdl is not None else 0.0,
+                                                bloom_intensity=bloom or 0.0, **(strengths if local is not None else {})))
+elif local is not None:
     if bloom is not None:
         st.bloom(source, exposure)
     st.local_exposure(source)
