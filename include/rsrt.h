@@ -694,6 +694,59 @@ rsrt_status rsrt_dof_depth_at(rsrt_context *ctx, uint32_t source, const rsrt_cam
 /* Rust: pub fn rsrt_dof_reset(ctx: *mut RsrtContext) -> i32; */
 rsrt_status rsrt_dof_reset(rsrt_context *ctx); /* drops the lens image */
 
+/* -- camera motion blur: a velocity pass, tile maxima, a line gather (no reference counterpart) -----------------------------------
+ * The integrator exposes every frame for an instant, so a camera that moves strobes from frame to frame.  The scene is static: the
+ * camera's motion is all the motion there is, and rsrt_motion_blur blurs one of the five images the library can hold along it.  Per
+ * pixel a velocity u from the first-hit distance in the pixel's AOV or guide record, the camera the source was rendered with and the
+ * camera one frame earlier (while the shutter is open the pixel's image travels from p - u to p + u, |u| at most max_radius pixels);
+ * per 16 x 16 tile the velocity of greatest length, and the greatest of those over the 3 x 3 tiles around each tile; then `taps` taps
+ * along that neighbourhood velocity, each weighed by whether it or the pixel can reach the other and which of them is in front.  A
+ * tile whose neighbourhood moves by less than half a pixel is copied.  It is a blur of LINEAR, UNEXPOSED radiance: it runs after
+ * rsrt_dof and before the meter, bloom, local exposure, the white meter and their displays, which take its output, the motion image,
+ * as their source RSRT_EXPOSURE_MOTION.  The motion image has the size of the source it was built from.  The arithmetic is published
+ * in include/rsrt_motion.h and is bitwise reproducible.  With `previous` equal to `camera`, or shutter 0, the motion image is the
+ * source's colour bit for bit.  The library keeps no camera and no shutter state.
+ *
+ * Sources RSRT_EXPOSURE_MEAN, _DENOISED and _TEMPORAL read the AOV buffer, which must have the accumulator's size;
+ * RSRT_EXPOSURE_UPSAMPLED reads the guide, which must have the upsampled image's size; RSRT_EXPOSURE_LENS reads the records the lens
+ * image was built from.  The motion image and its size stay valid until the next rsrt_motion_blur, rsrt_motion_reset, a change of the
+ * accumulator's size or rsrt_context_destroy.  Whole frame only.  Nothing here writes any other image or buffer of the context.  A
+ * refused call launches nothing and leaves the last motion image as it was.
+ * rsrt_motion_params defaults: shutter 0.5, max_radius 16, taps 16, flags 0 (RSRT_MOTION_* in include/rsrt_motion.h). */
+enum { RSRT_EXPOSURE_MOTION = 5 }; /* the last rsrt_motion_blur output: a source of the meters, bloom, local exposure and the displays */
+typedef struct rsrt_motion_params {
+    float shutter;       /* finite, in [0, 1]: the fraction of the frame interval the shutter is open (0.5: a 180 degree shutter) */
+    uint32_t max_radius; /* 1 .. 16 (RSRT_MOTION_MAX_RADIUS): the largest blur half-length, in pixels */
+    uint32_t taps;       /* even, 2 .. 32: taps along the line */
+    uint32_t flags;      /* 0 */
+} rsrt_motion_params;
+/* Builds the motion image of `source` (RSRT_EXPOSURE_MEAN .. _LENS) seen through `camera` (the one the source and its records were
+ * rendered with) after `previous` (the camera one frame earlier) into device_out_rgba32f (device memory, W x H x 4 f32, 16-byte
+ * aligned, alpha 1) or, when that is NULL, into library-owned memory; 44 bytes of library-owned scratch a pixel either way.
+ * Asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far.  sample_total is ignored for
+ * all sources but RSRT_EXPOSURE_MEAN.  RSRT_ERR_NOT_READY when the source image or its records do not exist;
+ * RSRT_ERR_INVALID_ARGUMENT for NULL camera, previous or params, params rsrt_motion_params_ok refuses, RSRT_EXPOSURE_MOTION or an
+ * unknown source, sample_total 0 under RSRT_EXPOSURE_MEAN, records of another size than the source, a misaligned output pointer.
+ * Rust: pub fn rsrt_motion_blur(ctx: *mut RsrtContext, source: u32, sample_total: u32, camera: *const RsrtCamera, previous: *const RsrtCamera,
+ *                               params: *const RsrtMotionParams, device_out_rgba32f: *mut c_void, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_motion_blur(rsrt_context *ctx, uint32_t source, uint32_t sample_total, const rsrt_camera *camera, const rsrt_camera *previous,
+                             const rsrt_motion_params *params, void *device_out_rgba32f, void *hip_stream);
+/* Waits and copies the motion image to host_rgba as RGBA32F, alpha 1; *width and *height (either may be NULL) receive its size, which
+ * is all a call with host_rgba NULL and n_floats 0 asks for.  RSRT_ERR_NOT_READY without a motion image since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for another n_floats than 4 a pixel.
+ * Rust: pub fn rsrt_motion_download(ctx: *mut RsrtContext, host_rgba: *mut f32, n_floats: usize, width: *mut u32, height: *mut u32) -> i32; */
+rsrt_status rsrt_motion_download(rsrt_context *ctx, float *host_rgba, size_t n_floats, uint32_t *width, uint32_t *height);
+/* Waits and copies the velocities of the last rsrt_motion_blur, 3 f32 a pixel (ux, uy, l), so that the velocity step can be held bit
+ * for bit.  Errors as for rsrt_motion_download, with n_floats three a pixel.
+ * Rust: pub fn rsrt_motion_velocity_download(ctx: *mut RsrtContext, host_uvl: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_motion_velocity_download(rsrt_context *ctx, float *host_uvl, size_t n_floats);
+/* Waits and copies every tile's own maximum of the last rsrt_motion_blur, 3 f32 a tile (ux, uy, l), rows of *tiles_x; *tiles_x and
+ * *tiles_y (either may be NULL) receive the tile counts, which is all a call with host_uvl NULL and n_floats 0 asks for.
+ * Rust: pub fn rsrt_motion_tiles_download(ctx: *mut RsrtContext, host_uvl: *mut f32, n_floats: usize, tiles_x: *mut u32, tiles_y: *mut u32) -> i32; */
+rsrt_status rsrt_motion_tiles_download(rsrt_context *ctx, float *host_uvl, size_t n_floats, uint32_t *tiles_x, uint32_t *tiles_y);
+/* Rust: pub fn rsrt_motion_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_motion_reset(rsrt_context *ctx); /* drops the motion image */
+
 /* -- white balance and colour grading: a chroma meter, a LUT display (no reference counterpart) ----------------------------------
  * The meter removes the picture's dependence on the environment's scale; nothing so far removes its dependence on the environment's
  * COLOUR: a low sun or a warm HDRI puts a cast over all of it, and the display ends in one hard-wired ACES -> sRGB step with nowhere to

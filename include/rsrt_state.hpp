@@ -16,6 +16,7 @@
 #include "rsrt_bloom.h"
 #include "rsrt_colour.h"
 #include "rsrt_dof.h"
+#include "rsrt_motion.h"
 #include "rsrt_exposure.h"
 #include "rsrt_host.h"
 #include "rsrt_local.h"
@@ -519,6 +520,48 @@ public:
     }
     float focus_distance() const { return focus_distance_; } // the remembered focus distance (0: none)
     void dof_reset() { check_ctx(rsrt_dof_reset(context(0))); } // drops the lens image
+    // -- camera motion blur (rsrt.h "camera motion blur"): one device, like the denoiser -----------------------------------
+    static rsrt_motion_params motion_defaults() { return rsrt_motion_params{RSRT_MOTION_SHUTTER, RSRT_MOTION_RADIUS, RSRT_MOTION_TAPS, RSRT_MOTION_FLAGS}; }
+    // the motion image of `source` (RSRT_EXPOSURE_MEAN .. _LENS) seen through the state's camera after `previous`, the camera one frame
+    // earlier, built on the device.  previous NULL: the camera of this state's last motion_blur(); on the first call, or after
+    // motion_reset(), the current camera, and the output is the source.  Every call remembers its camera afterwards (the library keeps
+    // none).  The later passes take the result as RSRT_EXPOSURE_MOTION.
+    void motion_blur(uint32_t source = RSRT_EXPOSURE_MEAN, const rsrt_camera_desc *previous = nullptr, rsrt_motion_params p = motion_defaults())
+    {
+        rsrt_camera cam, prev;
+        rsrt_camera_uniform(&camera_, &cam);
+        rsrt_camera_uniform(previous ? previous : (have_motion_camera_ ? &motion_camera_ : &camera_), &prev);
+        check_ctx(rsrt_motion_blur(context(0), source, sample_count_, &cam, &prev, &p, nullptr, nullptr));
+        motion_camera_ = camera_;
+        have_motion_camera_ = true;
+    }
+    // the last motion_blur(): RGBA32F, alpha 1, of its source's size; the size where asked for
+    std::vector<float> motion_download(uint32_t *width = nullptr, uint32_t *height = nullptr)
+    {
+        std::vector<float> out(source_pixels(RSRT_EXPOSURE_MOTION) * 4);
+        check_ctx(rsrt_motion_download(context(0), out.data(), out.size(), width, height));
+        return out;
+    }
+    std::vector<float> motion_velocity() // the velocities of the last motion_blur(), in pixels: ux, uy, l a pixel
+    {
+        std::vector<float> out(source_pixels(RSRT_EXPOSURE_MOTION) * 3);
+        check_ctx(rsrt_motion_velocity_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    // every 16 x 16 tile's own maximum of the last motion_blur(): ux, uy, l a tile, rows of *tiles_x
+    std::vector<float> motion_tiles(uint32_t *tiles_x = nullptr, uint32_t *tiles_y = nullptr)
+    {
+        uint32_t tx = 0, ty = 0;
+        check_ctx(rsrt_motion_tiles_download(context(0), nullptr, 0, &tx, &ty));
+        std::vector<float> out((size_t)tx * ty * 3);
+        check_ctx(rsrt_motion_tiles_download(context(0), out.data(), out.size(), tiles_x, tiles_y));
+        return out;
+    }
+    void motion_reset() // drops the motion image and forgets the remembered camera
+    {
+        have_motion_camera_ = false;
+        check_ctx(rsrt_motion_reset(context(0)));
+    }
     // -- the procedural sky (rsrt.h rsrt_environment_sky, rsrt_sky.h) -----------------------------------------------------------
     static rsrt_sky_params sky_defaults()
     {
@@ -663,9 +706,16 @@ private:
     std::array<float, 3> white_ = {0.0f, 0.0f, 0.0f}; // the last auto_white_balance() (all 0: none since white_reset)
     float exposure_or_one(float exposure) const { return exposure != 0.0f ? exposure : (exposure_ != 0.0f ? exposure_ : 1.0f); }
     float focus_distance_ = 0.0f; // the last focus_at() that hit a surface (0: none)
-    // the pixels of `source`: the guide's for RSRT_EXPOSURE_UPSAMPLED, what the library holds for RSRT_EXPOSURE_LENS, else the state's own
+    rsrt_camera_desc motion_camera_{}; // the camera of the last motion_blur()
+    bool have_motion_camera_ = false;
+    // the pixels of `source`: the guide's for RSRT_EXPOSURE_UPSAMPLED, what the library holds for RSRT_EXPOSURE_LENS and _MOTION, else the state's own
     size_t source_pixels(uint32_t source)
     {
+        if (source == RSRT_EXPOSURE_MOTION) {
+            uint32_t w = 0, h = 0;
+            check_ctx(rsrt_motion_download(context(0), nullptr, 0, &w, &h));
+            return (size_t)w * h;
+        }
         if (source == RSRT_EXPOSURE_LENS) {
             uint32_t w = 0, h = 0;
             check_ctx(rsrt_dof_download(context(0), nullptr, 0, &w, &h));

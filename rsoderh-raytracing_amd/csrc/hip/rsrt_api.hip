@@ -514,7 +514,7 @@ struct ImageView {
     float total = 1.0f;
     size_t pixels() const { return (size_t)w * h; }
 };
-enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3, IMAGE_LENS = 4 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
+enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3, IMAGE_LENS = 4, IMAGE_MOTION = 5 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
 
 struct rsrt_context {
     int device = 0;
@@ -661,6 +661,12 @@ struct rsrt_context {
     // NULL: no lens image since the last reset)
     SizedAlloc df_buf;
     ImageView df_last;
+    const PixelBuffer *df_rec = nullptr; // the records the lens image was built from (the AOV buffer or the guide): rsrt_motion_blur of it reads them
+    // camera motion blur (rt_motion.h): the prepared texels of the last rsrt_motion_blur (colour and l, z, u) and the library-owned motion
+    // image, one allocation that follows the size of the source the motion image was built from; the tiles' maxima, which follow the tile
+    // counts; and where the last rsrt_motion_blur wrote (img NULL: no motion image since the last reset).  The library keeps no camera.
+    SizedAlloc mt_buf, mt_tiles;
+    ImageView mt_last;
     // white balance and colour grading (rt_colour.h): two chroma histograms, kept as the exposure meter keeps its two, and the colour LUT
     // (cl_cap float4 nodes of room; cl_n the LUT's size, 0: none).  Neither follows the accumulator's size: accumulator_size_changed()
     // leaves them.  The library keeps no white point.
@@ -733,7 +739,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h, rt_colour.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h, rt_colour.h, rt_motion.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -860,6 +866,9 @@ void accumulator_size_changed(rsrt_context *ctx)
     ctx->lc_have = false;
     release(ctx->df_buf);
     ctx->df_last = ImageView{};
+    release(ctx->mt_buf);
+    release(ctx->mt_tiles);
+    ctx->mt_last = ImageView{};
 }
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -910,6 +919,10 @@ rsrt_status resolve_image(rsrt_context *ctx, const char *what, const char *prefi
     case IMAGE_LENS:
         if (!ctx->df_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno lens image (rsrt_dof first)", prefix);
         *v = ctx->df_last;
+        return RSRT_OK;
+    case IMAGE_MOTION:
+        if (!ctx->mt_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno motion image (rsrt_motion_blur first)", prefix);
+        *v = ctx->mt_last;
         return RSRT_OK;
     default:
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
@@ -1937,3 +1950,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_dof.h"
 #include "rt_sky.h"
 #include "rt_colour.h"
+#include "rt_motion.h"

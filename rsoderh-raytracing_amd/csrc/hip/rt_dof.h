@@ -149,6 +149,7 @@ rsrt_status rsrt_dof(rsrt_context *ctx, uint32_t source, uint32_t sample_total, 
                                                                                                                                            R, out);
     HIP_TRY(ctx, hipGetLastError());
     ctx->df_last = ImageView{out, v.w, v.h, 1.0f};
+    ctx->df_rec = rec;
     return end_work(ctx, stream);
 }
 

@@ -40,6 +40,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_local_exposure", "rsrt_local_exposure_download", "rsrt_local_exposure_reset", "rsrt_local_gain_download",
             "rsrt_display_local_srgb8",
             "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset",
+            "rsrt_motion_blur", "rsrt_motion_download", "rsrt_motion_velocity_download", "rsrt_motion_tiles_download", "rsrt_motion_reset",
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
             "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8"]
@@ -138,6 +139,30 @@ DOF_DEFAULTS = {"focus_distance": 1.0, "aperture": 0.01, "max_radius": 8, "flags
 
 class DofParams(C.Structure):
     _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("max_radius", C.c_uint32), ("flags", C.c_uint32)]
+
+
+# camera motion blur (include/rsrt.h "camera motion blur", include/rsrt_motion.h): the sources the passes after it can read — the five
+# images and the motion image the pass leaves — its tile, its defaults and its parameters
+DISPLAY_SOURCES = dict(IMAGE_SOURCES, motion=5)
+MOTION_TILE = 16
+MOTION_MAX_RADIUS = 16
+MOTION_DEFAULTS = {"shutter": 0.5, "max_radius": 16, "taps": 16, "flags": 0}
+
+
+class MotionParams(C.Structure):
+    _fields_ = [("shutter", C.c_float), ("max_radius", C.c_uint32), ("taps", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def camera_earlier(camera, yaw=0.0, dolly=0.0):
+    """The rsrt_camera record of the camera one frame before `camera` (a record like State.camera), for motion_blur(previous=...):
+    turned back by `yaw` radians about the world's up axis (+y) and moved back by `dolly` scene units along camera's forward axis."""
+    prev = np.array(camera).view(T.CAMERA).reshape(1).copy()
+    axes = prev["rot_transform"][0][:, :3].astype(np.float64)  # row j: the camera's axis j (right, up, backward) in the world
+    c, s = np.cos(-yaw), np.sin(-yaw)
+    if yaw:
+        prev["rot_transform"][0][:, :3] = (np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]]) @ axes.T).T
+    prev["pos"][0] = prev["pos"][0].astype(np.float64) + dolly * axes[2]
+    return prev
 
 
 # white balance and colour grading (include/rsrt.h "white balance and colour grading", include/rsrt_colour.h): the meter's defaults,
@@ -344,6 +369,11 @@ def lib():
         L.rsrt_dof_coc_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_dof_depth_at.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_dof_reset.argtypes = [C.c_void_p]
+        L.rsrt_motion_blur.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rsrt_motion_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.rsrt_motion_velocity_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_motion_tiles_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.rsrt_motion_reset.argtypes = [C.c_void_p]
         L.rsrt_environment_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_environment_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
         L.rsrt_white_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -386,6 +416,7 @@ class State:
         self.exposure = None            # the last auto_exposure() (None: none since exposure_reset)
         self.white = None               # the last auto_white_balance()'s white point (None: none since white_reset)
         self.focus_distance = None      # the last focus_at() that hit a surface (None: depth_of_field takes DOF_DEFAULTS')
+        self.motion_camera = None       # the camera of the last motion_blur() (None: the next one takes its own camera as the previous)
         self._env_sizes = {}            # slot -> (width, height) of what upload_environment / environment_sky put there
 
     # -- construction ---------------------------------------------------------------------------
@@ -733,9 +764,9 @@ class State:
     # -- auto-exposure (include/rsrt.h "auto-exposure") -----------------------------------------------
     def exposure_meter(self, source="mean", sample_total=None, stream=None):
         """rsrt_exposure_meter: builds the luminance histogram of `source` ("mean": the accumulator over sample_total, default
-        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) on the device.  Asynchronous."""
+        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_exposure_meter(self._ctx, IMAGE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
+        self._check(self._L.rsrt_exposure_meter(self._ctx, DISPLAY_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
                     "rsrt_exposure_meter")
 
     def exposure_download(self, **params):
@@ -765,14 +796,14 @@ class State:
 
     def display_exposed_srgb8(self, source="mean", exposure=None, sample_total=None):
         """rsrt_display_exposed_srgb8: `source` through the display pass at `exposure` (None: the remembered one; RsrtError with
-        RSRT_ERR_NOT_READY if there is none): [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens": its source's)."""
+        RSRT_ERR_NOT_READY if there is none): [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens", "motion": their source's)."""
         if exposure is None:
             if self.exposure is None:
                 raise RsrtError("display_exposed_srgb8: no remembered exposure (auto_exposure first)", NOT_READY)
             exposure = self.exposure
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, exposure, _p(out), out.size),
+        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, exposure, _p(out), out.size),
                     "rsrt_display_exposed_srgb8")
         return out
 
@@ -782,12 +813,12 @@ class State:
 
     def bloom(self, source="mean", exposure=None, levels=None, threshold=None, karis=True, sample_total=None, stream=None):
         """rsrt_bloom: builds the bloom image of `source` ("mean": the accumulator over sample_total, default sample_count;
-        "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) at `exposure` (None: the remembered one, else 1) on the device.  levels, threshold:
+        "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) at `exposure` (None: the remembered one, else 1) on the device.  levels, threshold:
         BLOOM_DEFAULTS otherwise; karis: the firefly weighting of the first downsample.  Asynchronous."""
         p = BloomParams(BLOOM_DEFAULTS["levels"] if levels is None else levels, BLOOM_KARIS if karis else 0,
                         BLOOM_DEFAULTS["threshold"] if threshold is None else threshold, 0.0)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_bloom(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_bloom(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                        C.c_void_p(stream) if stream else None), "rsrt_bloom")
 
     def bloom_download(self):
@@ -805,10 +836,10 @@ class State:
     def display_bloomed_srgb8(self, source="mean", exposure=None, intensity=None, sample_total=None):
         """rsrt_display_bloomed_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1 — what
         bloom() took) with `intensity` (BLOOM_DEFAULTS otherwise) times the doubled bloom image added before the tone map:
-        [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens": its source's)."""
+        [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens", "motion": their source's)."""
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                        BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
                     "rsrt_display_bloomed_srgb8")
         return out
@@ -816,10 +847,10 @@ class State:
     # -- local exposure (include/rsrt.h "local exposure") ---------------------------------------------------
     def local_exposure(self, source="mean", cell=None, sample_total=None, stream=None):
         """rsrt_local_exposure: builds the blurred bilateral grid of `source` ("mean": the accumulator over sample_total, default
-        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field()) on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
+        sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
         otherwise).  The grid is of the unexposed image.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_exposure(self._ctx, IMAGE_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
+        self._check(self._L.rsrt_local_exposure(self._ctx, DISPLAY_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
                                                 C.c_void_p(stream) if stream else None), "rsrt_local_exposure")
 
     def local_exposure_download(self):
@@ -842,8 +873,12 @@ class State:
                            q["max_stops"], q.get("flags", 0), 0)
 
     def _source_shape(self, source):
-        """(H, W) of `source`: the guide's for "upsampled", what the library holds for "lens", else the state's own."""
-        source = IMAGE_SOURCES.get(source, source)
+        """(H, W) of `source`: the guide's for "upsampled", what the library holds for "lens" and "motion", else the state's own."""
+        source = DISPLAY_SOURCES.get(source, source)
+        if source == DISPLAY_SOURCES["motion"]:
+            w, h = C.c_uint32(), C.c_uint32()
+            self._check(self._L.rsrt_motion_download(self._ctx, None, 0, C.byref(w), C.byref(h)), "rsrt_motion_download")
+            return (h.value, w.value)
         if source == IMAGE_SOURCES["lens"]:
             w, h = C.c_uint32(), C.c_uint32()
             self._check(self._L.rsrt_dof_download(self._ctx, None, 0, C.byref(w), C.byref(h)), "rsrt_dof_download")
@@ -856,7 +891,7 @@ class State:
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source), np.float32)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_gain_download(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_local_gain_download(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      _p(out), out.size), "rsrt_local_gain_download")
         return out
 
@@ -867,16 +902,16 @@ class State:
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_local_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_display_local_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
         return out
 
     # -- white balance and colour grading (include/rsrt.h "white balance and colour grading") ---------------
     def white_meter(self, source="mean", sample_total=None, stream=None):
         """rsrt_white_meter: builds the chroma histogram of `source` ("mean": the accumulator over sample_total, default sample_count;
-        "denoised", "temporal", "upsampled", "lens") on the device.  Asynchronous."""
+        "denoised", "temporal", "upsampled", "lens", "motion") on the device.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_white_meter(self._ctx, IMAGE_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
+        self._check(self._L.rsrt_white_meter(self._ctx, DISPLAY_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
 
     def white_download(self, **params):
         """rsrt_white_download of the last white_meter(): (histogram, 4097 uint32: 64 x 64 bins, v-major, and the skipped pixels; result
@@ -945,7 +980,7 @@ class State:
         c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, IMAGE_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                       C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), _p(out), out.size),
                     "rsrt_display_colour_srgb8")
         return out
@@ -989,6 +1024,51 @@ class State:
     def dof_reset(self):
         """Drops the lens image (the remembered focus distance stays)."""
         self._check(self._L.rsrt_dof_reset(self._ctx), "rsrt_dof_reset")
+
+    # -- camera motion blur (include/rsrt.h "camera motion blur") -------------------------------------------
+    def motion_blur(self, source="mean", previous=None, shutter=None, max_radius=None, taps=None, sample_total=None, out_ptr=None, stream=None):
+        """rsrt_motion_blur: builds the motion image of `source` ("mean": the accumulator over sample_total, default sample_count;
+        "denoised", "temporal": with the AOV buffer; "upsampled": with the guide; "lens": with the records the lens image was built
+        from) seen through the state's camera after `previous` (an rsrt_camera record: the camera one frame earlier), on the device (in
+        out_ptr when given).  previous None: the camera of this state's last motion_blur(); on the first call, or after
+        motion_reset(), the current camera, and the output is the source.  Every call remembers its camera afterwards.  shutter (the
+        fraction of the frame interval the shutter is open), max_radius (1 .. 16 pixels) and taps (even, 2 .. 32): MOTION_DEFAULTS
+        otherwise.  The later passes take the result as their source "motion".  Asynchronous."""
+        d = MOTION_DEFAULTS
+        p = MotionParams(d["shutter"] if shutter is None else shutter, d["max_radius"] if max_radius is None else max_radius,
+                         d["taps"] if taps is None else taps, 0)
+        if previous is None:
+            previous = self.camera if self.motion_camera is None else self.motion_camera
+        previous = np.ascontiguousarray(previous)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_motion_blur(self._ctx, DISPLAY_SOURCES.get(source, source), n, _p(self.camera), _p(previous), C.byref(p),
+                                             C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None), "rsrt_motion_blur")
+        self.motion_camera = self.camera.copy()
+
+    def motion_download(self):
+        """rsrt_motion_download: the motion image of the last motion_blur(), [H, W, 4] float32 of its source's size, alpha 1."""
+        out = np.empty(self._source_shape("motion") + (4,), np.float32)
+        self._check(self._L.rsrt_motion_download(self._ctx, _p(out), out.size, None, None), "rsrt_motion_download")
+        return out
+
+    def motion_velocity(self):
+        """rsrt_motion_velocity_download: the velocities of the last motion_blur() in pixels, [H, W, 3] float32 (ux, uy, l)."""
+        out = np.empty(self._source_shape("motion") + (3,), np.float32)
+        self._check(self._L.rsrt_motion_velocity_download(self._ctx, _p(out), out.size), "rsrt_motion_velocity_download")
+        return out
+
+    def motion_tiles(self):
+        """rsrt_motion_tiles_download: every 16 x 16 tile's own maximum of the last motion_blur(), [tiles_y, tiles_x, 3] float32."""
+        tx, ty = C.c_uint32(), C.c_uint32()
+        self._check(self._L.rsrt_motion_tiles_download(self._ctx, None, 0, C.byref(tx), C.byref(ty)), "rsrt_motion_tiles_download")
+        out = np.empty((ty.value, tx.value, 3), np.float32)
+        self._check(self._L.rsrt_motion_tiles_download(self._ctx, _p(out), out.size, None, None), "rsrt_motion_tiles_download")
+        return out
+
+    def motion_reset(self):
+        """Drops the motion image and forgets the remembered camera."""
+        self.motion_camera = None
+        self._check(self._L.rsrt_motion_reset(self._ctx), "rsrt_motion_reset")
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):

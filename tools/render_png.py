@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -11,6 +11,10 @@ dof=FOCUS,APERTURE[,RADIUS]: State.depth_of_field of the picture (the AOV pass o
 scene units along the axis (auto: at the depth of the picture's centre, State.focus_at), with APERTURE the blur radius of a point at
 infinity as a fraction of the picture's height and at most RADIUS pixels (default 8); it runs before exposure=, bloom= and local=, which
 then meter, bloom and grade the lens image.
+motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]: State.motion_blur of the picture (the AOV pass over the same samples gives the depths) for a camera
+that one frame earlier was turned back by YAW_DEG degrees about the world's up axis and stood DOLLY scene units back along its forward
+axis, with the shutter open for SHUTTER of the frame interval (default 0.5) and a blur of at most RADIUS pixels each way (default 16);
+it runs after dof= and before exposure=, bloom=, local=, wb= and cdl=, which then take the motion image.
 sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]: environment 0 is the procedural daylight sky (State.environment_sky, 2048 x 1024, built on the
 device: no map is prepared on the host) with the sun at that elevation and azimuth in degrees, instead of the synthetic map; it
 composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it.
@@ -34,12 +38,13 @@ local = next((a[len("local="):] for a in sys.argv[1:] if a.startswith("local="))
 if local is not None:
     local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
 dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
+motion = next((a[len("motion="):].split(",") for a in sys.argv[1:] if a.startswith("motion=")), None)
 sky = next((a[len("sky="):].split(",") for a in sys.argv[1:] if a.startswith("sky=")), None)
 wb = next((a[len("wb="):] for a in sys.argv[1:] if a.startswith("wb=")), None)
 if wb is not None and wb != "auto":
     wb = tuple(float(v) for v in wb.split(","))
 cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "sky=", "wb=", "cdl="))]
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "sky=", "wb=", "cdl="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
@@ -55,10 +60,10 @@ if args[3].startswith("noise="):
     spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024, exposure=exposure,
                                 on_round=lambda r: print("samples %4d -> %4d: max tile error %.4f, mean %.4f, %d tiles above" % r, flush=True))
     print("stopped at", spp, "samples")
-    if denoise or dof:
+    if denoise or dof or motion:
         st.render_aov(0, spp)
 else:
-    st.render_samples(int(args[3]), aov=denoise or bool(dof))
+    st.render_samples(int(args[3]), aov=denoise or bool(dof) or bool(motion))
 if denoise:
     st.denoise(download=False)
 source = "denoised" if denoise else "mean"
@@ -69,6 +74,13 @@ if dof:
     r = abs(st.dof_coc())
     print("blur radius: mean %.3g px, %.1f %% of the pixels above half a pixel" % (r.mean(), 100.0 * (r > 0.5).mean()))
     source = "lens"
+if motion:
+    import math
+    previous = R.state.camera_earlier(st.camera, math.radians(float(motion[0])), float(motion[1]))
+    st.motion_blur(source, previous, float(motion[2]) if len(motion) > 2 else None, int(motion[3]) if len(motion) > 3 else None)
+    l = st.motion_velocity()[..., 2]
+    print("blur half-length: mean %.3g px, largest %.3g px, %.1f %% of the pixels above half a pixel" % (l.mean(), l.max(), 100.0 * (l > 0.5).mean()))
+    source = "motion"
 if exposure == "auto":
     st.exposure_reset()  # meter the picture that is written, whatever render_to_noise metered on the way
     r = st.auto_exposure(source)
@@ -99,7 +111,7 @@ elif bloom is not None:
     host.write_png(out, st.display_bloomed_srgb8(source, exposure, bloom))
 elif exposure is not None:
     host.write_png(out, st.display_exposed_srgb8(source, exposure))
-elif dof:
+elif dof or motion:
     host.write_png(out, st.display_exposed_srgb8(source, 1.0))  # (exposure 1: the bytes of the plain display pass)
 else:
     host.write_png(out, st.denoised_display_srgb8() if denoise else st.display_srgb8())
