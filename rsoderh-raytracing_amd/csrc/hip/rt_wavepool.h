@@ -19,7 +19,10 @@
 // only read / written by the shading stages, are in a global-memory arena (14 dwords per slot for the tree
 // walks; 11 for the flat traversal, whose RNG word, bounce count and hit record ride in hot cells that are
 // idle at the time, + 2 that only a ray cut short by the triangle-loop vote touches; one contiguous column per
-// field and wave, so a stage's accesses coalesce).
+// field and wave, so a stage's accesses coalesce).  The arena does not fit the L2 (5 MB an XCD for the flat kernel), so
+// what is stored to it goes out over the fabric, and the kernel waits for that: stores it does not need are worth more
+// than the instructions around them (profiles/lazy_nee_ab.txt).  The flat kernel therefore stores nothing for a new
+// path but its output slot — throughput 1, radiance 0 and last pdf 1 are known from the bounce count, kFreshInCt below.
 //
 // Stages: GEN    take the next (pixel, sample) of the wave's chunk, build the camera ray — and trace it (its first
 //                round, for the walks) then and there: the lanes are all busy and the rays of a tile coherent
@@ -138,6 +141,11 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
     typedef PoolLayout<POOL, TRAV> L;
     constexpr bool kCoop = TRAV == 6; // the cooperative wide walk (rt_coop.h): TRACE takes every waiting ray of the pool at once, both rays of a vertex in one call
     constexpr bool kBounceInCt = TRAV == 2; // no C_BOUNCE / C_REF column
+    // Flat traversal: a new path's throughput (1), radiance (0) and last pdf (1) are not written to the arena.  The bounce count in
+    // H_CT is 0 exactly until the path's first SHADE has run, so whichever stage picks the path up first (SHADE, or MISS if the camera
+    // ray escapes) takes the constants instead of what it loaded — the slot's previous path's values — and GEN stores one cold word a
+    // path, C_OUT, instead of eight: arena writes are what this kernel waits for (profiles/lazy_nee_ab.txt).
+    constexpr bool kFreshInCt = kBounceInCt;
     // Flat traversal: a ray finishes in one TRACE call — or is cut short by the triangle-loop vote with its best t parked where the
     // result would go — so "best t so far" is INFINITY at every fresh start and the H_T cell is
     // only needed for the RESULT of the extension ray — which fits the shadow direction's first cell, dead by then (the
@@ -334,9 +342,11 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                         SETH(H_EX, slot, ps.d.x); SETH(H_EY, slot, ps.d.y); SETH(H_EZ, slot, ps.d.z);
                         if (kRngHot) SETHU(H_T, slot, ps.rng);
                         else if (!kCoop) SETH(H_T, slot, RT_INFINITY);
-                        SETC(C_TX, slot, 1.0f); SETC(C_TY, slot, 1.0f); SETC(C_TZ, slot, 1.0f);
-                        SETC(C_LX, slot, 0.0f); SETC(C_LY, slot, 0.0f); SETC(C_LZ, slot, 0.0f);
-                        SETC(C_LASTPDF, slot, 1.0f);
+                        if (!kFreshInCt) {
+                            SETC(C_TX, slot, 1.0f); SETC(C_TY, slot, 1.0f); SETC(C_TZ, slot, 1.0f);
+                            SETC(C_LX, slot, 0.0f); SETC(C_LY, slot, 0.0f); SETC(C_LZ, slot, 0.0f);
+                            SETC(C_LASTPDF, slot, 1.0f);
+                        }
                         if (!kRngHot) COLD(C_RNG, slot) = ps.rng;
                         if (!kBounceInCt) COLD(C_BOUNCE, slot) = 0u;
                         COLD(C_OUT, slot) = srel * P.n_slots + chunk_tile_slot0 + p;
@@ -428,9 +438,14 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 const EnvBilinearFetch sky_fetch = kPackedMiss ? sample_env_bilinear_begin_pmf(P.env, env_u, env_v) : sample_env_bilinear_begin(P.env, env_u, env_v);
                 float sky_pmf = 0.0f;
                 if (!kPackedMiss) sky_pmf = environment_direction_pmf(P.env, env_u, env_v);
-                const float last_pdf = COLDF(C_LASTPDF, slot);
-                const V3 T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
+                float last_pdf = COLDF(C_LASTPDF, slot);
+                V3 T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
                 V3 Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
+                if (kFreshInCt && ((ct >> CT_SHIFT) & RT_FLAT_BOUNCE_BITS) == 0u) { // the camera ray: nothing of this path is in the arena yet
+                    last_pdf = 1.0f;
+                    T = v3(1.0f, 1.0f, 1.0f);
+                    Lr = v3(0.0f, 0.0f, 0.0f);
+                }
                 const V3 nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
                 const uint32_t out_slot = COLD(C_OUT, slot);
                 Hit h;
@@ -504,6 +519,10 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                     Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
                     const V3 nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
                     bounce = (kBounceInCt ? (ct >> (CT_SHIFT + RT_FLAT_BOUNCE_SHIFT)) : COLD(C_BOUNCE, slot)) + 1u;
+                    if (kFreshInCt && bounce == 1u) { // the path's first vertex: nothing of this path is in the arena yet
+                        T = v3(1.0f, 1.0f, 1.0f);
+                        Lr = v3(0.0f, 0.0f, 0.0f);
+                    }
                     SHADE_STAMP(10);
                     hit_barycentrics(S, h, o, d); // not carried through the traversal: the same test gives the same bits
                     surf = resolve_hit(S, h, o, d);
