@@ -664,7 +664,8 @@ typedef struct rsrt_dof_params {
     uint32_t max_radius;  /* 1 .. 16 (RSRT_DOF_MAX_RADIUS): the largest blur radius, in pixels */
     uint32_t flags;       /* 0 */
 } rsrt_dof_params;
-/* Builds the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) seen through `camera` (the one the source and its records
+/* Builds the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED, or RSRT_EXPOSURE_FOG, which is blurred with the records of the
+ * image it was built from) seen through `camera` (the one the source and its records
  * were rendered with) into device_out_rgba32f (device memory, W x H x 4 f32, 16-byte aligned, alpha 1) or, when that is NULL, into
  * library-owned memory; 32 bytes of library-owned scratch a pixel either way.  Asynchronous on hip_stream, NULL = the context's
  * stream, ordered after everything enqueued so far.  sample_total is ignored for all sources but RSRT_EXPOSURE_MEAN.
@@ -720,7 +721,8 @@ typedef struct rsrt_motion_params {
     uint32_t taps;       /* even, 2 .. 32: taps along the line */
     uint32_t flags;      /* 0 */
 } rsrt_motion_params;
-/* Builds the motion image of `source` (RSRT_EXPOSURE_MEAN .. _LENS) seen through `camera` (the one the source and its records were
+/* Builds the motion image of `source` (RSRT_EXPOSURE_MEAN .. _LENS, or RSRT_EXPOSURE_FOG, which is blurred with the records of the
+ * image it was built from) seen through `camera` (the one the source and its records were
  * rendered with) after `previous` (the camera one frame earlier) into device_out_rgba32f (device memory, W x H x 4 f32, 16-byte
  * aligned, alpha 1) or, when that is NULL, into library-owned memory; 44 bytes of library-owned scratch a pixel either way.
  * Asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far.  sample_total is ignored for
@@ -746,6 +748,61 @@ rsrt_status rsrt_motion_velocity_download(rsrt_context *ctx, float *host_uvl, si
 rsrt_status rsrt_motion_tiles_download(rsrt_context *ctx, float *host_uvl, size_t n_floats, uint32_t *tiles_x, uint32_t *tiles_y);
 /* Rust: pub fn rsrt_motion_reset(ctx: *mut RsrtContext) -> i32; */
 rsrt_status rsrt_motion_reset(rsrt_context *ctx); /* drops the motion image */
+
+/* -- volumetric fog: a ray-marched sun-shaft pass and a fogged image (no reference counterpart) ----------------------------------
+ * Every pass above rearranges radiance the integrator produced; none puts anything between the camera and the surfaces.
+ * rsrt_fog_render marches a homogeneous participating medium along the camera rays rsrt_render casts: per pixel and sample, `steps`
+ * points between the camera and the first hit (or max_distance), each asked by a shadow query against the scene whether it sees the
+ * one directional light, each adding Henyey-Greenstein single scattering from the light where it does and a constant ambient term
+ * everywhere, attenuated by the medium up to the point.  The pixel's record, 4 f32, gains (inscatter rgb, transmittance of the whole
+ * segment) per sample; split calls give the bits of one call.  rsrt_fog_apply composes one of the four images with the records into
+ * the fog image: colour * mean transmittance + mean inscatter.  It goes BEFORE the lens: rsrt_dof, rsrt_motion_blur, both meters,
+ * bloom, local exposure and every display take the fog image as their source RSRT_EXPOSURE_FOG; for the lens and the shutter it
+ * carries the first-hit records of the image it was built from.  The arithmetic is published in include/rsrt_fog.h (which also says
+ * what the model leaves out: the light's own attenuation, multiple scattering, fog inside the integrator) and is bitwise
+ * reproducible.  With density 0 the fog image is the source's colour bit for bit.
+ *
+ * The fog records have a size of their own, like the guide: library-owned (allocated zeroed on first use or when the given size
+ * changes) or the caller's (rsrt_fog_bind).  rsrt_fog_render needs a scene and no accumulator.  The fog image has the size of the
+ * source it was built from and stays valid until the next rsrt_fog_apply, rsrt_fog_reset, a change of the accumulator's size or
+ * rsrt_context_destroy.  Whole frame only, like the denoiser: with world_size > 1 every call returns RSRT_ERR_INVALID_ARGUMENT.
+ * Nothing here writes the accumulator, the AOV buffer, the guide or any other image of the context.  A refused call launches nothing
+ * and leaves records and image as they were.
+ * rsrt_fog_params (include/rsrt_types.h) defaults: density 0.05, albedo 1, anisotropy 0.6, ambient 0, max_distance 50, steps 16,
+ * flags RSRT_FOG_JITTER (RSRT_FOG_* in include/rsrt_fog.h); the light has no default: rsrt_fog_light_from_sky there gives a sky's sun. */
+enum { RSRT_EXPOSURE_FOG = 6 }; /* the last rsrt_fog_apply output: a source of the lens, the shutter, the meters, bloom, local exposure and the displays */
+/* Adds the fog of samples [sample_begin, sample_begin + sample_count) of a width x height frame seen through `camera` to the fog
+ * records.  Asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far.
+ * RSRT_ERR_NOT_READY without a scene; RSRT_ERR_INVALID_ARGUMENT for NULL camera or params, params rsrt_fog_params_ok refuses, a bad
+ * resolution or sample range as in rsrt_aov_render, bound records of another size.
+ * Rust: pub fn rsrt_fog_render(ctx: *mut RsrtContext, camera: *const RsrtCamera, width: u32, height: u32, sample_begin: u32,
+ *                              sample_count: u32, params: *const RsrtFogParams, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_fog_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t width, uint32_t height, uint32_t sample_begin,
+                            uint32_t sample_count, const rsrt_fog_params *params, void *hip_stream);
+/* The caller's device memory (width x height x 4 f32, 16-byte aligned) as the fog records; NULL: back to the library's.
+ * Rust: pub fn rsrt_fog_bind(ctx: *mut RsrtContext, device_f32x4: *mut c_void, width: u32, height: u32) -> i32; */
+rsrt_status rsrt_fog_bind(rsrt_context *ctx, void *device_f32x4, uint32_t width, uint32_t height);
+/* Rust: pub fn rsrt_fog_clear(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_fog_clear(rsrt_context *ctx); /* zeroes the records; RSRT_ERR_NOT_READY without any */
+/* Waits and copies the records, 4 f32 a pixel (inscatter sum rgb, transmittance sum).  RSRT_ERR_NOT_READY without records;
+ * RSRT_ERR_INVALID_ARGUMENT for another n_floats.
+ * Rust: pub fn rsrt_fog_download(ctx: *mut RsrtContext, host_f32x4: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_fog_download(rsrt_context *ctx, float *host_f32x4, size_t n_floats);
+/* Builds the fog image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) and the records of fog_sample_total samples into
+ * device_out_rgba32f (device memory, W x H x 4 f32, 16-byte aligned, alpha 1) or, when that is NULL, into library-owned memory.
+ * Asynchronous on hip_stream.  sample_total is ignored for all sources but RSRT_EXPOSURE_MEAN.  RSRT_ERR_NOT_READY when the source
+ * image or the records do not exist; RSRT_ERR_INVALID_ARGUMENT for RSRT_EXPOSURE_LENS, _MOTION, _FOG or an unknown source,
+ * fog_sample_total 0, sample_total 0 under RSRT_EXPOSURE_MEAN, records of another size than the source, a misaligned output pointer.
+ * Rust: pub fn rsrt_fog_apply(ctx: *mut RsrtContext, source: u32, sample_total: u32, fog_sample_total: u32,
+ *                             device_out_rgba32f: *mut c_void, hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_fog_apply(rsrt_context *ctx, uint32_t source, uint32_t sample_total, uint32_t fog_sample_total, void *device_out_rgba32f,
+                           void *hip_stream);
+/* Waits and copies the fog image to host_rgba as RGBA32F, alpha 1.  RSRT_ERR_NOT_READY without a fog image since the last reset;
+ * RSRT_ERR_INVALID_ARGUMENT for another n_floats than 4 a pixel.
+ * Rust: pub fn rsrt_fog_image_download(ctx: *mut RsrtContext, host_rgba: *mut f32, n_floats: usize) -> i32; */
+rsrt_status rsrt_fog_image_download(rsrt_context *ctx, float *host_rgba, size_t n_floats);
+/* Rust: pub fn rsrt_fog_reset(ctx: *mut RsrtContext) -> i32; */
+rsrt_status rsrt_fog_reset(rsrt_context *ctx); /* drops the records (a bound buffer is the caller's again) and the fog image */
 
 /* -- white balance and colour grading: a chroma meter, a LUT display (no reference counterpart) ----------------------------------
  * The meter removes the picture's dependence on the environment's scale; nothing so far removes its dependence on the environment's

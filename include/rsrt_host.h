@@ -83,6 +83,11 @@ int rsrt_synth_environment(uint32_t width, uint32_t height, float *rgba_out);
  * non-zero for NULL arguments, a zero size or parameters rsrt_sky_params_ok refuses, and then writes nothing.
  * Rust: pub fn rsrt_sky_fill(width: u32, height: u32, params: *const RsrtSkyParams, rgba_out: *mut f32) -> i32; */
 int rsrt_sky_fill(uint32_t width, uint32_t height, const rsrt_sky_params *params, float *rgba_out);
+/* The sun of that sky on a map of env_height rows as the fog pass's light (rsrt_fog_light_from_sky, include/rsrt_fog.h): dir_out and
+ * irradiance_out receive 3 floats each, rsrt_fog_params' light_dir and light_irradiance.  Returns non-zero for NULL arguments, a zero
+ * height or parameters rsrt_sky_params_ok refuses, and then writes nothing.
+ * Rust: pub fn rsrt_fog_sky_light(env_height: u32, params: *const RsrtSkyParams, dir_out: *mut f32, irradiance_out: *mut f32) -> i32; */
+int rsrt_fog_sky_light(uint32_t env_height, const rsrt_sky_params *params, float *dir_out, float *irradiance_out);
 
 /* Radiance RGBE (.hdr): rgb_out = malloc'ed width*height*3 f32, rows top to bottom; free with rsrt_free.
  * value = mantissa * 2^(e-136), (0,0,0) when e == 0 — the `image` 0.25 hdr decoder's rule. */

@@ -18,6 +18,7 @@
 #include "rsrt_dof.h"
 #include "rsrt_motion.h"
 #include "rsrt_exposure.h"
+#include "rsrt_fog.h"
 #include "rsrt_host.h"
 #include "rsrt_local.h"
 #include "rsrt_sky.h"
@@ -562,6 +563,68 @@ public:
         have_motion_camera_ = false;
         check_ctx(rsrt_motion_reset(context(0)));
     }
+    // -- volumetric fog (rsrt.h "volumetric fog", rsrt_fog.h): one device, like the denoiser -------------------------------------
+    // RSRT_FOG_*; the light has no default: straight up at irradiance 1 here, fog_light_from_sky() gives a sky's sun
+    static rsrt_fog_params fog_defaults()
+    {
+        return rsrt_fog_params{RSRT_FOG_DENSITY, {RSRT_FOG_ALBEDO, RSRT_FOG_ALBEDO, RSRT_FOG_ALBEDO}, RSRT_FOG_ANISOTROPY, {0.0f, 1.0f, 0.0f}, {1.0f, 1.0f, 1.0f},
+                               {RSRT_FOG_AMBIENT, RSRT_FOG_AMBIENT, RSRT_FOG_AMBIENT}, RSRT_FOG_MAX_DISTANCE, RSRT_FOG_STEPS, RSRT_FOG_FLAGS};
+    }
+    // p with the sun of the procedural sky of `sky` on a map of env_height rows as its light (rsrt_fog_light_from_sky)
+    static rsrt_fog_params fog_light_from_sky(rsrt_fog_params p, const rsrt_sky_params &sky, uint32_t env_height = 1024)
+    {
+        if (!rsrt_sky_params_ok(&sky) || env_height == 0) throw Error("fog_light_from_sky: parameters rsrt_sky_params_ok does not accept, or a zero height");
+        rsrt_fog_light_from_sky(&sky, env_height, p.light_dir, p.light_irradiance);
+        return p;
+    }
+    // adds the fog of samples [sample_begin, sample_begin + n) of the state's camera and size to the fog records; raw, like render_aov:
+    // fog_sample_count() grows by n and the state keeps p.  clear_fog() before a new camera or other parameters
+    void render_fog(uint32_t sample_begin, uint32_t n, const rsrt_fog_params &p)
+    {
+        rsrt_camera cam;
+        rsrt_camera_uniform(&camera_, &cam);
+        if (fog_width_ != width_ || fog_height_ != height_) fog_sample_count_ = 0; // records of another size are allocated zeroed
+        check_ctx(rsrt_fog_render(context(0), &cam, width_, height_, sample_begin, n, &p, nullptr));
+        fog_width_ = width_;
+        fog_height_ = height_;
+        fog_params_ = p;
+        fog_sample_count_ += n;
+    }
+    void render_fog(uint32_t n, const rsrt_fog_params &p) { render_fog(fog_sample_count_, n, p); } // progressive: from fog_sample_count()
+    void render_fog(uint32_t n = 1) { render_fog(fog_sample_count_, n, fog_params_); }               // ... with the parameters of the call before
+    void clear_fog()
+    {
+        check_ctx(rsrt_fog_clear(context(0)));
+        fog_sample_count_ = 0;
+    }
+    std::vector<float> download_fog() // the records, W*H*4: inscatter sum rgb, transmittance sum
+    {
+        std::vector<float> out((size_t)fog_width_ * fog_height_ * 4);
+        check_ctx(rsrt_fog_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    uint32_t fog_sample_count() const { return fog_sample_count_; }
+    const rsrt_fog_params &fog_params() const { return fog_params_; } // what the records were rendered with
+    // the fog image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) and the fog records, built on the device.  The later passes —
+    // depth_of_field, motion_blur, the meters, bloom, local exposure, the displays — take it as RSRT_EXPOSURE_FOG.
+    void fog(uint32_t source = RSRT_EXPOSURE_MEAN)
+    {
+        const size_t n = source_pixels(source);
+        check_ctx(rsrt_fog_apply(context(0), source, sample_count_, fog_sample_count_, nullptr, nullptr));
+        fog_pixels_ = n;
+    }
+    std::vector<float> fog_download() // the last fog(): RGBA32F, alpha 1, of its source's size
+    {
+        std::vector<float> out(source_pixels(RSRT_EXPOSURE_FOG) * 4);
+        check_ctx(rsrt_fog_image_download(context(0), out.data(), out.size()));
+        return out;
+    }
+    void fog_reset() // drops the records and the fog image
+    {
+        check_ctx(rsrt_fog_reset(context(0)));
+        fog_sample_count_ = fog_width_ = fog_height_ = 0;
+        fog_pixels_ = 0;
+    }
     // -- the procedural sky (rsrt.h rsrt_environment_sky, rsrt_sky.h) -----------------------------------------------------------
     static rsrt_sky_params sky_defaults()
     {
@@ -708,9 +771,13 @@ private:
     float focus_distance_ = 0.0f; // the last focus_at() that hit a surface (0: none)
     rsrt_camera_desc motion_camera_{}; // the camera of the last motion_blur()
     bool have_motion_camera_ = false;
+    uint32_t fog_sample_count_ = 0, fog_width_ = 0, fog_height_ = 0; // samples in the fog records and their size
+    rsrt_fog_params fog_params_ = fog_defaults();                    // what the last render_fog took
+    size_t fog_pixels_ = 0;                                          // the pixels of the last fog() image (0: none)
     // the pixels of `source`: the guide's for RSRT_EXPOSURE_UPSAMPLED, what the library holds for RSRT_EXPOSURE_LENS and _MOTION, else the state's own
     size_t source_pixels(uint32_t source)
     {
+        if (source == RSRT_EXPOSURE_FOG && fog_pixels_) return fog_pixels_; // (the size of the source the last fog() composed)
         if (source == RSRT_EXPOSURE_MOTION) {
             uint32_t w = 0, h = 0;
             check_ctx(rsrt_motion_download(context(0), nullptr, 0, &w, &h));

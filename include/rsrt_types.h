@@ -117,6 +117,21 @@ typedef struct rsrt_sky_params {
     uint32_t flags;        /* must be 0 */
 } rsrt_sky_params;
 
+/* The participating medium of the fog pass (rsrt_fog_render in rsrt.h; the model is include/rsrt_fog.h): a homogeneous medium lit by
+ * single scattering from one directional light plus a constant isotropic ambient term.  68 bytes.  Defaults: RSRT_FOG_* in
+ * include/rsrt_fog.h. */
+typedef struct rsrt_fog_params {
+    float density;             /* the extinction coefficient sigma_t per scene unit: finite, 0 .. 1e6, and density * max_distance finite */
+    float albedo[3];           /* the single-scattering albedo, each in [0, 1] */
+    float anisotropy;          /* Henyey-Greenstein g, |g| <= 0.95 */
+    float light_dir[3];        /* the direction TOWARDS the light: a unit vector (|len^2 - 1| <= 1e-3), used as given */
+    float light_irradiance[3]; /* radiance times solid angle of the light: finite, >= 0 */
+    float ambient[3];          /* in-scattered radiance from everywhere else: finite, >= 0 */
+    float max_distance;        /* the segment of a camera ray that hits nothing, and the cap of one that does: finite, > 0 */
+    uint32_t steps;            /* march points a camera ray, 1 .. 64 (RSRT_FOG_MAX_STEPS) */
+    uint32_t flags;            /* RSRT_FOG_JITTER or 0 */
+} rsrt_fog_params;
+
 #ifdef __cplusplus
 }
 #endif

@@ -514,7 +514,7 @@ struct ImageView {
     float total = 1.0f;
     size_t pixels() const { return (size_t)w * h; }
 };
-enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3, IMAGE_LENS = 4, IMAGE_MOTION = 5 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
+enum ImageSource : uint32_t { IMAGE_MEAN = 0, IMAGE_DENOISED = 1, IMAGE_TEMPORAL = 2, IMAGE_UPSAMPLED = 3, IMAGE_LENS = 4, IMAGE_MOTION = 5, IMAGE_FOG = 6 }; // (= RSRT_EXPOSURE_*, include/rsrt.h)
 
 struct rsrt_context {
     int device = 0;
@@ -667,6 +667,13 @@ struct rsrt_context {
     // counts; and where the last rsrt_motion_blur wrote (img NULL: no motion image since the last reset).  The library keeps no camera.
     SizedAlloc mt_buf, mt_tiles;
     ImageView mt_last;
+    // volumetric fog (rt_fog.h): the fog records (1 float4 a pixel: inscatter sum rgb, transmittance sum; a size of their own, like the
+    // guide's), the library-owned fog image, which follows the size of the source it was built from, where the last rsrt_fog_apply wrote
+    // (img NULL: no fog image since the last reset) and the first-hit records of that source: rsrt_dof and rsrt_motion_blur of it read them
+    PixelBuffer fog{"fog records", "fog", 1u};
+    SizedAlloc fg_out;
+    ImageView fg_last;
+    const PixelBuffer *fg_rec = nullptr;
     // white balance and colour grading (rt_colour.h): two chroma histograms, kept as the exposure meter keeps its two, and the colour LUT
     // (cl_cap float4 nodes of room; cl_n the LUT's size, 0: none).  Neither follows the accumulator's size: accumulator_size_changed()
     // leaves them.  The library keeps no white point.
@@ -739,7 +746,7 @@ rsrt_status ensure_scratch(rsrt_context *ctx, size_t bytes)
 }
 
 // ------------------------------------------------------------------ image buffers
-// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h, rt_colour.h, rt_motion.h) share on the host: the buffers a
+// What the image-space passes (rt_denoise.h, rt_temporal.h, rt_upsample.h, rt_noise.h, rt_exposure.h, rt_bloom.h, rt_local.h, rt_dof.h, rt_colour.h, rt_motion.h, rt_fog.h) share on the host: the buffers a
 // caller may bind, the library's allocations that follow a size, which image a call means, and the way results reach the host.
 // `what` is the calling entry point's name as its error texts spell it.
 
@@ -869,6 +876,8 @@ void accumulator_size_changed(rsrt_context *ctx)
     release(ctx->mt_buf);
     release(ctx->mt_tiles);
     ctx->mt_last = ImageView{};
+    release(ctx->fg_out);
+    ctx->fg_last = ImageView{};
 }
 rsrt_status ensure_accumulator(rsrt_context *ctx, uint32_t w, uint32_t h)
 {
@@ -923,6 +932,10 @@ rsrt_status resolve_image(rsrt_context *ctx, const char *what, const char *prefi
     case IMAGE_MOTION:
         if (!ctx->mt_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno motion image (rsrt_motion_blur first)", prefix);
         *v = ctx->mt_last;
+        return RSRT_OK;
+    case IMAGE_FOG:
+        if (!ctx->fg_last.img) return fail(ctx, RSRT_ERR_NOT_READY, "%sno fog image (rsrt_fog_apply first)", prefix);
+        *v = ctx->fg_last;
         return RSRT_OK;
     default:
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
@@ -1221,7 +1234,7 @@ void rsrt_context_destroy(rsrt_context *ctx)
     (void)hipFree(ctx->scene_blob);
     for (auto &e : ctx->envs) { (void)hipFree(e.rgba); (void)hipFree(e.alias); }
     accumulator_size_changed(ctx);
-    for (PixelBuffer *b : {&ctx->acc, &ctx->aov, &ctx->guide}) (void)hipFree(b->owned);
+    for (PixelBuffer *b : {&ctx->acc, &ctx->aov, &ctx->guide, &ctx->fog}) (void)hipFree(b->owned);
     release(ctx->up_scratch);
     release(ctx->up_out);
     (void)hipFree(ctx->ns_tiles);
@@ -1951,3 +1964,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_sky.h"
 #include "rt_colour.h"
 #include "rt_motion.h"
+#include "rt_fog.h"

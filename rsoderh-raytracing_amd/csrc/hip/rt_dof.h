@@ -82,10 +82,17 @@ __global__ __launch_bounds__(RT_DOF_BLOCK) void rt_dof_gather_kernel(const float
 
 namespace {
 
-// the first-hit records `source` is blurred by: the AOV buffer (of the accumulator's size) or, for the upsampled image, the guide
+// the first-hit records `source` is blurred by: the AOV buffer (of the accumulator's size), for the upsampled image the guide, and for
+// the fog image the ones of the image it was built from
 rsrt_status dof_records(rsrt_context *ctx, const char *what, uint32_t source, const PixelBuffer **rec)
 {
     if (source == IMAGE_LENS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the lens image is not a source of its own pass", what);
+    if (source == IMAGE_FOG) {
+        if (!ctx->fg_last.img || !ctx->fg_rec) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no fog image (rsrt_fog_apply first)", what);
+        if (!ctx->fg_rec->p) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no %s (the fog image was built from an image of its size)", what, ctx->fg_rec->name);
+        *rec = ctx->fg_rec;
+        return RSRT_OK;
+    }
     if (source > IMAGE_LENS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
     if (source == IMAGE_UPSAMPLED) {
         if (!ctx->guide.p) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no guide buffer (rsrt_guide_render or rsrt_guide_bind first)", what);

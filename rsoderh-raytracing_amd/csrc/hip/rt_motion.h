@@ -132,7 +132,7 @@ namespace {
 rsrt_status motion_records(rsrt_context *ctx, const char *what, uint32_t source, const PixelBuffer **rec)
 {
     if (source == IMAGE_MOTION) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the motion image is not a source of its own pass", what);
-    if (source > IMAGE_MOTION) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
+    if (source > IMAGE_FOG) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: unknown source %u", what, source);
     if (source != IMAGE_LENS) return dof_records(ctx, what, source, rec);
     if (!ctx->df_last.img || !ctx->df_rec) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no lens image (rsrt_dof first)", what);
     if (!ctx->df_rec->p) return fail(ctx, RSRT_ERR_NOT_READY, "%s: no %s any more (the lens image was built from it)", what, ctx->df_rec->name);

@@ -5,6 +5,7 @@
 
 #include "../../../include/rsrt_detmath.h"
 #include "../../../include/rsrt_host.h"
+#include "../../../include/rsrt_fog.h"
 #include "../../../include/rsrt_sky.h"
 #include "host_math.h"
 
@@ -180,5 +181,13 @@ extern "C" int rsrt_sky_fill(uint32_t width, uint32_t height, const rsrt_sky_par
             o[3] = 0.0f;
         }
     }
+    return 0;
+}
+
+// The sun of that sky as the fog pass's light (include/rsrt_fog.h rsrt_fog_light_from_sky)
+extern "C" int rsrt_fog_sky_light(uint32_t env_height, const rsrt_sky_params *params, float *dir_out, float *irradiance_out)
+{
+    if (!dir_out || !irradiance_out || !params || env_height == 0 || !rsrt_sky_params_ok(params)) return 1;
+    rsrt_fog_light_from_sky(params, env_height, dir_out, irradiance_out);
     return 0;
 }

@@ -34,6 +34,8 @@ def lib():
         L.rsrt_synth_environment.restype = C.c_int
         L.rsrt_sky_fill.restype = C.c_int
         L.rsrt_sky_fill.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_fog_sky_light.restype = C.c_int
+        L.rsrt_fog_sky_light.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsrt_load_hdr.restype = C.c_int
         L.rsrt_load_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]
         L.rsrt_free.argtypes = [C.c_void_p]
@@ -181,6 +183,17 @@ def sky_fill(width, height, **params):
     if width <= 0 or height <= 0 or lib().rsrt_sky_fill(width, height, C.byref(p), _p(out)) != 0:
         raise ValueError("rsrt_sky_fill refused: a zero size, or parameters rsrt_sky_params_ok (include/rsrt_sky.h) does not accept")
     return out
+
+
+def fog_light_from_sky(height=1024, **params):
+    """rsrt_fog_light_from_sky (include/rsrt_fog.h): the sun of the procedural sky of `params` on a map of `height` rows as the fog
+    pass's light, {"light_dir": (x, y, z), "light_irradiance": (r, g, b)} — what State.render_fog(**...) takes."""
+    from .state import SkyParams
+    p = SkyParams.of(**params)
+    d, e = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    if height <= 0 or lib().rsrt_fog_sky_light(height, C.byref(p), _p(d), _p(e)) != 0:
+        raise ValueError("rsrt_fog_sky_light refused: a zero height, or parameters rsrt_sky_params_ok (include/rsrt_sky.h) does not accept")
+    return {"light_dir": tuple(float(x) for x in d), "light_irradiance": tuple(float(x) for x in e)}
 
 
 class Environment:

@@ -41,6 +41,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_display_local_srgb8",
             "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset",
             "rsrt_motion_blur", "rsrt_motion_download", "rsrt_motion_velocity_download", "rsrt_motion_tiles_download", "rsrt_motion_reset",
+            "rsrt_fog_render", "rsrt_fog_bind", "rsrt_fog_clear", "rsrt_fog_download", "rsrt_fog_apply", "rsrt_fog_image_download", "rsrt_fog_reset",
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
             "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8"]
@@ -220,6 +221,38 @@ class SkyParams(C.Structure):
                    p["sun_radius"], p["flags"])
 
 
+# volumetric fog (include/rsrt.h "volumetric fog", include/rsrt_fog.h): the sources the passes after it can read — the six images and
+# the fog image rsrt_fog_apply leaves — its defaults (RSRT_FOG_*; the light has none: fog_light_from_sky gives a sky's sun) and its
+# parameters
+ALL_SOURCES = dict(DISPLAY_SOURCES, fog=6)
+FOG_JITTER = 1
+FOG_MAX_STEPS = 64
+FOG_FLOATS = 4  # per pixel: inscatter sum rgb, transmittance sum
+FOG_DEFAULTS = {"density": 0.05, "albedo": (1.0, 1.0, 1.0), "anisotropy": 0.6, "light_dir": (0.0, 1.0, 0.0), "light_irradiance": (1.0, 1.0, 1.0),
+                "ambient": (0.0, 0.0, 0.0), "max_distance": 50.0, "steps": 16, "flags": FOG_JITTER}
+
+
+class FogParams(C.Structure):
+    _fields_ = [("density", C.c_float), ("albedo", C.c_float * 3), ("anisotropy", C.c_float), ("light_dir", C.c_float * 3),
+                ("light_irradiance", C.c_float * 3), ("ambient", C.c_float * 3), ("max_distance", C.c_float), ("steps", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, **params):
+        """FOG_DEFAULTS with `params` over them (albedo, light_irradiance, ambient: one number for all channels or three; jitter=bool sets
+        flags); an unknown name is a TypeError."""
+        if "jitter" in params:
+            params = dict(params)
+            params["flags"] = FOG_JITTER if params.pop("jitter") else 0
+        unknown = set(params) - set(FOG_DEFAULTS)
+        if unknown:
+            raise TypeError("unknown fog parameter(s): " + ", ".join(sorted(unknown)))
+        p = dict(FOG_DEFAULTS, **params)
+        three = lambda k: (C.c_float * 3)(*np.broadcast_to(np.asarray(p[k], np.float32), (3,)))  # noqa: E731
+        return cls(p["density"], three("albedo"), p["anisotropy"], three("light_dir"), three("light_irradiance"), three("ambient"), p["max_distance"],
+                   p["steps"], p["flags"])
+
+
 class TemporalParams(C.Structure):
     _fields_ = [("max_history", C.c_uint32), ("depth_tolerance", C.c_float), ("normal_tolerance", C.c_float)]
 
@@ -374,7 +407,14 @@ def lib():
         L.rsrt_motion_velocity_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_motion_tiles_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.rsrt_motion_reset.argtypes = [C.c_void_p]
-        L.rsrt_environment_sky.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.rsrt_fog_render.argtypes = [C.c_void_p, C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p]
+        L.rsrt_fog_bind.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        L.rsrt_fog_clear.argtypes = [C.c_void_p]
+        L.rsrt_fog_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_fog_apply.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_fog_image_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_fog_reset.argtypes = [C.c_void_p]
+        L.rsrt_environment_sky.argtypes =[C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_environment_download.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
         L.rsrt_white_meter.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_white_download.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
@@ -418,6 +458,11 @@ class State:
         self.focus_distance = None      # the last focus_at() that hit a surface (None: depth_of_field takes DOF_DEFAULTS')
         self.motion_camera = None       # the camera of the last motion_blur() (None: the next one takes its own camera as the previous)
         self._env_sizes = {}            # slot -> (width, height) of what upload_environment / environment_sky put there
+        self.fog_sample_count = 0       # samples in the fog records (render_fog)
+        self.fog_params = None          # the FogParams the records were rendered with (None: none since clear_fog / fog_reset)
+        self.fog_width = self.fog_height = 0  # the records' size
+        self._fog_shape = None          # (H, W) of the last fog() image
+        self._fog_bound = False
 
     # -- construction ---------------------------------------------------------------------------
     @classmethod
@@ -766,7 +811,7 @@ class State:
         """rsrt_exposure_meter: builds the luminance histogram of `source` ("mean": the accumulator over sample_total, default
         sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_exposure_meter(self._ctx, DISPLAY_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
+        self._check(self._L.rsrt_exposure_meter(self._ctx, ALL_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
                     "rsrt_exposure_meter")
 
     def exposure_download(self, **params):
@@ -803,7 +848,7 @@ class State:
             exposure = self.exposure
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, exposure, _p(out), out.size),
+        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, exposure, _p(out), out.size),
                     "rsrt_display_exposed_srgb8")
         return out
 
@@ -818,7 +863,7 @@ class State:
         p = BloomParams(BLOOM_DEFAULTS["levels"] if levels is None else levels, BLOOM_KARIS if karis else 0,
                         BLOOM_DEFAULTS["threshold"] if threshold is None else threshold, 0.0)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_bloom(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_bloom(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                        C.c_void_p(stream) if stream else None), "rsrt_bloom")
 
     def bloom_download(self):
@@ -839,7 +884,7 @@ class State:
         [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens", "motion": their source's)."""
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                        BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
                     "rsrt_display_bloomed_srgb8")
         return out
@@ -850,7 +895,7 @@ class State:
         sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
         otherwise).  The grid is of the unexposed image.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_exposure(self._ctx, DISPLAY_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
+        self._check(self._L.rsrt_local_exposure(self._ctx, ALL_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
                                                 C.c_void_p(stream) if stream else None), "rsrt_local_exposure")
 
     def local_exposure_download(self):
@@ -874,7 +919,9 @@ class State:
 
     def _source_shape(self, source):
         """(H, W) of `source`: the guide's for "upsampled", what the library holds for "lens" and "motion", else the state's own."""
-        source = DISPLAY_SOURCES.get(source, source)
+        source = ALL_SOURCES.get(source, source)
+        if source == ALL_SOURCES["fog"] and self._fog_shape is not None:  # (the size of the source the last fog() composed)
+            return self._fog_shape
         if source == DISPLAY_SOURCES["motion"]:
             w, h = C.c_uint32(), C.c_uint32()
             self._check(self._L.rsrt_motion_download(self._ctx, None, 0, C.byref(w), C.byref(h)), "rsrt_motion_download")
@@ -891,7 +938,7 @@ class State:
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source), np.float32)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_gain_download(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_local_gain_download(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      _p(out), out.size), "rsrt_local_gain_download")
         return out
 
@@ -902,7 +949,7 @@ class State:
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_local_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_display_local_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
                                                      bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
         return out
 
@@ -911,7 +958,7 @@ class State:
         """rsrt_white_meter: builds the chroma histogram of `source` ("mean": the accumulator over sample_total, default sample_count;
         "denoised", "temporal", "upsampled", "lens", "motion") on the device.  Asynchronous."""
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_white_meter(self._ctx, DISPLAY_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
+        self._check(self._L.rsrt_white_meter(self._ctx, ALL_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
 
     def white_download(self, **params):
         """rsrt_white_download of the last white_meter(): (histogram, 4097 uint32: 64 x 64 bins, v-major, and the skipped pixels; result
@@ -980,7 +1027,7 @@ class State:
         c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
         out = np.empty(self._source_shape(source) + (4,), np.uint8)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, DISPLAY_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                       C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), _p(out), out.size),
                     "rsrt_display_colour_srgb8")
         return out
@@ -997,7 +1044,7 @@ class State:
             focus_distance = d["focus_distance"] if self.focus_distance is None else self.focus_distance
         p = DofParams(focus_distance, d["aperture"] if aperture is None else aperture, d["max_radius"] if max_radius is None else max_radius, 0)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_dof(self._ctx, IMAGE_SOURCES.get(source, source), n, _p(self.camera), C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
+        self._check(self._L.rsrt_dof(self._ctx, ALL_SOURCES.get(source, source), n, _p(self.camera), C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
                                      C.c_void_p(stream) if stream else None), "rsrt_dof")
 
     def dof_download(self):
@@ -1016,7 +1063,7 @@ class State:
         """Autofocus (rsrt_dof_depth_at): the depth along the optical axis at pixel (x, y) of `source`'s records, remembered as the focus
         distance of later depth_of_field() calls.  A sky pixel returns inf and leaves the focus as it was."""
         z = C.c_float()
-        self._check(self._L.rsrt_dof_depth_at(self._ctx, IMAGE_SOURCES.get(source, source), _p(self.camera), x, y, C.byref(z)), "rsrt_dof_depth_at")
+        self._check(self._L.rsrt_dof_depth_at(self._ctx, ALL_SOURCES.get(source, source), _p(self.camera), x, y, C.byref(z)), "rsrt_dof_depth_at")
         if np.isfinite(z.value) and z.value > 0:
             self.focus_distance = z.value
         return z.value
@@ -1041,7 +1088,7 @@ class State:
             previous = self.camera if self.motion_camera is None else self.motion_camera
         previous = np.ascontiguousarray(previous)
         n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_motion_blur(self._ctx, DISPLAY_SOURCES.get(source, source), n, _p(self.camera), _p(previous), C.byref(p),
+        self._check(self._L.rsrt_motion_blur(self._ctx, ALL_SOURCES.get(source, source), n, _p(self.camera), _p(previous), C.byref(p),
                                              C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None), "rsrt_motion_blur")
         self.motion_camera = self.camera.copy()
 
@@ -1069,6 +1116,81 @@ class State:
         """Drops the motion image and forgets the remembered camera."""
         self.motion_camera = None
         self._check(self._L.rsrt_motion_reset(self._ctx), "rsrt_motion_reset")
+
+    # -- volumetric fog (include/rsrt.h "volumetric fog") -----------------------------------------------------
+    def render_fog(self, n=None, sample_begin=None, stream=None, size=None, **params):
+        """rsrt_fog_render: adds the fog of n samples (default 1) from sample_begin (default fog_sample_count: progressive, like
+        render_aov) of the state's camera to the fog records, of the state's size or of size = (width, height) — the guide's, for the fog
+        of the upsampled image.  params: rsrt_fog_params fields (density, albedo, anisotropy,
+        light_dir, light_irradiance, ambient, max_distance, steps, flags or jitter=bool), FOG_DEFAULTS otherwise; fog_light_from_sky
+        gives light_dir and light_irradiance of a sky's sun.  With no params at all a later call takes the ones the records were
+        rendered with.  Raw, like render_aov: no hash check; clear_fog() before a new camera or other parameters.  Asynchronous."""
+        p = self.fog_params if (not params and self.fog_params is not None) else FogParams.of(**params)
+        n = 1 if n is None else n
+        w, h = (self.width, self.height) if size is None else size
+        have = self.fog_sample_count if (self.fog_width, self.fog_height) == (w, h) else 0  # (records of another size are allocated zeroed)
+        begin = have if sample_begin is None else sample_begin
+        self._check(self._L.rsrt_fog_render(self._ctx, _p(self.camera), w, h, begin, n, C.byref(p),
+                                            C.c_void_p(stream) if stream else None), "rsrt_fog_render")
+        self.fog_width, self.fog_height = w, h
+        self.fog_params = p
+        self.fog_sample_count = have + n
+
+    def bind_fog(self, device_ptr, width, height):
+        """Use caller-owned device memory (W*H*4 f32) as the fog records (None: back to the library's, which the next render_fog allocates)."""
+        self._check(self._L.rsrt_fog_bind(self._ctx, C.c_void_p(device_ptr) if device_ptr else None, width, height), "rsrt_fog_bind")
+        if device_ptr:
+            self.fog_width, self.fog_height, self._fog_bound = width, height, True
+        elif self._fog_bound:  # (the library gave its own buffer up at the bind)
+            self.fog_width, self.fog_height, self._fog_bound = 0, 0, False
+
+    def clear_fog(self):
+        """rsrt_fog_clear: zeroes the records; the remembered parameters go with them."""
+        self._check(self._L.rsrt_fog_clear(self._ctx), "rsrt_fog_clear")
+        self.fog_sample_count = 0
+        self.fog_params = None
+
+    def download_fog(self):
+        """rsrt_fog_download: the records, [H, W, 4] float32 (inscatter sum rgb, transmittance sum)."""
+        out = np.empty((self.fog_height, self.fog_width, FOG_FLOATS), np.float32)
+        self._check(self._L.rsrt_fog_download(self._ctx, _p(out), out.size), "rsrt_fog_download")
+        return out
+
+    def fog(self, source="mean", out_ptr=None, stream=None, sample_total=None, fog_sample_total=None):
+        """rsrt_fog_apply: builds the fog image of `source` ("mean": the accumulator over sample_total, default sample_count;
+        "denoised", "temporal", "upsampled") and the fog records (of fog_sample_total samples, default fog_sample_count), on the device
+        (in out_ptr when given).  The later passes — depth_of_field, motion_blur, the meters, bloom, local exposure and the displays —
+        take the result as their source "fog".  Asynchronous."""
+        n = self.sample_count if sample_total is None else sample_total
+        nf = self.fog_sample_count if fog_sample_total is None else fog_sample_total
+        src = ALL_SOURCES.get(source, source)
+        self._check(self._L.rsrt_fog_apply(self._ctx, src, n, nf, C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None),
+                    "rsrt_fog_apply")
+        self._fog_shape = self._source_shape(src)
+
+    def fog_download(self):
+        """rsrt_fog_image_download: the fog image of the last fog(), [H, W, 4] float32 of its source's size, alpha 1."""
+        out = np.empty((self._fog_shape or (self.height, self.width)) + (4,), np.float32)
+        self._check(self._L.rsrt_fog_image_download(self._ctx, _p(out), out.size), "rsrt_fog_image_download")
+        return out
+
+    def fog_reset(self):
+        """rsrt_fog_reset: drops the records and the fog image, and forgets the parameters."""
+        self._check(self._L.rsrt_fog_reset(self._ctx), "rsrt_fog_reset")
+        self.fog_sample_count = 0
+        self.fog_params = None
+        self.fog_width = self.fog_height = 0
+        self._fog_bound = False
+        self._fog_shape = None
+
+    def fog_light_from_sky(self, slot=None, height=None, **sky_params):
+        """rsrt_fog_light_from_sky on the host: {"light_dir": (x, y, z), "light_irradiance": (r, g, b)} of the sun of the procedural sky
+        of `sky_params` (SKY_DEFAULTS otherwise) on a map of `height` rows (default: the height environment_sky gave `slot`, else the
+        environment_index's, else 1024) — what render_fog(**...) takes."""
+        from . import host
+        if height is None:
+            height = self._env_sizes.get(self.environment_index if slot is None else slot, (2048, 1024))[1]
+        return host.fog_light_from_sky(height, **sky_params)
 
     # -- temporal pass (include/rsrt.h "temporal pass") ----------------------------------------------
     def render_temporal(self, n=1, max_history=None, depth_tolerance=None, normal_tolerance=None, stream=None, moments=False):

@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -15,6 +15,10 @@ motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]: State.motion_blur of the picture (the A
 that one frame earlier was turned back by YAW_DEG degrees about the world's up axis and stood DOLLY scene units back along its forward
 axis, with the shutter open for SHUTTER of the frame interval (default 0.5) and a blur of at most RADIUS pixels each way (default 16);
 it runs after dof= and before exposure=, bloom=, local=, wb= and cdl=, which then take the motion image.
+fog=DENSITY[,G[,STEPS]]: State.render_fog over the picture's samples — a homogeneous medium of extinction DENSITY per scene unit, Henyey-Greenstein
+anisotropy G (default 0.6), STEPS march points a camera ray (default 16) — and State.fog of the picture; the light is the sun of sky= when
+given (State.fog_light_from_sky), else the synthetic map's sun, from normalize(0.4, 0.6, -0.7) with the irradiance of its lobe, 20 pi (1, 0.95,
+0.85).  It runs after --denoise and before dof=, motion= and the rest, which then take the fog image.
 sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]: environment 0 is the procedural daylight sky (State.environment_sky, 2048 x 1024, built on the
 device: no map is prepared on the host) with the sun at that elevation and azimuth in degrees, instead of the synthetic map; it
 composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it.
@@ -39,19 +43,21 @@ if local is not None:
     local = None if local == "off" else ((None, None) if local == "on" else tuple(float(v) for v in local.split(",")))
 dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
 motion = next((a[len("motion="):].split(",") for a in sys.argv[1:] if a.startswith("motion=")), None)
+fog = next((a[len("fog="):].split(",") for a in sys.argv[1:] if a.startswith("fog=")), None)
 sky = next((a[len("sky="):].split(",") for a in sys.argv[1:] if a.startswith("sky=")), None)
 wb = next((a[len("wb="):] for a in sys.argv[1:] if a.startswith("wb=")), None)
 if wb is not None and wb != "auto":
     wb = tuple(float(v) for v in wb.split(","))
 cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "sky=", "wb=", "cdl="))]
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "sky=", "wb=", "cdl="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
     import math
     st = R.State.new(sc, [], w, h); st.max_bounces = mb
     turbidity = float(sky[2]) if len(sky) > 2 else R.state.SKY_DEFAULTS["turbidity"]
-    st.environment_sky(0, 2048, 1024, sun_elevation=math.radians(float(sky[0])), sun_azimuth=math.radians(float(sky[1])), turbidity=turbidity)
+    sky_params = {"sun_elevation": math.radians(float(sky[0])), "sun_azimuth": math.radians(float(sky[1])), "turbidity": turbidity}
+    st.environment_sky(0, 2048, 1024, **sky_params)
     print("sky: sun at elevation %g degrees, azimuth %g degrees, turbidity %g (2048x1024, built on the device)" % (float(sky[0]), float(sky[1]), turbidity))
 else:
     st = R.State.new(sc, R.Environment.synthetic(2048, 1024), w, h); st.max_bounces = mb
@@ -67,6 +73,19 @@ else:
 if denoise:
     st.denoise(download=False)
 source = "denoised" if denoise else "mean"
+if fog:
+    import math
+    if sky:
+        light = st.fog_light_from_sky(**sky_params)
+    else:  # the synthetic map's sun (rsrt_synth_environment): 5e4 exp(-(1 - cos) / 2e-4) (1, .95, .85) integrates to 5e4 * 2 pi * 2e-4 of each
+        n = math.sqrt(0.4 * 0.4 + 0.6 * 0.6 + 0.7 * 0.7)
+        light = {"light_dir": (0.4 / n, 0.6 / n, -0.7 / n), "light_irradiance": tuple(20.0 * math.pi * c for c in (1.0, 0.95, 0.85))}
+    st.render_fog(st.sample_count, 0, density=float(fog[0]), anisotropy=float(fog[1]) if len(fog) > 1 else R.state.FOG_DEFAULTS["anisotropy"],
+                  steps=int(fog[2]) if len(fog) > 2 else R.state.FOG_DEFAULTS["steps"], **light)
+    st.fog(source)
+    rec = st.download_fog() / st.fog_sample_count
+    print("fog: mean transmittance %.3g, mean inscatter %.3g %.3g %.3g (light from %.3f %.3f %.3f)" % ((rec[..., 3].mean(),) + tuple(rec[..., :3].mean(axis=(0, 1))) + tuple(light["light_dir"])))
+    source = "fog"
 if dof:
     focus = st.focus_at(w // 2, h // 2) if dof[0] == "auto" else float(dof[0])
     print("focus distance %.6g%s" % (focus, " (the centre is sky: the default focus)" if focus == float("inf") else ""))
@@ -111,7 +130,7 @@ elif bloom is not None:
     host.write_png(out, st.display_bloomed_srgb8(source, exposure, bloom))
 elif exposure is not None:
     host.write_png(out, st.display_exposed_srgb8(source, exposure))
-elif dof or motion:
+elif dof or motion or fog:
     host.write_png(out, st.display_exposed_srgb8(source, 1.0))  # (exposure 1: the bytes of the plain display pass)
 else:
     host.write_png(out, st.denoised_display_srgb8() if denoise else st.display_srgb8())
