@@ -797,6 +797,23 @@ rsrt_status rsrt_fog_download(rsrt_context *ctx, float *host_f32x4, size_t n_flo
  *                             device_out_rgba32f: *mut c_void, hip_stream: *mut c_void) -> i32; */
 rsrt_status rsrt_fog_apply(rsrt_context *ctx, uint32_t source, uint32_t sample_total, uint32_t fog_sample_total, void *device_out_rgba32f,
                            void *hip_stream);
+/* rsrt_fog_apply for fog records SMALLER than the source (marched at half size, say: rsrt_fog_render with a width and height of its
+ * own): the fog image of the source's size W x H is rebuilt from the w x h records (w <= W, h <= H) and the source's first-hit
+ * records — the guide for RSRT_EXPOSURE_UPSAMPLED, the AOV buffer otherwise — of record_sample_total samples.  The inscatter is
+ * divided by 1 - transmittance per low pixel, upsampled with a tent over 3 x 3 low pixels and multiplied by 1 - tau, where tau is the
+ * output pixel's own transmittance, computed from its first-hit record and `params` (those the records were rendered with; density and
+ * max_distance are read); out = colour * tau + inscatter.  The arithmetic is published in include/rsrt_fog_upsample.h and is bitwise
+ * reproducible; with density 0 the fog image is the source's colour bit for bit.  Equal sizes are allowed and give the 3 x 3 tent, not
+ * rsrt_fog_apply's result.  It leaves the fog image and its first-hit records exactly as rsrt_fog_apply does, so every later pass takes
+ * the result as RSRT_EXPOSURE_FOG.  It refuses what rsrt_fog_apply refuses, records of another size excepted, and with
+ * RSRT_ERR_INVALID_ARGUMENT NULL params, params rsrt_fog_params_ok refuses, record_sample_total 0, fog records wider or taller than the
+ * source and first-hit records of another size than the source; RSRT_ERR_NOT_READY without first-hit records.  A refused call launches
+ * nothing and leaves records and image as they were.
+ * Rust: pub fn rsrt_fog_apply_upsampled(ctx: *mut RsrtContext, source: u32, sample_total: u32, fog_sample_total: u32,
+ *                                       record_sample_total: u32, params: *const RsrtFogParams, device_out_rgba32f: *mut c_void,
+ *                                       hip_stream: *mut c_void) -> i32; */
+rsrt_status rsrt_fog_apply_upsampled(rsrt_context *ctx, uint32_t source, uint32_t sample_total, uint32_t fog_sample_total,
+                                     uint32_t record_sample_total, const rsrt_fog_params *params, void *device_out_rgba32f, void *hip_stream);
 /* Waits and copies the fog image to host_rgba as RGBA32F, alpha 1.  RSRT_ERR_NOT_READY without a fog image since the last reset;
  * RSRT_ERR_INVALID_ARGUMENT for another n_floats than 4 a pixel.
  * Rust: pub fn rsrt_fog_image_download(ctx: *mut RsrtContext, host_rgba: *mut f32, n_floats: usize) -> i32; */

@@ -579,14 +579,16 @@ public:
     }
     // adds the fog of samples [sample_begin, sample_begin + n) of the state's camera and size to the fog records; raw, like render_aov:
     // fog_sample_count() grows by n and the state keeps p.  clear_fog() before a new camera or other parameters
-    void render_fog(uint32_t sample_begin, uint32_t n, const rsrt_fog_params &p)
+    void render_fog(uint32_t sample_begin, uint32_t n, const rsrt_fog_params &p) { render_fog(sample_begin, n, p, width_, height_); }
+    // ... to records of a size of their own: the guide's for the fog of the upsampled image, or half the source's for fog(source, true)
+    void render_fog(uint32_t sample_begin, uint32_t n, const rsrt_fog_params &p, uint32_t width, uint32_t height)
     {
         rsrt_camera cam;
         rsrt_camera_uniform(&camera_, &cam);
-        if (fog_width_ != width_ || fog_height_ != height_) fog_sample_count_ = 0; // records of another size are allocated zeroed
-        check_ctx(rsrt_fog_render(context(0), &cam, width_, height_, sample_begin, n, &p, nullptr));
-        fog_width_ = width_;
-        fog_height_ = height_;
+        if (fog_width_ != width || fog_height_ != height) fog_sample_count_ = 0; // records of another size are allocated zeroed
+        check_ctx(rsrt_fog_render(context(0), &cam, width, height, sample_begin, n, &p, nullptr));
+        fog_width_ = width;
+        fog_height_ = height;
         fog_params_ = p;
         fog_sample_count_ += n;
     }
@@ -607,10 +609,16 @@ public:
     const rsrt_fog_params &fog_params() const { return fog_params_; } // what the records were rendered with
     // the fog image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) and the fog records, built on the device.  The later passes —
     // depth_of_field, motion_blur, the meters, bloom, local exposure, the displays — take it as RSRT_EXPOSURE_FOG.
-    void fog(uint32_t source = RSRT_EXPOSURE_MEAN)
+    // upsample: the records are smaller than the source (rsrt_fog_apply_upsampled); the fog image is rebuilt from them, the source's
+    // first-hit records (the guide for RSRT_EXPOSURE_UPSAMPLED, the AOV buffer otherwise) and fog_params().
+    void fog(uint32_t source = RSRT_EXPOSURE_MEAN, bool upsample = false)
     {
         const size_t n = source_pixels(source);
-        check_ctx(rsrt_fog_apply(context(0), source, sample_count_, fog_sample_count_, nullptr, nullptr));
+        if (upsample)
+            check_ctx(rsrt_fog_apply_upsampled(context(0), source, sample_count_, fog_sample_count_,
+                                               source == RSRT_EXPOSURE_UPSAMPLED ? guide_sample_count_ : aov_sample_count_, &fog_params_, nullptr, nullptr));
+        else
+            check_ctx(rsrt_fog_apply(context(0), source, sample_count_, fog_sample_count_, nullptr, nullptr));
         fog_pixels_ = n;
     }
     std::vector<float> fog_download() // the last fog(): RGBA32F, alpha 1, of its source's size

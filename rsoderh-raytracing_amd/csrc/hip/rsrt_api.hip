@@ -669,9 +669,10 @@ struct rsrt_context {
     ImageView mt_last;
     // volumetric fog (rt_fog.h): the fog records (1 float4 a pixel: inscatter sum rgb, transmittance sum; a size of their own, like the
     // guide's), the library-owned fog image, which follows the size of the source it was built from, where the last rsrt_fog_apply wrote
-    // (img NULL: no fog image since the last reset) and the first-hit records of that source: rsrt_dof and rsrt_motion_blur of it read them
+    // (img NULL: no fog image since the last reset) and the first-hit records of that source: rsrt_dof and rsrt_motion_blur of it read them;
+    // the rebuild's scratch (rsrt_fog_apply_upsampled: a float4 a LOW pixel, follows the records' size)
     PixelBuffer fog{"fog records", "fog", 1u};
-    SizedAlloc fg_out;
+    SizedAlloc fg_out, fg_src;
     ImageView fg_last;
     const PixelBuffer *fg_rec = nullptr;
     // white balance and colour grading (rt_colour.h): two chroma histograms, kept as the exposure meter keeps its two, and the colour LUT
@@ -1237,6 +1238,7 @@ void rsrt_context_destroy(rsrt_context *ctx)
     for (PixelBuffer *b : {&ctx->acc, &ctx->aov, &ctx->guide, &ctx->fog}) (void)hipFree(b->owned);
     release(ctx->up_scratch);
     release(ctx->up_out);
+    release(ctx->fg_src);
     (void)hipFree(ctx->ns_tiles);
     (void)hipFree(ctx->ex_hist);
     (void)hipFree(ctx->wb_hist);

@@ -8,7 +8,13 @@
 //                         not" as the full walk does because the walk never prunes.  Every lane of a wave runs sample_count x steps
 //                         trips; the walks inside differ in length.  16 B read and written a pixel.  No scratch memory.
 //  rt_fog_compose_kernel  one thread a pixel: out = colour * mean transmittance + mean inscatter.  32 B read, 16 B written a pixel.
+//  rt_fog_source_kernel   the rebuild's pass over the LOW records (arithmetic in include/rsrt_fog_upsample.h): one thread a
+//                         low pixel, record -> mean inscatter / (1 - mean transmittance).  16 B read and written a low pixel.
+//  rt_fog_rebuild_kernel  one thread an output pixel: 16 B of source and 32 B of first-hit record read, nine source terms of the low frame
+//                         (plain global loads; neighbouring lanes share them, about 4 B a pixel of new traffic at half size), the
+//                         pixel's own transmittance from its first hit, 16 B written.
 #include "../../../include/rsrt_fog.h"
+#include "../../../include/rsrt_fog_upsample.h"
 
 // does the ray (o, d) hit anything the tree holds: rsrt_cast_rays mode 1's did_hit (cast_ray_bvh alone, no fallback)
 template <class View>
@@ -70,6 +76,52 @@ __global__ __launch_bounds__(256) void rt_fog_compose_kernel(const float4 *img, 
     float o[3];
     rsrt_fog_compose(c, r, n, o);
     out[i] = make_float4(o[0], o[1], o[2], 1.0f);
+}
+
+// rec: the low fog records, of n samples; src: their demodulated form
+__global__ __launch_bounds__(256) void rt_fog_source_kernel(const float4 *rec, float n, size_t count, float4 *src)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const float4 q = rec[i];
+    const float r[4] = {q.x, q.y, q.z, q.w};
+    float s[3];
+    rsrt_fogup_source(r, n, s);
+    src[i] = make_float4(s[0], s[1], s[2], 0.0f);
+}
+
+// img: sums of `total` samples, W x H; g: the first-hit records of the same size, of g_total samples; src: rt_fog_source_kernel's, w x h
+__global__ __launch_bounds__(256) void rt_fog_rebuild_kernel(const float4 *img, float total, const float4 *g, float g_total, const float4 *src, uint32_t w,
+                                                             uint32_t h, uint32_t W, uint32_t H, rsrt_fog_constants K, float4 *out)
+{
+    const size_t P = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (P >= (size_t)W * H) return;
+    const uint32_t X = (uint32_t)(P % W), Y = (uint32_t)(P / W);
+    const float u = rsrt_up_coord(X, w, W), v = rsrt_up_coord(Y, h, H);
+    const int xn = rsrt_up_nearest(u), yn = rsrt_up_nearest(v);
+    float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int dy = -1; dy <= 1; dy++) {
+        const int qy = yn + dy;
+        if (qy < 0 || qy >= (int)h) continue;
+        const float hy = rsrt_up_tent(qy, v);
+        const float4 *row = src + (size_t)qy * w;
+#pragma unroll
+        for (int dx = -1; dx <= 1; dx++) {
+            const int qx = xn + dx;
+            if (qx < 0 || qx >= (int)w) continue;
+            const float hx = rsrt_up_tent(qx, u);
+            const float4 c = row[qx];
+            const float sq[3] = {c.x, c.y, c.z};
+            rsrt_fogup_tap(hx * hy, sq, acc);
+        }
+    }
+    float a[8], o[3];
+    dn_aov(g, P, a);
+    const float4 s = img[P];
+    const float colour[3] = {s.x / total, s.y / total, s.z / total};
+    rsrt_fogup_finish(colour, acc, rsrt_fogup_tau(&K, a, g_total), o);
+    out[P] = make_float4(o[0], o[1], o[2], 1.0f);
 }
 
 namespace {
@@ -184,6 +236,55 @@ rsrt_status rsrt_fog_apply(rsrt_context *ctx, uint32_t source, uint32_t sample_t
     return end_work(ctx, stream);
 }
 
+rsrt_status rsrt_fog_apply_upsampled(rsrt_context *ctx, uint32_t source, uint32_t sample_total, uint32_t fog_sample_total,
+                                     uint32_t record_sample_total, const rsrt_fog_params *params, void *device_out_rgba32f, void *hip_stream)
+{
+    if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
+    DeviceGuard g(ctx->device);
+    rsrt_status st = whole_frame(ctx, "fog_apply_upsampled");
+    if (st) return st;
+    if (source == IMAGE_FOG) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: the fog image is not a source of its own pass");
+    if (source == IMAGE_LENS || source == IMAGE_MOTION) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: the fog goes before the lens and the shutter (source %u)", source);
+    if (source > IMAGE_FOG) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: unknown source %u", source);
+    if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: params is NULL");
+    if (!rsrt_fog_params_ok(params)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: params are not ones rsrt_fog_render accepts");
+    if (fog_sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: fog_sample_total must be > 0");
+    if (record_sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: record_sample_total must be > 0");
+    if (source == IMAGE_MEAN && sample_total == 0) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: sample_total must be > 0");
+    if ((uintptr_t)device_out_rgba32f % 16) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: output pointer must be 16-byte aligned");
+    if (!ctx->fog.p) return fail(ctx, RSRT_ERR_NOT_READY, "fog_apply_upsampled: no fog records (rsrt_fog_render or rsrt_fog_bind first)");
+    ImageView v;
+    if ((st = resolve_image(ctx, "fog_apply_upsampled", "fog_apply_upsampled: ", source, sample_total, false, &v))) return st;
+    // the first-hit records of the source's size: the guide for the upsampled image, the AOV buffer otherwise
+    const PixelBuffer *const rec = source == IMAGE_UPSAMPLED ? &ctx->guide : &ctx->aov;
+    if (!rec->p) return fail(ctx, RSRT_ERR_NOT_READY, "fog_apply_upsampled: no %s", rec->name);
+    if (rec->w != v.w || rec->h != v.h)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: %s is %ux%u, the source %ux%u", rec->name, rec->w, rec->h, v.w, v.h);
+    if (ctx->fog.w > v.w || ctx->fog.h > v.h)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "fog_apply_upsampled: %s is %ux%u, larger than the source %ux%u", ctx->fog.name, ctx->fog.w, ctx->fog.h, v.w, v.h);
+    const hipStream_t stream = stream_of(ctx, hip_stream);
+    if ((st = ensure_sized(ctx, ctx->fg_src, ctx->fog.w, ctx->fog.h, sizeof(float4)))) return st;
+    if (!device_out_rgba32f) {
+        if (!ctx->fg_out.is(v.w, v.h) && ctx->fg_last.img == ctx->fg_out.p) ctx->fg_last = ImageView{}; // (the allocation that held the fog image goes)
+        if ((st = ensure_sized(ctx, ctx->fg_out, v.w, v.h, sizeof(float4)))) return st;
+    }
+    if ((st = begin_work(ctx, stream))) return st;
+    ctx->fg_last = ImageView{}; // (a failed launch leaves no fog image)
+    rsrt_fog_constants K;
+    memset(&K, 0, sizeof K);
+    rsrt_fog_prepare(params, &K);
+    const size_t n = v.pixels(), low = ctx->fog.pixels();
+    float4 *const src = static_cast<float4 *>(ctx->fg_src.p);
+    float4 *const out = device_out_rgba32f ? static_cast<float4 *>(device_out_rgba32f) : static_cast<float4 *>(ctx->fg_out.p);
+    rt_fog_source_kernel<<<dim3((unsigned)((low + 255) / 256)), dim3(256), 0, stream>>>(ctx->fog.p, (float)fog_sample_total, low, src);
+    rt_fog_rebuild_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream>>>(v.img, v.total, rec->p, (float)record_sample_total, src, ctx->fog.w, ctx->fog.h,
+                                                                                     v.w, v.h, K, out);
+    HIP_TRY(ctx, hipGetLastError());
+    ctx->fg_last = ImageView{out, v.w, v.h, 1.0f};
+    ctx->fg_rec = rec;
+    return end_work(ctx, stream);
+}
+
 rsrt_status rsrt_fog_image_download(rsrt_context *ctx, float *host_rgba, size_t n_floats)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
@@ -200,6 +301,7 @@ rsrt_status rsrt_fog_reset(rsrt_context *ctx)
     { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
     ctx->fg_last = ImageView{};
     release(ctx->fg_out);
+    release(ctx->fg_src);
     ctx->fog.p = nullptr; // a bound buffer is the caller's again; the library's own goes
     (void)hipFree(ctx->fog.owned);
     ctx->fog.owned = nullptr;

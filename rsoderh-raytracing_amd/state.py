@@ -42,6 +42,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_dof", "rsrt_dof_download", "rsrt_dof_coc_download", "rsrt_dof_depth_at", "rsrt_dof_reset",
             "rsrt_motion_blur", "rsrt_motion_download", "rsrt_motion_velocity_download", "rsrt_motion_tiles_download", "rsrt_motion_reset",
             "rsrt_fog_render", "rsrt_fog_bind", "rsrt_fog_clear", "rsrt_fog_download", "rsrt_fog_apply", "rsrt_fog_image_download", "rsrt_fog_reset",
+            "rsrt_fog_apply_upsampled",
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
             "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8"]
@@ -412,6 +413,7 @@ def lib():
         L.rsrt_fog_clear.argtypes = [C.c_void_p]
         L.rsrt_fog_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_fog_apply.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.rsrt_fog_apply_upsampled.argtypes = [C.c_void_p] + [C.c_uint32] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rsrt_fog_image_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_fog_reset.argtypes = [C.c_void_p]
         L.rsrt_environment_sky.argtypes =[C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
@@ -1156,16 +1158,27 @@ class State:
         self._check(self._L.rsrt_fog_download(self._ctx, _p(out), out.size), "rsrt_fog_download")
         return out
 
-    def fog(self, source="mean", out_ptr=None, stream=None, sample_total=None, fog_sample_total=None):
+    def fog(self, source="mean", out_ptr=None, stream=None, sample_total=None, fog_sample_total=None, upsample=False, record_sample_total=None):
         """rsrt_fog_apply: builds the fog image of `source` ("mean": the accumulator over sample_total, default sample_count;
         "denoised", "temporal", "upsampled") and the fog records (of fog_sample_total samples, default fog_sample_count), on the device
         (in out_ptr when given).  The later passes — depth_of_field, motion_blur, the meters, bloom, local exposure and the displays —
-        take the result as their source "fog".  Asynchronous."""
+        take the result as their source "fog".  Asynchronous.
+        upsample=True: rsrt_fog_apply_upsampled — the records are smaller than the source (render_fog(size=...), half the size say) and
+        the fog image is rebuilt from them and the source's first-hit records (the guide for "upsampled", the AOV buffer otherwise; of
+        record_sample_total samples, default guide_sample_count / aov_sample_count) with the remembered fog_params."""
         n = self.sample_count if sample_total is None else sample_total
         nf = self.fog_sample_count if fog_sample_total is None else fog_sample_total
         src = ALL_SOURCES.get(source, source)
-        self._check(self._L.rsrt_fog_apply(self._ctx, src, n, nf, C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None),
-                    "rsrt_fog_apply")
+        out, on = C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None
+        if upsample:
+            if self.fog_params is None:
+                raise RsrtError("fog(upsample=True): no fog parameters remembered (render_fog first)")
+            nr = record_sample_total
+            if nr is None:
+                nr = self.guide_sample_count if src == ALL_SOURCES["upsampled"] else self.aov_sample_count
+            self._check(self._L.rsrt_fog_apply_upsampled(self._ctx, src, n, nf, nr, C.byref(self.fog_params), out, on), "rsrt_fog_apply_upsampled")
+        else:
+            self._check(self._L.rsrt_fog_apply(self._ctx, src, n, nf, out, on), "rsrt_fog_apply")
         self._fog_shape = self._source_shape(src)
 
     def fog_download(self):

@@ -2,8 +2,10 @@
 --reps): rsrt_fog_render of one sample at 8, 16 and 32 steps (jitter on, the light the synthetic map's sun), rsrt_fog_apply of the mean
 and, for scale, in the same run, rsrt_aov_render of one sample — the same per-lane walk on the coherent camera rays.  The rates are
 w h steps shadow queries (and w h camera rays for the AOV pass) over the median time.  No time is fixed in advance; `notes` says whether
-the march's shadow-ray rate reaches the AOV pass's own rays per second.  Prints one JSON line and writes it to
-profiles/fog_house_1080p.json (--out).
+the march's shadow-ray rate reaches the AOV pass's own rays per second.  Beside them, in the same run, fog at half size (DESIGN.md
+§23): rsrt_fog_render at ceil(w / 2) x ceil(h / 2) at the same step counts and rsrt_fog_apply_upsampled of the mean at the full size,
+with what they take of the full-size march and of rsrt_fog_apply.  Prints one JSON line and writes it to
+profiles/fog_upsample_house_1080p.json (--out; profiles/fog_house_1080p.json holds the run before the half-size rows existed).
 """
 import argparse
 import ctypes as C
@@ -27,7 +29,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--steps", default="8,16,32")
     ap.add_argument("--density", type=float, default=0.15)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fog_house_1080p.json"))
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fog_upsample_house_1080p.json"))
     a = ap.parse_args()
     import rsoderh_raytracing_amd as R
     scene = R.Scene.load_toml(os.path.join(ROOT, "tests", "golden", "assets", "scenes", a.scene + ".toml"))
@@ -76,7 +78,24 @@ def main():
     out["fog_apply"] = timed(lambda: st.fog("mean", stream=sp))
     out["fog_apply"]["unique_bytes"] = n * 48  # the sum and the record read, the image written: a float4 each
     out["fog_apply"]["gb_per_s"] = n * 48 / (out["fog_apply"]["ms_median"] * 1e-3) / 1e9
-    rates = [v["shadow_rays_per_s"] for k, v in out.items() if k.startswith("fog_render_")]
+    # fog at half size: the march over a quarter of the rays, and the rebuild at the full size in the place of rsrt_fog_apply
+    hw, hh = (a.width + 1) // 2, (a.height + 1) // 2
+    out["half_size"] = [hw, hh]
+    for steps in [int(v) for v in a.steps.split(",")]:
+        k = "fog_render_half_%d_steps" % steps
+        out[k] = timed(lambda: st.render_fog(1, 0, stream=sp, size=(hw, hh), density=a.density, steps=steps, **light))
+        out[k]["shadow_rays_per_s"] = hw * hh * steps / (out[k]["ms_median"] * 1e-3)
+        out[k]["of_full_size"] = out[k]["ms_median"] / out["fog_render_%d_steps" % steps]["ms_median"]
+    out["fog_apply_upsampled"] = timed(lambda: st.fog("mean", stream=sp, upsample=True))
+    # the sum, the first-hit record and the image as before, the low records read and their source terms written and read
+    out["fog_apply_upsampled"]["unique_bytes"] = n * 64 + hw * hh * 48
+    out["fog_apply_upsampled"]["gb_per_s"] = out["fog_apply_upsampled"]["unique_bytes"] / (out["fog_apply_upsampled"]["ms_median"] * 1e-3) / 1e9
+    out["fog_apply_upsampled"]["of_fog_apply"] = out["fog_apply_upsampled"]["ms_median"] / out["fog_apply"]["ms_median"]
+    for steps in [int(v) for v in a.steps.split(",")]:
+        full = out["fog_render_%d_steps" % steps]["ms_median"] + out["fog_apply"]["ms_median"]
+        half = out["fog_render_half_%d_steps" % steps]["ms_median"] + out["fog_apply_upsampled"]["ms_median"]
+        out["fog_render_half_%d_steps" % steps]["march_and_compose_gain"] = full / half
+    rates = [v["shadow_rays_per_s"] for k, v in out.items() if k.startswith("fog_render_") and "half" not in k]
     out["notes"] = {"march_reaches_the_aov_ray_rate": bool(min(rates) >= out["aov_render"]["rays_per_s"]),
                     "march_over_aov_ray_rate": [r / out["aov_render"]["rays_per_s"] for r in rates]}
     st.close()

@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [foghalf=on] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -19,6 +19,8 @@ fog=DENSITY[,G[,STEPS]]: State.render_fog over the picture's samples — a homog
 anisotropy G (default 0.6), STEPS march points a camera ray (default 16) — and State.fog of the picture; the light is the sun of sky= when
 given (State.fog_light_from_sky), else the synthetic map's sun, from normalize(0.4, 0.6, -0.7) with the irradiance of its lobe, 20 pi (1, 0.95,
 0.85).  It runs after --denoise and before dof=, motion= and the rest, which then take the fog image.
+foghalf=on (with fog=): the march runs at ceil(W / 2) x ceil(H / 2) and the fog image is rebuilt at full size from those records and the
+picture's first-hit records (State.fog(upsample=True)); the AOV pass runs over the picture's samples for it.
 sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]: environment 0 is the procedural daylight sky (State.environment_sky, 2048 x 1024, built on the
 device: no map is prepared on the host) with the sun at that elevation and azimuth in degrees, instead of the synthetic map; it
 composes with everything above.  The sky's default scale leaves daylight far above a display's range: use exposure=auto with it.
@@ -44,12 +46,13 @@ if local is not None:
 dof = next((a[len("dof="):].split(",") for a in sys.argv[1:] if a.startswith("dof=")), None)
 motion = next((a[len("motion="):].split(",") for a in sys.argv[1:] if a.startswith("motion=")), None)
 fog = next((a[len("fog="):].split(",") for a in sys.argv[1:] if a.startswith("fog=")), None)
+foghalf = bool(fog) and "foghalf=on" in sys.argv[1:]
 sky = next((a[len("sky="):].split(",") for a in sys.argv[1:] if a.startswith("sky=")), None)
 wb = next((a[len("wb="):] for a in sys.argv[1:] if a.startswith("wb=")), None)
 if wb is not None and wb != "auto":
     wb = tuple(float(v) for v in wb.split(","))
 cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "sky=", "wb=", "cdl="))]
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "foghalf=", "sky=", "wb=", "cdl="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
@@ -66,10 +69,10 @@ if args[3].startswith("noise="):
     spp, _ = st.render_to_noise(float(target[0]), max_samples=int(target[1]) if len(target) > 1 else 1024, exposure=exposure,
                                 on_round=lambda r: print("samples %4d -> %4d: max tile error %.4f, mean %.4f, %d tiles above" % r, flush=True))
     print("stopped at", spp, "samples")
-    if denoise or dof or motion:
+    if denoise or dof or motion or foghalf:
         st.render_aov(0, spp)
 else:
-    st.render_samples(int(args[3]), aov=denoise or bool(dof) or bool(motion))
+    st.render_samples(int(args[3]), aov=denoise or bool(dof) or bool(motion) or foghalf)
 if denoise:
     st.denoise(download=False)
 source = "denoised" if denoise else "mean"
@@ -81,8 +84,8 @@ if fog:
         n = math.sqrt(0.4 * 0.4 + 0.6 * 0.6 + 0.7 * 0.7)
         light = {"light_dir": (0.4 / n, 0.6 / n, -0.7 / n), "light_irradiance": tuple(20.0 * math.pi * c for c in (1.0, 0.95, 0.85))}
     st.render_fog(st.sample_count, 0, density=float(fog[0]), anisotropy=float(fog[1]) if len(fog) > 1 else R.state.FOG_DEFAULTS["anisotropy"],
-                  steps=int(fog[2]) if len(fog) > 2 else R.state.FOG_DEFAULTS["steps"], **light)
-    st.fog(source)
+                  steps=int(fog[2]) if len(fog) > 2 else R.state.FOG_DEFAULTS["steps"], size=((w + 1) // 2, (h + 1) // 2) if foghalf else None, **light)
+    st.fog(source, upsample=foghalf)
     rec = st.download_fog() / st.fog_sample_count
     print("fog: mean transmittance %.3g, mean inscatter %.3g %.3g %.3g (light from %.3f %.3f %.3f)" % ((rec[..., 3].mean(),) + tuple(rec[..., :3].mean(axis=(0, 1))) + tuple(light["light_dir"])))
     source = "fog"
