@@ -916,6 +916,37 @@ rsrt_status rsrt_colour_lut_reset(rsrt_context *ctx); /* drops the LUT */
 rsrt_status rsrt_display_colour_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
                                       float bloom_intensity, const rsrt_colour_params *colour, uint8_t *host_rgba8, size_t n_bytes);
 
+/* -- finished display: sharpening, film grain and dither after the tone map (no reference counterpart) ---------------------------
+ * Every pass so far works on linear radiance BEFORE the tone map; behind it stood one hard quantiser.  rsrt_display_finished_srgb8 is
+ * rsrt_display_colour_srgb8 with three display-referred steps between the LUT and the byte, all in the square-root domain the LUT
+ * uses: a contrast-adaptive sharpener over a pixel's cross (FSR 1's RCAS, optionally with its noise limiter), monochrome film grain
+ * shaped so that it cannot leave [0, 1] (FSR 1's LFGA), and a triangular dither of one code's amplitude over the sRGB thresholds,
+ * which breaks up the bands of skies, fog and bloom at 8 bits.  The noise is an integer hash of (x, y, seed, draw): the library keeps
+ * NO seed, the same seed gives the same bytes, and a caller who wants grain that moves passes a frame index.  The arithmetic is
+ * published in include/rsrt_finish.h and is bitwise reproducible; with sharpness, grain and dither all 0 the bytes are
+ * rsrt_display_colour_srgb8's.  There is no sharpened IMAGE: the result exists only as bytes, and no other pass can take it as a source.
+ * Whole frame only.  Nothing here writes any buffer the context holds.  A refused call launches nothing.
+ * rsrt_finish_params defaults: sharpness 0.5, grain 0, dither 1, seed 0, flags 0 (RSRT_FINISH_* in include/rsrt_finish.h). */
+#define RSRT_FINISH_NOISE_AWARE 1u /* rsrt_finish_params.flags: sharpen less where a pixel stands out of its cross (salt and pepper at 1 - 4 spp) */
+typedef struct rsrt_finish_params {
+    float sharpness; /* 0 .. 1: 0 skips the sharpener (and its kernel variant reads no neighbour) */
+    float grain;     /* 0 .. 1: the grain's amplitude as a share of min(enc, 1 - enc) */
+    float dither;    /* 0 .. 1: the dither's amplitude in codes; 0 is the hard quantiser */
+    uint32_t seed;   /* of the noise */
+    uint32_t flags;  /* RSRT_FINISH_NOISE_AWARE or 0 */
+    uint32_t _pad[3];
+} rsrt_finish_params;
+/* `source` through the finished display pass: rsrt_finish_sdr per pixel, then rsrt_finish_pixel over its cross (include/rsrt_finish.h),
+ * RGBA8, alpha 255.  Sources, `local`, bloom_intensity, `colour`, readiness and errors exactly as for rsrt_display_colour_srgb8, and
+ * RSRT_ERR_INVALID_ARGUMENT for NULL finish or one rsrt_finish_params_ok refuses (sharpness, grain or dither not finite and in [0, 1],
+ * an unknown flag).
+ * Rust: pub fn rsrt_display_finished_srgb8(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                          local: *const RsrtLocalParams, bloom_intensity: f32, colour: *const RsrtColourParams,
+ *                                          finish: *const RsrtFinishParams, host_rgba8: *mut u8, n_bytes: usize) -> i32; */
+rsrt_status rsrt_display_finished_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                                        float bloom_intensity, const rsrt_colour_params *colour, const rsrt_finish_params *finish, uint8_t *host_rgba8,
+                                        size_t n_bytes);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

@@ -15,6 +15,7 @@
 #include "rsrt.h"
 #include "rsrt_bloom.h"
 #include "rsrt_colour.h"
+#include "rsrt_finish.h"
 #include "rsrt_dof.h"
 #include "rsrt_motion.h"
 #include "rsrt_exposure.h"
@@ -482,6 +483,26 @@ public:
         if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
         std::vector<uint8_t> out(source_pixels(source) * 4);
         check_ctx(rsrt_display_colour_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, out.data(), out.size()));
+        return out;
+    }
+    // -- finished display (rsrt.h "finished display"): one device, like the denoiser --------------------------------------
+    static rsrt_finish_params finish_defaults()
+    {
+        return rsrt_finish_params{RSRT_FINISH_SHARPNESS, RSRT_FINISH_GRAIN, RSRT_FINISH_DITHER, RSRT_FINISH_SEED, RSRT_FINISH_FLAGS, {0u, 0u, 0u}};
+    }
+    // display_colour (whose arguments source .. bloom_intensity are) with the sharpener, the film grain and the dithered quantiser of
+    // `finish` behind the LUT; finish.seed seeds the noise: a frame index for grain that moves, the same seed for the same bytes
+    std::vector<uint8_t> display_finished(const rsrt_finish_params &finish = finish_defaults(), uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f,
+                                          const float *white = nullptr, float lut_strength = -1.0f, const rsrt_local_params *local = nullptr,
+                                          float bloom_intensity = 0.0f)
+    {
+        const bool remembered = white_[0] != 0.0f;
+        rsrt_colour_params c{{1.0f, 1.0f, 1.0f}, lut_strength, 0u, {0u, 0u, 0u}};
+        for (int i = 0; i < 3; i++) c.white[i] = white ? white[i] : (remembered ? white_[i] : 1.0f);
+        if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
+        std::vector<uint8_t> out(source_pixels(source) * 4);
+        check_ctx(rsrt_display_finished_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &finish, out.data(),
+                                              out.size()));
         return out;
     }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------

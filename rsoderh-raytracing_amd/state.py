@@ -45,7 +45,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_fog_apply_upsampled",
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
-            "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8"]
+            "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8", "rsrt_display_finished_srgb8"]
 
 
 class RsrtError(RuntimeError):
@@ -199,6 +199,15 @@ class CdlParams(C.Structure):
 
 class ColourParams(C.Structure):
     _fields_ = [("white", C.c_float * 3), ("lut_strength", C.c_float), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+# the finished display (include/rsrt.h "finished display", include/rsrt_finish.h): its flag, its defaults and its parameters
+FINISH_NOISE_AWARE = 1  # rsrt_finish_params.flags: sharpen less where a pixel stands out of its cross
+FINISH_DEFAULTS = {"sharpness": 0.5, "grain": 0.0, "dither": 1.0, "seed": 0, "flags": 0}
+
+
+class FinishParams(C.Structure):
+    _fields_ = [("sharpness", C.c_float), ("grain", C.c_float), ("dither", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 3)]
 
 
 # the procedural daylight sky (include/rsrt.h rsrt_environment_sky, include/rsrt_sky.h): its defaults (RSRT_SKY_*) and its parameters.
@@ -426,6 +435,7 @@ def lib():
         L.rsrt_colour_lut_download.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsrt_colour_lut_reset.argtypes = [C.c_void_p]
         L.rsrt_display_colour_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_display_finished_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         _lib = L
     return _lib
 
@@ -1032,6 +1042,30 @@ class State:
         self._check(self._L.rsrt_display_colour_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
                                                       C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), _p(out), out.size),
                     "rsrt_display_colour_srgb8")
+        return out
+
+    # -- finished display (include/rsrt.h "finished display") -----------------------------------------------
+    def display_finished_srgb8(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
+                               sharpness=None, grain=None, dither=None, seed=None, noise_aware=False, sample_total=None, **params):
+        """rsrt_display_finished_srgb8: display_colour_srgb8 (whose arguments `source` .. `bloom_intensity`, sample_total and params are)
+        with the sharpener at `sharpness`, film grain at `grain` and the dithered quantiser at `dither` behind the LUT (None:
+        FINISH_DEFAULTS), the noise seeded with `seed` (pass a frame index for grain that moves; the same seed gives the same bytes; an integer
+        of any size or sign, of which the low 32 bits are used);
+        noise_aware: the sharpener's limiter (FINISH_NOISE_AWARE).  [H, W, 4] uint8, of the source's own size."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        if white is None:
+            white = (1.0, 1.0, 1.0) if self.white is None else self.white
+        if lut_strength is None:
+            lut_strength = 1.0 if self._has_colour_lut() else 0.0
+        c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
+        d = FINISH_DEFAULTS
+        f = FinishParams(d["sharpness"] if sharpness is None else sharpness, d["grain"] if grain is None else grain, d["dither"] if dither is None else dither,
+                         (d["seed"] if seed is None else int(seed)) & 0xFFFFFFFF, d["flags"] | (FINISH_NOISE_AWARE if noise_aware else 0), (C.c_uint32 * 3)())
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
+        n = self.sample_count if sample_total is None else sample_total
+        self._check(self._L.rsrt_display_finished_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
+                                                        C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(f), _p(out), out.size),
+                    "rsrt_display_finished_srgb8")
         return out
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------

@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [foghalf=on] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [foghalf=on] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] [finish=SHARPNESS[,GRAIN[,DITHER]]] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -27,7 +27,10 @@ composes with everything above.  The sky's default scale leaves daylight far abo
 wb=auto: meter the chroma of the picture that is written (State.auto_white_balance), print the white point and multiply it in before the
 tone map; wb=R,G,B: those gains.  cdl=SLOPE,OFFSET,POWER,SAT: bake that ASC CDL into a 33^3 LUT on the device (State.colour_lut) and read
 the tone-mapped picture through it.  Either one sends the picture through the colour display (State.display_colour_srgb8), which
-composes with exposure= (1 without), bloom=, local=, dof= and sky=:  house 960 540 64 8 out.png sky=8,120 exposure=auto wb=auto"""
+composes with exposure= (1 without), bloom=, local=, dof= and sky=:  house 960 540 64 8 out.png sky=8,120 exposure=auto wb=auto
+finish=SHARPNESS[,GRAIN[,DITHER]]: the final display goes through the finished display (State.display_finished_srgb8) with whatever
+exposure=, wb=, cdl=, local= and bloom= were given: the sharpener at SHARPNESS (0 .. 1), film grain at GRAIN (default 0) and the dithered
+quantiser at DITHER (default 1), seed 0."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -52,7 +55,8 @@ wb = next((a[len("wb="):] for a in sys.argv[1:] if a.startswith("wb=")), None)
 if wb is not None and wb != "auto":
     wb = tuple(float(v) for v in wb.split(","))
 cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "foghalf=", "sky=", "wb=", "cdl="))]
+finish = next((tuple(float(v) for v in a[len("finish="):].split(",")) for a in sys.argv[1:] if a.startswith("finish=")), None)
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "foghalf=", "sky=", "wb=", "cdl=", "finish="))]
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
@@ -108,7 +112,7 @@ if exposure == "auto":
     r = st.auto_exposure(source)
     print("metered exposure %.6g, average luminance %.6g (%d pixels metered, %d skipped)" % (r["exposure"], r["average_luminance"], r["metered"], r["skipped"]))
     exposure = r["exposure"]
-if wb is not None or cdl is not None:
+if wb is not None or cdl is not None or finish is not None:
     if wb == "auto":
         r = st.auto_white_balance(source)
         print("white point %.4f %.4f %.4f (illuminant %.4f 1 %.4f; %d of %d pixels in the window%s)" % (r["white"] + (r["illuminant"][0], r["illuminant"][2], r["gated"],
@@ -121,8 +125,13 @@ if wb is not None or cdl is not None:
     if local is not None:
         st.local_exposure(source)
         strengths = {"shadows": R.state.LOCAL_DEFAULTS["shadows"] if local[0] is None else local[0], "highlights": local[1]}
-    host.write_png(out, st.display_colour_srgb8(source, 1.0 if exposure is None else exposure, wb or (1.0, 1.0, 1.0), 1.0 if cdl is not None else 0.0,
-                                                bloom_intensity=bloom or 0.0, **(strengths if local is not None else {})))
+    show = st.display_colour_srgb8
+    if finish is not None:
+        knobs = dict(zip(("sharpness", "grain", "dither"), finish))
+        print("finish: sharpness %g, grain %g, dither %g" % tuple(knobs.get(k, R.state.FINISH_DEFAULTS[k]) for k in ("sharpness", "grain", "dither")))
+        show = lambda *a, **kw: st.display_finished_srgb8(*a, **kw, **knobs)
+    host.write_png(out, show(source, 1.0 if exposure is None else exposure, wb or (1.0, 1.0, 1.0), 1.0 if cdl is not None else 0.0,
+                        bloom_intensity=bloom or 0.0, **(strengths if local is not None else {})))
 elif local is not None:
     if bloom is not None:
         st.bloom(source, exposure)
