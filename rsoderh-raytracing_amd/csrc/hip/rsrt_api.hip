@@ -1726,7 +1726,7 @@ rsrt_status rsrt_render(rsrt_context *ctx, const rsrt_camera *camera, uint32_t w
         bpc = std::min(nb, 8);
     }
 
-    const size_t need_cold = (size_t)ctx->cus * bpc * (block / RT_WAVE) * pool_wave_cold_dwords(trav, pool) * sizeof(uint32_t); // cold path-state arena: one block of columns per wave that can be resident
+    const size_t need_cold = (size_t)ctx->cus * bpc * (block / RT_WAVE) * pool_wave_cold_dwords(trav, pool) * sizeof(uint32_t); // cold path-state arena: one block (rt_cold_layout.h: the walks' columns, the flat kernel's 64-byte records) per wave that can be resident
     // the context's buffers are shared by every call: enqueue_pass orders each resolve after whatever ran last (another stream's
     // render, rsrt_accumulator_clear on the context's own stream, ...)
     rsrt_context::Lane *last_lane = nullptr;

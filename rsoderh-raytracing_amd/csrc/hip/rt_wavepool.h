@@ -18,11 +18,17 @@
 // are in LDS, 11 dwords per slot; the COLD columns — throughput, radiance, the pending NEE term, last pdf ... —
 // only read / written by the shading stages, are in a global-memory arena (14 dwords per slot for the tree
 // walks; 11 for the flat traversal, whose RNG word, bounce count and hit record ride in hot cells that are
-// idle at the time, + 2 that only a ray cut short by the triangle-loop vote touches; one contiguous column per
-// field and wave, so a stage's accesses coalesce).  The arena does not fit the L2 (5 MB an XCD for the flat kernel), so
+// idle at the time, + 2 that only a ray cut short by the triangle-loop vote touches).  Where a field lies is
+// rt_cold_layout.h's cold_index.  The walks keep one contiguous column per field and wave.  The flat kernel keeps one
+// 64-byte record per slot, its fields grouped into 16-byte quads by the stages that touch them together: a stage trip
+// runs 64 of a pool's 192 slots, about every third, so a store to a 768-byte column dirtied all twelve of its 64-byte
+// segments for a third of their bytes, ten columns a SHADE trip; a record is dirtied by its own slot alone, and the
+// stage's stores hit the lines its loads have just brought in (profiles/cold_layout_ab.txt).  The arena does not fit
+// the L2 (6.3 MB an XCD for the flat kernel), so
 // what is stored to it goes out over the fabric, and the kernel waits for that: stores it does not need are worth more
 // than the instructions around them (profiles/lazy_nee_ab.txt).  The flat kernel therefore stores nothing for a new
-// path but its output slot — throughput 1, radiance 0 and last pdf 1 are known from the bounce count, kFreshInCt below.
+// path — throughput 1, radiance 0 and last pdf 1 are known from the bounce count (kFreshInCt below), and the output slot waits
+// in an idle hot cell until the first SHADE stores it with the radiance (kOutHot).
 //
 // Stages: GEN    take the next (pixel, sample) of the wave's chunk, build the camera ray — and trace it (its first
 //                round, for the walks) then and there: the lanes are all busy and the rays of a tile coherent
@@ -41,6 +47,7 @@
 #pragma once
 #include "rt_device.h"
 #include "rt_coop.h"
+#include "rt_cold_layout.h"
 
 enum HotField { H_OX, H_OY, H_OZ, H_EX, H_EY, H_EZ, H_SX, H_SY, H_SZ, H_T, H_CT, H_COUNT };
 // H_CT: stage tag (3 bits) | flags (4 bits) | cursor of the traversal in progress, or the record of the hit it found (25 bits)
@@ -52,31 +59,13 @@ enum CtBits : uint32_t {
     CT_FLAGS = 120u,
     CT_SHIFT = 7u
 };
-enum ColdField {
-    C_TX, C_TY, C_TZ, C_LX, C_LY, C_LZ, C_NEEX, C_NEEY, C_NEEZ, C_LASTPDF, C_OUT,
-    C_RNG, // (the flat traversal keeps it in a hot cell)
-    C_BOUNCE,
-    C_REF, // tree-walk traversals only: best hit of the extension ray, record | source << 30
-    C_COUNT,
-    // the flat traversal stops early: its bounce count and hit record ride in the idle cursor bits of H_CT; two columns
-    // hold the untested triangles of a ray whose triangle loop was cut short (only such rays touch them)
-    C_REM_LO = C_RNG, C_REM_HI = C_BOUNCE,
-    C_COUNT_FLAT = C_REF
-};
+// ColdField, pool_cold_columns, pool_wave_cold_dwords and cold_index: rt_cold_layout.h
 #define RT_FLAT_BOUNCE_SHIFT 8u     // flat traversal, H_CT payload: hit record (6-bit index | 2-bit source) | bounce << 8 | resumed << 24
 #define RT_FLAT_BOUNCE_BITS 0xffff00u
 #define RT_FLAT_RESUMED (1u << 24)
 #define RT_FLAT_MAX_BOUNCES 0xffffu // 16 bits of the 25; rsrt_render picks a tree-walk kernel beyond that
-// the wide walk parks an unfinished ray's stack in columns of its own, and a deep tree's walk keeps the bottom of its stack there (RT_WSTATE_WORDS
-// columns, rt_device.h WalkState); only such rays touch them
-#define C_WIDE_STATE ((uint32_t)C_COUNT)
-#define C_COUNT_WIDE ((uint32_t)C_COUNT + 2u + RT_WSTACK)   /* TRAV 4: next node, pending group, the register stack */
-#define C_COUNT_WIDE_DEEP ((uint32_t)C_COUNT + RT_WSTATE_WORDS) /* TRAV 5: + overflow count and overflow words */
-__host__ __device__ constexpr uint32_t pool_cold_columns(int trav)
-{
-    // (6, the cooperative walk: no C_REF — the hit's record waits in the slot's hot result cell — and nothing parked)
-    return trav == 2 ? (uint32_t)C_COUNT_FLAT : (trav == 4 ? C_COUNT_WIDE : (trav == 5 ? C_COUNT_WIDE_DEEP : (trav == 6 ? (uint32_t)C_REF : (uint32_t)C_COUNT)));
-}
+static_assert(kColdWideStack == RT_WSTACK && kColdWideStateWords == RT_WSTATE_WORDS && kColdCoopOverflow == RT_COOP_GCAP,
+              "rt_cold_layout.h sizes the walks' columns by the walks' own constants");
 enum PoolTag { TAG_FREE = 0, TAG_TRACE = 1, TAG_MISS = 2, TAG_SHADE = 3, TAG_FINISH = 4, TAG_IDLE = 6 };
 enum PoolStage { ST_GEN = 0, ST_TRACE = 1, ST_MISS = 2, ST_SHADE = 3, ST_FINISH = 4, ST_COUNT = 5 };
 
@@ -86,7 +75,6 @@ enum PoolStage { ST_GEN = 0, ST_TRACE = 1, ST_MISS = 2, ST_SHADE = 3, ST_FINISH 
 __host__ __device__ constexpr uint32_t pool_hot_columns(int trav) { return trav == 6 ? 12u : (uint32_t)H_COUNT; }
 __host__ __device__ constexpr uint32_t pool_list_dwords(int trav) { return trav == 6 ? RT_COOP_LCAP : 64u; }
 __host__ __device__ constexpr uint32_t pool_wave_lds_dwords(int trav, uint32_t pool) { return pool_hot_columns(trav) * pool + pool_list_dwords(trav) + (trav == 6 ? RT_COOP_NCAP + RT_COOP_MAP : 0u); }
-__host__ __device__ constexpr uint32_t pool_wave_cold_dwords(int trav, uint32_t pool) { return pool_cold_columns(trav) * pool + (trav == 6 ? RT_COOP_GCAP : 0u); }
 template <uint32_t POOL, int TRAV>
 struct PoolLayout {
     static constexpr uint32_t kSlotsPerLane = (POOL + 63u) / 64u;
@@ -143,9 +131,15 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
     constexpr bool kBounceInCt = TRAV == 2; // no C_BOUNCE / C_REF column
     // Flat traversal: a new path's throughput (1), radiance (0) and last pdf (1) are not written to the arena.  The bounce count in
     // H_CT is 0 exactly until the path's first SHADE has run, so whichever stage picks the path up first (SHADE, or MISS if the camera
-    // ray escapes) takes the constants instead of what it loaded — the slot's previous path's values — and GEN stores one cold word a
-    // path, C_OUT, instead of eight: arena writes are what this kernel waits for (profiles/lazy_nee_ab.txt).
+    // ray escapes) takes the constants instead of what it loaded — the slot's previous path's values: arena writes are what this kernel
+    // waits for (profiles/lazy_nee_ab.txt).
     constexpr bool kFreshInCt = kBounceInCt;
+    // ... and GEN stores nothing to the arena at all: a new path's output slot waits in H_SY, the second cell of the shadow direction,
+    // which nothing touches before the path's first SHADE has read it (H_SX holds the camera ray's t).  The first stage takes it from
+    // there; SHADE stores it with the radiance, one full 16-byte quad of the slot's record (rt_cold_layout.h), and every later stage
+    // reads it from the record.  A camera ray that escapes never touches the record.  GEN's lone 4-byte store dirtied a record of its
+    // own a path: leaving it out is worth 1.8 ms of the house frame (profiles/cold_layout_ab.txt).
+    constexpr bool kOutHot = kFreshInCt;
     // Flat traversal: a ray finishes in one TRACE call — or is cut short by the triangle-loop vote with its best t parked where the
     // result would go — so "best t so far" is INFINITY at every fresh start and the H_T cell is
     // only needed for the RESULT of the extension ray — which fits the shadow direction's first cell, dead by then (the
@@ -185,9 +179,9 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
 // (TRAV 6: the extension ray's result cell, rt_coop.h CoopCols::BEST)
 #define BEST_REF(slot) W[9u * POOL + 2u * (slot)]
 #define BEST_T(slot) W[9u * POOL + 2u * (slot) + 1u]
-#define COLD(f, slot) G[(f) * POOL + (slot)]
-#define COLDF(f, slot) as_f(G[(f) * POOL + (slot)])
-#define SETC(f, slot, val) G[(f) * POOL + (slot)] = as_u(val)
+#define COLD(f, slot) G[cold_index(TRAV, POOL, (f), (slot))]
+#define COLDF(f, slot) as_f(COLD(f, slot))
+#define SETC(f, slot, val) COLD(f, slot) = as_u(val)
 
     for (uint32_t k = 0; k < L::kSlotsPerLane; k++)
         if (lane0 + 64u * k < POOL) SET_TAG(lane0 + 64u * k, TAG_FREE);
@@ -261,7 +255,7 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
         h.ref = (TRAV >= 3 && !shadow) ? RT_REF_UNKNOWN : ((kFlatVote && cur != 0u) ? ((ct >> CT_SHIFT) & 63u) : 0u);
         const float t_in = h.t;
         trace_dispatch<TRAV>(DBG_ARG S, sc, o, d, prune, shadow && anyhit_shadow, P.trace_budget, TRAV == 2 ? (kFlatVote ? P.flat_quorum : 0u) : P.descend_quorum,
-                             cur, h, &COLD(C_REF, slot), n_work, flat_rem, TRAV >= 4 ? &G[C_WIDE_STATE * POOL + slot] : nullptr, POOL, P.stop_quorum, coherent);
+                             cur, h, TRAV == 2 ? nullptr : &COLD(C_REF, slot), n_work, flat_rem, TRAV >= 4 ? &G[C_WIDE_STATE * POOL + slot] : nullptr, POOL, P.stop_quorum, coherent);
         ray_end(slot, ct, h, cur, t_in, flat_rem);
     };
     for (;;) {
@@ -349,7 +343,8 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                         }
                         if (!kRngHot) COLD(C_RNG, slot) = ps.rng;
                         if (!kBounceInCt) COLD(C_BOUNCE, slot) = 0u;
-                        COLD(C_OUT, slot) = srel * P.n_slots + chunk_tile_slot0 + p;
+                        if (kOutHot) SETHU(H_SY, slot, srel * P.n_slots + chunk_tile_slot0 + p);
+                        else COLD(C_OUT, slot) = srel * P.n_slots + chunk_tile_slot0 + p;
                         if (kGenTrace) { started = true; cam_o = ps.o; cam_d = ps.d; }
                         else SET_CT(slot, 0u, F_EXT, TAG_TRACE);
                         n_paths++;
@@ -438,16 +433,31 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 const EnvBilinearFetch sky_fetch = kPackedMiss ? sample_env_bilinear_begin_pmf(P.env, env_u, env_v) : sample_env_bilinear_begin(P.env, env_u, env_v);
                 float sky_pmf = 0.0f;
                 if (!kPackedMiss) sky_pmf = environment_direction_pmf(P.env, env_u, env_v);
-                float last_pdf = COLDF(C_LASTPDF, slot);
-                V3 T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
-                V3 Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
-                if (kFreshInCt && ((ct >> CT_SHIFT) & RT_FLAT_BOUNCE_BITS) == 0u) { // the camera ray: nothing of this path is in the arena yet
-                    last_pdf = 1.0f;
-                    T = v3(1.0f, 1.0f, 1.0f);
-                    Lr = v3(0.0f, 0.0f, 0.0f);
+                float last_pdf;
+                V3 T, Lr, nee_prev;
+                uint32_t out_slot;
+                if constexpr (!kFreshInCt) {
+                    last_pdf = COLDF(C_LASTPDF, slot);
+                    T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
+                    Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
+                    nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
+                    out_slot = COLD(C_OUT, slot);
+                } else {
+                    // the camera ray: nothing of this path is in the arena yet — its constants, and its output slot from where GEN left it
+                    const bool fresh = ((ct >> CT_SHIFT) & RT_FLAT_BOUNCE_BITS) == 0u;
+                    const uint32_t out_hot = HOT(H_SY, slot);
+                    last_pdf = COLDF(C_LASTPDF, slot);
+                    T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
+                    Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
+                    nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
+                    out_slot = COLD(C_OUT, slot);
+                    if (fresh) {
+                        last_pdf = 1.0f;
+                        T = v3(1.0f, 1.0f, 1.0f);
+                        Lr = v3(0.0f, 0.0f, 0.0f);
+                        out_slot = out_hot;
+                    }
                 }
-                const V3 nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
-                const uint32_t out_slot = COLD(C_OUT, slot);
                 Hit h;
                 h.t = RT_INFINITY; h.ref = 0; h.src = SRC_BVH; h.u = h.v = 0.0f;
                 for (uint32_t i = 0; i < sc.n_spheres; i++) {
@@ -503,6 +513,7 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 }
                 DBG_ADD(27, (as_u(hit_record(S, h, 0).w) & 3u) == PRIM_TRIANGLE ? 1 : 0); DBG_ADD(31, (as_u(hit_record(S, h, 0).w) & 3u) == PRIM_SPHERE ? 1 : 0);
                 uint32_t rng, bounce;
+                uint32_t out_slot = 0u; // (kOutHot: the path's output slot, stored back with the radiance)
                 V3 T, Lr;
                 Surface surf;
                 BsdfMaterial mat;
@@ -518,10 +529,12 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                     T = v3(COLDF(C_TX, slot), COLDF(C_TY, slot), COLDF(C_TZ, slot));
                     Lr = v3(COLDF(C_LX, slot), COLDF(C_LY, slot), COLDF(C_LZ, slot));
                     const V3 nee_prev = v3(COLDF(C_NEEX, slot), COLDF(C_NEEY, slot), COLDF(C_NEEZ, slot));
+                    if (kOutHot) out_slot = COLD(C_OUT, slot);
                     bounce = (kBounceInCt ? (ct >> (CT_SHIFT + RT_FLAT_BOUNCE_SHIFT)) : COLD(C_BOUNCE, slot)) + 1u;
                     if (kFreshInCt && bounce == 1u) { // the path's first vertex: nothing of this path is in the arena yet
                         T = v3(1.0f, 1.0f, 1.0f);
                         Lr = v3(0.0f, 0.0f, 0.0f);
+                        if (kOutHot) out_slot = HOT(H_SY, slot); // (where GEN left it)
                     }
                     SHADE_STAMP(10);
                     hit_barycentrics(S, h, o, d); // not carried through the traversal: the same test gives the same bits
@@ -585,10 +598,11 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 }
                 if (bounce >= P.max_bounces) finished = true;
                 if (finished && !want_shadow) {
-                    store_sample(P.sample_buf + (size_t)COLD(C_OUT, slot) * 3u, Lr);
+                    store_sample(P.sample_buf + (size_t)(kOutHot ? out_slot : COLD(C_OUT, slot)) * 3u, Lr);
                     SET_TAG(slot, TAG_FREE);
                 } else {
                     SETC(C_LX, slot, Lr.x); SETC(C_LY, slot, Lr.y); SETC(C_LZ, slot, Lr.z);
+                    if (kOutHot) COLD(C_OUT, slot) = out_slot; // (the quad's fourth dword: as loaded, or a new path's from GEN)
                     if (nee_counts) { SETC(C_NEEX, slot, nee.x); SETC(C_NEEY, slot, nee.y); SETC(C_NEEZ, slot, nee.z); }
                     if (!finished) {
                         SETC(C_LASTPDF, slot, bs.pdf);
