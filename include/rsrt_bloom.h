@@ -37,8 +37,8 @@
  * Chain of N levels:  U_N = D_N;  U_k = D_k + up(tent(U_{k+1})), k = N - 1 .. 1;  the bloom image B = tent(U_1) * (1.0f / (float)N),
  * of D_1's size.
  *
- * Bloomed display pixel: hdr = rsrt_round_to_f16(sum / total) * exposure (rsrt_display_pixel_exposed's), hdr = hdr + intensity * up(B),
- * then rsrt_aces_tone_map and rsrt_srgb8_encode.
+ * Bloomed display pixel: hdr = rsrt_display_hdr_exposed (rsrt_exposure.h), hdr = hdr + intensity * up(B) (rsrt_display_hdr_bloomed), then
+ * rsrt_aces_tone_map and rsrt_display_encode.
  */
 #ifndef RSRT_BLOOM_H
 #define RSRT_BLOOM_H
@@ -46,7 +46,7 @@
 #include <stdint.h>
 
 #include "rsrt.h" /* rsrt_bloom_params, RSRT_BLOOM_KARIS */
-#include "rsrt_tonemap.h"
+#include "rsrt_exposure.h" /* rsrt_display_hdr_exposed */
 
 #define RSRT_BLOOM_MAX_LEVELS 8u
 #define RSRT_BLOOM_CLAMP 65504.0f
@@ -251,18 +251,22 @@ RSRT_HD rsrt_bloom_rgb rsrt_bloom_up_tent_at(const rsrt_bloom_texel *u, int w, i
     return rsrt_bloom_up4(taa, tba, tab, tbb, wx0, wx1, wy0, wy1);
 }
 
+/* the display chain's third step: the exposed mean plus intensity times up(B) at the pixel */
+RSRT_HD void rsrt_display_hdr_bloomed(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float hdr[3])
+{
+    const float bloom[3] = {up_b.r, up_b.g, up_b.b};
+    rsrt_display_hdr_exposed(sum_rgb, total, exposure, hdr);
+    for (int i = 0; i < 3; i++) hdr[i] = hdr[i] + intensity * bloom[i];
+}
+
 /* one pixel: sums (f32) and up(B) at it -> display bytes at an exposure */
 RSRT_HD void rsrt_display_pixel_bloomed(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b,
                                         unsigned char out_rgb[3])
 {
-    const float bloom[3] = {up_b.r, up_b.g, up_b.b};
     float hdr[3], sdr[3];
-    for (int i = 0; i < 3; i++) {
-        hdr[i] = rsrt_round_to_f16(sum_rgb[i] / total) * exposure;
-        hdr[i] = hdr[i] + intensity * bloom[i];
-    }
+    rsrt_display_hdr_bloomed(sum_rgb, total, exposure, intensity, up_b, hdr);
     rsrt_aces_tone_map(hdr, sdr);
-    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+    rsrt_display_encode(sdr, out_rgb);
 }
 
 #endif

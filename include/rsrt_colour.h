@@ -54,11 +54,11 @@
  *   n0 = base, n1 = n0 + a.stride, n2 = n1 + b.stride, n3 = n2 + c.stride, the weights w0 = 1 - a.t, w1 = a.t - b.t, w2 = b.t - c.t,
  *   w3 = c.t, and per channel  g = ((w0 * n0 + w1 * n1) + w2 * n2) + w3 * n3.  Exact at the nodes: every weight is then 0 or 1.
  *
- * Colour display pixel (rsrt_display_pixel_colour):  hdr as rsrt_display_pixel_local forms it (f16-rounded mean times exposure, plus
+ * Colour display pixel (rsrt_display_pixel_colour):  hdr = rsrt_display_hdr_local (rsrt_local.h: the f16-rounded mean times exposure, plus
  *   intensity * up(B), times the local gain);  hdr[i] = hdr[i] * white[i];  rsrt_aces_tone_map;  with lut_strength > 0, per channel:
  *   s = sdr (NaN -> 0),  enc = rsrt_sqrtf(s),  g = the interpolation above at the three enc,  o = enc + lut_strength * (g - enc)
- *   clamped to [0, 1],  sdr = o * o;  then rsrt_srgb8_encode.  With white {1, 1, 1} and lut_strength 0 the bytes are
- *   rsrt_display_local_srgb8's.
+ *   clamped to [0, 1],  sdr = o * o  (up to here: rsrt_display_sdr_colour);  then rsrt_display_encode.  With white {1, 1, 1} and
+ *   lut_strength 0 the bytes are rsrt_display_local_srgb8's.
  */
 #ifndef RSRT_COLOUR_H
 #define RSRT_COLOUR_H
@@ -292,22 +292,25 @@ RSRT_HD void rsrt_colour_grade(const float *lut, uint32_t n, float strength, flo
     }
 }
 
-/* one pixel: sums (f32), up(B) at it (0 where no bloom is asked for), its local gain (1 where none is asked for), the white point and
- * the LUT (looked at only with lut_strength > 0) -> display bytes at an exposure */
+/* the display chain's fifth to seventh step: one pixel's sums (f32), up(B) at it (0 where no bloom is asked for), its local gain (1 where
+ * none is asked for), the white point and the LUT (looked at only with lut_strength > 0) -> the tone-mapped, graded colour */
+RSRT_HD void rsrt_display_sdr_colour(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float gain,
+                                     const rsrt_colour_params *colour, const float *lut, uint32_t n, float sdr[3])
+{
+    float hdr[3];
+    rsrt_display_hdr_local(sum_rgb, total, exposure, intensity, up_b, gain, hdr);
+    for (int i = 0; i < 3; i++) hdr[i] = hdr[i] * colour->white[i];
+    rsrt_aces_tone_map(hdr, sdr);
+    if (colour->lut_strength > 0.0f) rsrt_colour_grade(lut, n, colour->lut_strength, sdr);
+}
+
+/* ... -> display bytes at an exposure */
 RSRT_HD void rsrt_display_pixel_colour(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float gain,
                                        const rsrt_colour_params *colour, const float *lut, uint32_t n, unsigned char out_rgb[3])
 {
-    const float bloom[3] = {up_b.r, up_b.g, up_b.b};
-    float hdr[3], sdr[3];
-    for (int i = 0; i < 3; i++) {
-        hdr[i] = rsrt_round_to_f16(sum_rgb[i] / total) * exposure;
-        hdr[i] = hdr[i] + intensity * bloom[i];
-        hdr[i] = hdr[i] * gain;
-        hdr[i] = hdr[i] * colour->white[i];
-    }
-    rsrt_aces_tone_map(hdr, sdr);
-    if (colour->lut_strength > 0.0f) rsrt_colour_grade(lut, n, colour->lut_strength, sdr);
-    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+    float sdr[3];
+    rsrt_display_sdr_colour(sum_rgb, total, exposure, intensity, up_b, gain, colour, lut, n, sdr);
+    rsrt_display_encode(sdr, out_rgb);
 }
 
 #endif

@@ -32,8 +32,8 @@
  *   N == 0 (nothing metered): metered = 0, average_luminance = 0, target = exposure = (previous_exposure > 0 ? previous_exposure : 1)
  * The library keeps no exposure: adaptation over time is the caller handing the last exposure back as previous_exposure.
  *
- * Exposed display pixel: mean = rsrt_round_to_f16(sum / total), hdr = mean * exposure, then rsrt_aces_tone_map and
- * rsrt_srgb8_encode.  With exposure 1 the multiply is exact and the bytes are rsrt_display_pixel's.
+ * Exposed display pixel: mean = rsrt_display_mean (rsrt_tonemap.h), hdr = mean * exposure (rsrt_display_hdr_exposed), then
+ * rsrt_aces_tone_map and rsrt_display_encode.  With exposure 1 the multiply is exact and the bytes are rsrt_display_pixel's.
  */
 #ifndef RSRT_EXPOSURE_H
 #define RSRT_EXPOSURE_H
@@ -122,13 +122,20 @@ RSRT_HD void rsrt_exposure_from_histogram(const uint32_t *hist, const rsrt_expos
     out->exposure = p->previous_exposure > 0.0f ? p->previous_exposure + (target - p->previous_exposure) * p->blend : target;
 }
 
+/* the display chain's second step: the f16-rounded mean times the exposure */
+RSRT_HD void rsrt_display_hdr_exposed(const float sum_rgb[3], float total, float exposure, float hdr[3])
+{
+    rsrt_display_mean(sum_rgb, total, hdr);
+    for (int i = 0; i < 3; i++) hdr[i] = hdr[i] * exposure;
+}
+
 /* one pixel: sums (f32) -> display bytes at an exposure */
 RSRT_HD void rsrt_display_pixel_exposed(const float sum_rgb[3], float total, float exposure, unsigned char out_rgb[3])
 {
     float hdr[3], sdr[3];
-    for (int i = 0; i < 3; i++) hdr[i] = rsrt_round_to_f16(sum_rgb[i] / total) * exposure;
+    rsrt_display_hdr_exposed(sum_rgb, total, exposure, hdr);
     rsrt_aces_tone_map(hdr, sdr);
-    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+    rsrt_display_encode(sdr, out_rgb);
 }
 
 #endif

@@ -10,9 +10,9 @@
  * exactly the order written here, min(a, b) is a < b ? a : b and max(a, b) is a > b ? a : b, the noise is an integer hash, and a numpy
  * restatement reproduces every bit and byte (tests/finish_ref.py holds it).
  *
- * 1. sdr (rsrt_finish_sdr): the tone-mapped, graded colour of a pixel exactly as rsrt_display_pixel_colour (rsrt_colour.h) forms it up
- *    to, and not including, rsrt_srgb8_encode: f16-rounded mean times exposure, plus intensity * up(B), times the local gain, times the
- *    white point, rsrt_aces_tone_map, rsrt_colour_grade with lut_strength > 0.
+ * 1. sdr (rsrt_finish_sdr): rsrt_display_sdr_colour (rsrt_colour.h), the tone-mapped, graded colour of a pixel that
+ *    rsrt_display_pixel_colour encodes: f16-rounded mean times exposure, plus intensity * up(B), times the local gain, times the white
+ *    point, rsrt_aces_tone_map, rsrt_colour_grade with lut_strength > 0.
  * 2. record (rsrt_finish_record), 4 floats a pixel:  s = sdr > 0 ? (sdr > 1 ? 1 : sdr) : 0  (NaN, -0 and negatives give +0; the clamp is
  *    byte-neutral for the quantiser),  enc = rsrt_sqrtf(s)  per channel, and the luma  L = (0.5f * enc.r + enc.g) + 0.5f * enc.b
  *    (RCAS's: green whole, red and blue halved; 0 .. 2).
@@ -71,16 +71,7 @@ RSRT_HD float rsrt_finish_max(float a, float b) { return a > b ? a : b; }
 RSRT_HD void rsrt_finish_sdr(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float gain,
                              const rsrt_colour_params *colour, const float *lut, uint32_t n, float sdr[3])
 {
-    const float bloom[3] = {up_b.r, up_b.g, up_b.b};
-    float hdr[3];
-    for (int i = 0; i < 3; i++) {
-        hdr[i] = rsrt_round_to_f16(sum_rgb[i] / total) * exposure;
-        hdr[i] = hdr[i] + intensity * bloom[i];
-        hdr[i] = hdr[i] * gain;
-        hdr[i] = hdr[i] * colour->white[i];
-    }
-    rsrt_aces_tone_map(hdr, sdr);
-    if (colour->lut_strength > 0.0f) rsrt_colour_grade(lut, n, colour->lut_strength, sdr);
+    rsrt_display_sdr_colour(sum_rgb, total, exposure, intensity, up_b, gain, colour, lut, n, sdr);
 }
 
 RSRT_HD float rsrt_finish_luma(const float enc[3]) { return (0.5f * enc[0] + enc[1]) + 0.5f * enc[2]; }

@@ -35,9 +35,8 @@
  *   measured over every e = k * 2^-12 in [-16, 16] and the float neighbours of the integers against float64 (tests/test_local.py
  *   asserts 2^-12: a sixteenth of what a display byte is worth near white).
  *
- * Graded display pixel:  hdr = rsrt_round_to_f16(sum / total) * exposure;  hdr = hdr + intensity * up(B) exactly as
- * rsrt_display_pixel_bloomed does (up(B) = 0 where no bloom is asked for);  hdr = hdr * gain;  then rsrt_aces_tone_map and
- * rsrt_srgb8_encode.  The gain comes after the bloom: the glow is light in the lens, the local exposure is the print.  With both
+ * Graded display pixel:  hdr = rsrt_display_hdr_bloomed (rsrt_bloom.h; up(B) = 0 where no bloom is asked for);  hdr = hdr * gain
+ * (rsrt_display_hdr_local);  then rsrt_aces_tone_map and rsrt_display_encode.  The gain comes after the bloom: the glow is light in the lens, the local exposure is the print.  With both
  * strengths 0 the bytes are rsrt_display_exposed_srgb8's (intensity 0) or rsrt_display_bloomed_srgb8's.
  */
 #ifndef RSRT_LOCAL_H
@@ -173,19 +172,21 @@ RSRT_HD float rsrt_local_gain_at(const uint32_t *grid, uint32_t gx, uint32_t gy,
     return rsrt_local_gain(rsrt_local_slice(grid, gx, gy, cell, x, y, q), mid, p);
 }
 
+/* the display chain's fourth step: the bloomed colour times the pixel's gain */
+RSRT_HD void rsrt_display_hdr_local(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float gain, float hdr[3])
+{
+    rsrt_display_hdr_bloomed(sum_rgb, total, exposure, intensity, up_b, hdr);
+    for (int i = 0; i < 3; i++) hdr[i] = hdr[i] * gain;
+}
+
 /* one pixel: sums (f32), up(B) at it (0 where no bloom is asked for) and its gain -> display bytes at an exposure */
 RSRT_HD void rsrt_display_pixel_local(const float sum_rgb[3], float total, float exposure, float intensity, rsrt_bloom_rgb up_b, float gain,
                                       unsigned char out_rgb[3])
 {
-    const float bloom[3] = {up_b.r, up_b.g, up_b.b};
     float hdr[3], sdr[3];
-    for (int i = 0; i < 3; i++) {
-        hdr[i] = rsrt_round_to_f16(sum_rgb[i] / total) * exposure;
-        hdr[i] = hdr[i] + intensity * bloom[i];
-        hdr[i] = hdr[i] * gain;
-    }
+    rsrt_display_hdr_local(sum_rgb, total, exposure, intensity, up_b, gain, hdr);
     rsrt_aces_tone_map(hdr, sdr);
-    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+    rsrt_display_encode(sdr, out_rgb);
 }
 
 #endif

@@ -352,9 +352,7 @@ public:
             if (exposure_ == 0.0f) throw Error("display_exposed: no remembered exposure (auto_exposure first): RSRT_ERR_NOT_READY");
             exposure = exposure_;
         }
-        std::vector<uint8_t> out(source_pixels(source) * 4);
-        check_ctx(rsrt_display_exposed_srgb8(context(0), source, sample_count_, exposure, out.data(), out.size()));
-        return out;
+        return displayed(rsrt_display_exposed_srgb8, source, exposure);
     }
     // -- bloom (rsrt.h "bloom"): one device, like the denoiser -----------------------------------------------------
     static rsrt_bloom_params bloom_defaults() { return rsrt_bloom_params{RSRT_BLOOM_LEVELS, RSRT_BLOOM_FLAGS, RSRT_BLOOM_THRESHOLD, 0.0f}; }
@@ -377,9 +375,7 @@ public:
     // doubled bloom image added before the tone map; of the source's own size
     std::vector<uint8_t> display_bloomed(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, float intensity = RSRT_BLOOM_INTENSITY)
     {
-        std::vector<uint8_t> out(source_pixels(source) * 4);
-        check_ctx(rsrt_display_bloomed_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), intensity, out.data(), out.size()));
-        return out;
+        return displayed(rsrt_display_bloomed_srgb8, source, exposure_or_one(exposure), intensity);
     }
     // -- local exposure (rsrt.h "local exposure"): one device, like the denoiser --------------------------------------
     static rsrt_local_params local_defaults()
@@ -413,9 +409,7 @@ public:
     std::vector<uint8_t> display_local(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const rsrt_local_params &p = local_defaults(),
                                        float bloom_intensity = 0.0f)
     {
-        std::vector<uint8_t> out(source_pixels(source) * 4);
-        check_ctx(rsrt_display_local_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), &p, bloom_intensity, out.data(), out.size()));
-        return out;
+        return displayed(rsrt_display_local_srgb8, source, exposure_or_one(exposure), &p, bloom_intensity);
     }
     // -- white balance and colour grading (rsrt.h "white balance and colour grading"): one device, like the denoiser ----
     static rsrt_white_params white_defaults()
@@ -477,13 +471,8 @@ public:
     std::vector<uint8_t> display_colour(uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const float *white = nullptr, float lut_strength = -1.0f,
                                         const rsrt_local_params *local = nullptr, float bloom_intensity = 0.0f)
     {
-        const bool remembered = white_[0] != 0.0f;
-        rsrt_colour_params c{{1.0f, 1.0f, 1.0f}, lut_strength, 0u, {0u, 0u, 0u}};
-        for (int i = 0; i < 3; i++) c.white[i] = white ? white[i] : (remembered ? white_[i] : 1.0f);
-        if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
-        std::vector<uint8_t> out(source_pixels(source) * 4);
-        check_ctx(rsrt_display_colour_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, out.data(), out.size()));
-        return out;
+        const rsrt_colour_params c = colour_params(white, lut_strength);
+        return displayed(rsrt_display_colour_srgb8, source, exposure_or_one(exposure), local, bloom_intensity, &c);
     }
     // -- finished display (rsrt.h "finished display"): one device, like the denoiser --------------------------------------
     static rsrt_finish_params finish_defaults()
@@ -496,14 +485,8 @@ public:
                                           const float *white = nullptr, float lut_strength = -1.0f, const rsrt_local_params *local = nullptr,
                                           float bloom_intensity = 0.0f)
     {
-        const bool remembered = white_[0] != 0.0f;
-        rsrt_colour_params c{{1.0f, 1.0f, 1.0f}, lut_strength, 0u, {0u, 0u, 0u}};
-        for (int i = 0; i < 3; i++) c.white[i] = white ? white[i] : (remembered ? white_[i] : 1.0f);
-        if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
-        std::vector<uint8_t> out(source_pixels(source) * 4);
-        check_ctx(rsrt_display_finished_srgb8(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &finish, out.data(),
-                                              out.size()));
-        return out;
+        const rsrt_colour_params c = colour_params(white, lut_strength);
+        return displayed(rsrt_display_finished_srgb8, source, exposure_or_one(exposure), local, bloom_intensity, &c, &finish);
     }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------
     static rsrt_dof_params dof_defaults() { return rsrt_dof_params{RSRT_DOF_FOCUS_DISTANCE, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS}; }
@@ -819,6 +802,23 @@ private:
         }
         const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
         return (size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_);
+    }
+    // a display into a vector: display(context, source, sample_count, args..., bytes, their number), RGBA8 of the source's own size
+    template <class Display, class... Args>
+    std::vector<uint8_t> displayed(Display display, uint32_t source, Args... args)
+    {
+        std::vector<uint8_t> out(source_pixels(source) * 4);
+        check_ctx(display(context(0), source, sample_count_, args..., out.data(), out.size()));
+        return out;
+    }
+    // the colour displays' parameters: `white` (NULL: the remembered white point, else 1) and lut_strength (negative: 1 with a LUT, 0 without)
+    rsrt_colour_params colour_params(const float *white, float lut_strength)
+    {
+        const bool remembered = white_[0] != 0.0f;
+        rsrt_colour_params c{{1.0f, 1.0f, 1.0f}, lut_strength, 0u, {0u, 0u, 0u}};
+        for (int i = 0; i < 3; i++) c.white[i] = white ? white[i] : (remembered ? white_[i] : 1.0f);
+        if (lut_strength < 0.0f) c.lut_strength = rsrt_colour_lut_download(context(0), nullptr, 0, nullptr) == RSRT_OK ? RSRT_COLOUR_LUT_STRENGTH : 0.0f;
+        return c;
     }
 };
 

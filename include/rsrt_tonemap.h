@@ -76,13 +76,25 @@ RSRT_HD float rsrt_round_to_f16(float f)
     return out.f;
 }
 
+/* the display chain's first step (rsrt_exposure.h, _bloom.h, _local.h, _colour.h each add one): the mean as the rgba16float texture holds it */
+RSRT_HD void rsrt_display_mean(const float sum_rgb[3], float total, float mean[3])
+{
+    for (int i = 0; i < 3; i++) mean[i] = rsrt_round_to_f16(sum_rgb[i] / total);
+}
+
+/* last step: tone-mapped colour -> display bytes */
+RSRT_HD void rsrt_display_encode(const float sdr[3], unsigned char out_rgb[3])
+{
+    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+}
+
 /* one pixel: sums (f32) -> display bytes */
 RSRT_HD void rsrt_display_pixel(const float sum_rgb[3], float sample_total, unsigned char out_rgb[3])
 {
     float mean[3], sdr[3];
-    for (int i = 0; i < 3; i++) mean[i] = rsrt_round_to_f16(sum_rgb[i] / sample_total);
+    rsrt_display_mean(sum_rgb, sample_total, mean);
     rsrt_aces_tone_map(mean, sdr);
-    for (int i = 0; i < 3; i++) out_rgb[i] = (unsigned char)rsrt_srgb8_encode(sdr[i]);
+    rsrt_display_encode(sdr, out_rgb);
 }
 
 #endif

@@ -507,6 +507,13 @@ struct SizedAlloc {
     bool is(uint32_t W, uint32_t H) const { return p && w == W && h == H; }
     size_t pixels() const { return (size_t)w * h; }
 };
+// A histogram meter (rt_exposure.h): two histograms in one allocation (a call adds into the zero one and zeroes the other for the next),
+// which of them holds the last call's, whether there was one since the last reset, and whether a failed launch left them unknown.
+struct HistMeter {
+    uint32_t *hist = nullptr;
+    uint32_t cur = 0;
+    bool have = false, dirty = false;
+};
 // An image one of the passes can read: sums of `total` samples a pixel (1: a colour).
 struct ImageView {
     const float4 *img = nullptr;
@@ -640,12 +647,8 @@ struct rsrt_context {
     uint32_t ns_tx = 0, ns_ty = 0;
     float ns_threshold = 0.0f;
     bool ns_have = false;
-    // auto-exposure (rt_exposure.h): two histograms (a call adds into the zero one and zeroes the other for the next call), which of
-    // them holds the last rsrt_exposure_meter's, whether there was one since the last reset, and whether a failed launch left them in an
-    // unknown state.  The library keeps no exposure.
-    uint32_t *ex_hist = nullptr;
-    uint32_t ex_cur = 0;
-    bool ex_have = false, ex_dirty = false;
+    // auto-exposure (rt_exposure.h): the luminance histograms of rsrt_exposure_meter.  The library keeps no exposure.
+    HistMeter ex;
     // bloom (rt_bloom.h): the pyramid of the last rsrt_bloom — B, then D_1 .. D_8 — which follows the size of the source B was built
     // for, and whether there was one since the last reset
     SizedAlloc bl_pyr;
@@ -675,12 +678,10 @@ struct rsrt_context {
     SizedAlloc fg_out, fg_src;
     ImageView fg_last;
     const PixelBuffer *fg_rec = nullptr;
-    // white balance and colour grading (rt_colour.h): two chroma histograms, kept as the exposure meter keeps its two, and the colour LUT
-    // (cl_cap float4 nodes of room; cl_n the LUT's size, 0: none).  Neither follows the accumulator's size: accumulator_size_changed()
-    // leaves them.  The library keeps no white point.
-    uint32_t *wb_hist = nullptr;
-    uint32_t wb_cur = 0;
-    bool wb_have = false, wb_dirty = false;
+    // white balance and colour grading (rt_colour.h): the chroma histograms of rsrt_white_meter and the colour LUT (cl_cap float4 nodes
+    // of room; cl_n the LUT's size, 0: none).  Neither follows the accumulator's size: accumulator_size_changed() leaves them.  The
+    // library keeps no white point.
+    HistMeter wb;
     float4 *cl_lut = nullptr;
     size_t cl_cap = 0;
     uint32_t cl_n = 0;
@@ -1240,8 +1241,8 @@ void rsrt_context_destroy(rsrt_context *ctx)
     release(ctx->up_out);
     release(ctx->fg_src);
     (void)hipFree(ctx->ns_tiles);
-    (void)hipFree(ctx->ex_hist);
-    (void)hipFree(ctx->wb_hist);
+    (void)hipFree(ctx->ex.hist);
+    (void)hipFree(ctx->wb.hist);
     (void)hipFree(ctx->cl_lut);
     for (auto &L : ctx->lanes) {
         (void)hipFree(L.sample_buf);

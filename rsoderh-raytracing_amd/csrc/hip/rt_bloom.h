@@ -126,6 +126,20 @@ rsrt_status bloom_source(rsrt_context *ctx, const char *what, uint32_t source, u
     return resolve_image(ctx, what, "", source, sample_total, false, v);
 }
 
+// what a pass built for one source is v's too, or "<what>: the bloom image was built for WxH, the source is WxH" (and the grid likewise)
+rsrt_status built_for(rsrt_context *ctx, const char *what, const char *piece, const SizedAlloc &a, const ImageView &v)
+{
+    if (a.is(v.w, v.h)) return RSRT_OK;
+    return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the %s was built for %ux%u, the source is %ux%u", what, piece, a.w, a.h, v.w, v.h);
+}
+
+// there is a bloom image, and it is v's
+rsrt_status bloom_ready(rsrt_context *ctx, const char *what, const ImageView &v)
+{
+    if (!ctx->bl_have) return fail(ctx, RSRT_ERR_NOT_READY, "no bloom image (rsrt_bloom first)");
+    return built_for(ctx, what, "bloom image", ctx->bl_pyr, v);
+}
+
 } // namespace
 
 extern "C" {
@@ -211,9 +225,7 @@ rsrt_status rsrt_display_bloomed_srgb8(rsrt_context *ctx, uint32_t source, uint3
     const size_t n = v.pixels();
     if (!rsrt_bloom_finite_nonneg(intensity)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_bloomed_srgb8: intensity must be finite and >= 0");
     if (!host_rgba8 || n_bytes != n * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_bloomed_srgb8: expected %zu bytes", n * 4);
-    if (!ctx->bl_have) return fail(ctx, RSRT_ERR_NOT_READY, "no bloom image (rsrt_bloom first)");
-    if (!ctx->bl_pyr.is(v.w, v.h))
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "display_bloomed_srgb8: the bloom image was built for %ux%u, the source is %ux%u", ctx->bl_pyr.w, ctx->bl_pyr.h, v.w, v.h);
+    if ((st = bloom_ready(ctx, "display_bloomed_srgb8", v))) return st; // (at intensity 0 too)
     const uint32_t bw = rsrt_bloom_level_size(v.w, 1), bh = rsrt_bloom_level_size(v.h, 1);
     return read_back(ctx, host_rgba8, n * sizeof(uchar4), 0, [&](void *tmp) {
         rt_display_bloomed_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(v.img, (int)v.w, (int)v.h, v.total, exposure, intensity,

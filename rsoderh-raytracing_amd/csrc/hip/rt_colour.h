@@ -11,9 +11,9 @@
 //                             order of anything.  Two histograms in the context, as the exposure meter has them: a call adds into
 //                             the zero one and its workgroup 0 zeroes the other for the call after, so a meter call is one launch.
 //  rt_colour_lut_kernel       one thread a node: rsrt_colour_lut_node, stored as a float4 (alpha 1).
-//  rt_display_colour_kernel   rt_display_local_kernel's tile with rsrt_display_pixel_colour; the grid is read only with a local grade,
-//                             the bloom image only with intensity > 0, the LUT — four 16-byte nodes a pixel, through L2 — only with
-//                             lut_strength > 0.  No scratch memory, no LDS.
+//  rt_display_colour_kernel   rt_display_local_kernel's tile and DisplayChain (rt_local.h) with rsrt_display_pixel_colour; the grid is
+//                             read only with a local grade, the bloom image only with intensity > 0 (rt_display_gather), the LUT — four
+//                             16-byte nodes a pixel, through L2 — only with lut_strength > 0.  No scratch memory, no LDS.
 #include "../../../include/rsrt_colour.h"
 
 #define RT_WB_BLOCK 256u
@@ -73,27 +73,23 @@ __global__ __launch_bounds__(256) void rt_colour_lut_kernel(float4 *lut, uint32_
     lut[i] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
 }
 
-// img: w x h sums; grid: the blurred grid of it, looked at only with graded; b: bw x bh, looked at only with intensity > 0; lut: n^3
-// nodes, looked at only with colour.lut_strength > 0
-__global__ __launch_bounds__(RT_LC_BLOCK) void rt_display_colour_kernel(const float4 *img, int w, int h, float total, float exposure, bool graded, rsrt_local_params p,
-                                                                        const uint32_t *grid, uint32_t gx, uint32_t gy, uint32_t cell, float intensity,
-                                                                        const rsrt_bloom_texel *b, int bw, int bh, rsrt_colour_params colour, const float4 *lut,
-                                                                        uint32_t n, uchar4 *out)
+// rt_display_local_kernel's tile with the white point and the LUT
+__global__ __launch_bounds__(RT_LC_BLOCK) void rt_display_colour_kernel(DisplayChain c, uchar4 *out)
 {
     const int bx = (int)blockIdx.x * RT_LC_TW, by = (int)blockIdx.y * RT_LC_TH;
     const int x = bx + (int)threadIdx.x % RT_LC_TW, y = by + (int)threadIdx.x / RT_LC_TW;
-    if (x >= w || y >= h) return;
-    const size_t i = (size_t)y * (size_t)w + (size_t)x;
-    const float4 a = img[i];
-    const float sum[3] = {a.x, a.y, a.z};
-    const float gain = graded ? rsrt_local_gain_at(grid, gx, gy, cell, x, y, rsrt_local_q_of(sum, total), rsrt_local_mid(p.key, exposure), &p) : 1.0f;
+    if (x >= c.w || y >= c.h) return;
+    float sum[3], gain;
+    rsrt_bloom_rgb up_b;
+    rt_display_gather(c, c.graded, x, y, sum, &gain, &up_b);
     unsigned char rgb[3];
-    rsrt_display_pixel_colour(sum, total, exposure, intensity, intensity > 0.0f ? rsrt_bloom_up_at(b, bw, bh, x, y) : rsrt_bloom_make(0.0f, 0.0f, 0.0f), gain, &colour,
-                              reinterpret_cast<const float *>(lut), n, rgb);
-    out[i] = make_uchar4(rgb[0], rgb[1], rgb[2], 255);
+    rsrt_display_pixel_colour(sum, c.total, c.exposure, c.intensity, up_b, gain, &c.colour, reinterpret_cast<const float *>(c.lut), c.n, rgb);
+    out[(size_t)y * (size_t)c.w + (size_t)x] = make_uchar4(rgb[0], rgb[1], rgb[2], 255);
 }
 
 namespace {
+
+const MeterShape kWhiteMeter = {RSRT_WHITE_WORDS, RT_WB_STRIDE, RT_WB_BLOCK, RT_WB_AHEAD, rt_white_hist_kernel};
 
 size_t lut_nodes(uint32_t n) { return (size_t)n * n * n; }
 
@@ -120,29 +116,8 @@ rsrt_status rsrt_white_meter(rsrt_context *ctx, uint32_t source, uint32_t sample
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     ImageView v;
-    rsrt_status st = exposure_source(ctx, "white_meter", source, sample_total, &v);
-    if (st) return st;
-    const hipStream_t stream = stream_of(ctx, hip_stream);
-    const size_t n = v.pixels();
-    if (!ctx->wb_hist || ctx->wb_dirty) { // both histograms zero: once, and after a launch that failed
-        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-        if (!ctx->wb_hist) HIP_TRY(ctx, hipMalloc(&ctx->wb_hist, 2u * RT_WB_STRIDE * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemset(ctx->wb_hist, 0, 2u * RT_WB_STRIDE * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipDeviceSynchronize()); // (the memset is enqueued on the null stream, which the kernel's stream does not wait for)
-        ctx->wb_cur = 0;
-        ctx->wb_dirty = ctx->wb_have = false;
-    }
-    if ((st = begin_work(ctx, stream))) return st;
-    const size_t trip = (size_t)RT_WB_BLOCK * RT_WB_AHEAD, want = (n + trip - 1u) / trip;
-    uint32_t *const now = ctx->wb_hist + (ctx->wb_cur ^ 1u) * RT_WB_STRIDE, *const old = ctx->wb_hist + ctx->wb_cur * RT_WB_STRIDE;
-    ctx->wb_have = false; // (a failed launch leaves no histogram, and neither buffer known to be zero)
-    ctx->wb_dirty = true;
-    rt_white_hist_kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(RT_WB_BLOCK), 0, stream>>>(v.img, n, v.total, now, old);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->wb_cur ^= 1u;
-    ctx->wb_dirty = false;
-    ctx->wb_have = true;
-    return end_work(ctx, stream);
+    const rsrt_status st = exposure_source(ctx, "white_meter", source, sample_total, &v);
+    return st ? st : meter_launch(ctx, ctx->wb, kWhiteMeter, v, stream_of(ctx, hip_stream));
 }
 
 rsrt_status rsrt_white_download(rsrt_context *ctx, const rsrt_white_params *params, uint32_t *host_hist, size_t n_words, rsrt_white_result *out)
@@ -155,24 +130,16 @@ rsrt_status rsrt_white_download(rsrt_context *ctx, const rsrt_white_params *para
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "white_download: want gate in 1 .. 31, iterations <= 8, min_permille <= 1000, strength and blend in [0, 1], "
                                                      "max_stops in [0, 4], previous all 0 or finite and > 0, flags 0");
     if (host_hist && n_words != RSRT_WHITE_WORDS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "white_download: expected %u words", RSRT_WHITE_WORDS);
-    if (!ctx->wb_have) return fail(ctx, RSRT_ERR_NOT_READY, "no chroma histogram (rsrt_white_meter first)");
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    std::vector<uint32_t> own;
-    if (!host_hist) {
-        own.resize(RSRT_WHITE_WORDS);
-        host_hist = own.data();
-    }
-    HIP_TRY(ctx, hipMemcpy(host_hist, ctx->wb_hist + ctx->wb_cur * RT_WB_STRIDE, RSRT_WHITE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out) rsrt_white_from_histogram(host_hist, params, out);
-    return RSRT_OK;
+    if (!ctx->wb.have) return fail(ctx, RSRT_ERR_NOT_READY, "no chroma histogram (rsrt_white_meter first)");
+    return meter_download(ctx, ctx->wb, kWhiteMeter, host_hist, [&](const uint32_t *hist) {
+        if (out) rsrt_white_from_histogram(hist, params, out);
+    });
 }
 
 rsrt_status rsrt_white_reset(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    { rsrt_status st0 = whole_frame(ctx, "white_reset"); if (st0) return st0; }
-    ctx->wb_have = false;
-    return RSRT_OK;
+    return meter_reset(ctx, ctx->wb, "white_reset");
 }
 
 rsrt_status rsrt_colour_lut_build(rsrt_context *ctx, uint32_t n, const rsrt_cdl_params *cdl, void *hip_stream)
@@ -252,36 +219,12 @@ rsrt_status rsrt_display_colour_srgb8(rsrt_context *ctx, uint32_t source, uint32
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    const char *const what = "display_colour_srgb8";
-    ImageView v;
-    rsrt_status st = bloom_source(ctx, what, source, sample_total, exposure, &v);
+    DisplayChain c;
+    const rsrt_status st = display_chain(ctx, "display_colour_srgb8", CHAIN_COLOUR, source, sample_total, exposure, local, colour, nullptr, bloom_intensity, host_rgba8,
+                                         n_bytes, &c);
     if (st) return st;
-    const size_t n = v.pixels();
-    if (local && !rsrt_local_params_ok(local))
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want shadows and highlights in [0, 1], key finite and > 0, max_stops in [0, 16], flags 0", what);
-    if (!colour) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: colour is NULL", what);
-    if (!rsrt_colour_params_ok(colour)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want white finite and > 0, lut_strength in [0, 1], flags 0", what);
-    if (!rsrt_bloom_finite_nonneg(bloom_intensity)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: bloom_intensity must be finite and >= 0", what);
-    if (!host_rgba8 || n_bytes != n * 4) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu bytes", what, n * 4);
-    if (local) {
-        if (!ctx->lc_have) return fail(ctx, RSRT_ERR_NOT_READY, "no local exposure grid (rsrt_local_exposure first)");
-        if (!ctx->lc_grid.is(v.w, v.h))
-            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the grid was built for %ux%u, the source is %ux%u", what, ctx->lc_grid.w, ctx->lc_grid.h, v.w, v.h);
-    }
-    if (bloom_intensity > 0.0f) {
-        if (!ctx->bl_have) return fail(ctx, RSRT_ERR_NOT_READY, "no bloom image (rsrt_bloom first)");
-        if (!ctx->bl_pyr.is(v.w, v.h))
-            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the bloom image was built for %ux%u, the source is %ux%u", what, ctx->bl_pyr.w, ctx->bl_pyr.h, v.w, v.h);
-    }
-    if (colour->lut_strength > 0.0f && !ctx->cl_n) return fail(ctx, RSRT_ERR_NOT_READY, "no colour LUT (rsrt_colour_lut_build or rsrt_colour_lut_upload first)");
-    const uint32_t cell = local ? ctx->lc_cell : RSRT_LOCAL_CELL, gx = rsrt_local_cells(v.w, cell), gy = rsrt_local_cells(v.h, cell);
-    const rsrt_local_params lp = local ? *local : rsrt_local_params{0.0f, 0.0f, RSRT_LOCAL_KEY, 0.0f, 0u, 0u};
-    const dim3 tiles((v.w + RT_LC_TW - 1u) / RT_LC_TW, (v.h + RT_LC_TH - 1u) / RT_LC_TH);
-    return read_back(ctx, host_rgba8, n * 4u, 0, [&](void *tmp) {
-        rt_display_colour_kernel<<<tiles, dim3(RT_LC_BLOCK), 0, ctx->stream>>>(v.img, (int)v.w, (int)v.h, v.total, exposure, local != nullptr, lp,
-                                                                              local ? local_blurred(ctx) : nullptr, gx, gy, cell, bloom_intensity,
-                                                                              static_cast<const rsrt_bloom_texel *>(ctx->bl_pyr.p), (int)rsrt_bloom_level_size(v.w, 1),
-                                                                              (int)rsrt_bloom_level_size(v.h, 1), *colour, ctx->cl_lut, ctx->cl_n, static_cast<uchar4 *>(tmp));
+    return read_back(ctx, host_rgba8, n_bytes, 0, [&](void *tmp) {
+        rt_display_colour_kernel<<<display_tiles(c), dim3(RT_LC_BLOCK), 0, ctx->stream>>>(c, static_cast<uchar4 *>(tmp));
         return RSRT_OK;
     });
 }

@@ -14,6 +14,8 @@
 //                              workgroup 0 zeroes the other — the result of the call before, which the new call supersedes — for
 //                              the call after.  So a meter call is one launch, with no memset in front of it.
 //  rt_display_exposed_kernel   rt_display_kernel with rsrt_display_pixel_exposed.
+// The host side of such a meter (a HistMeter in the context) is meter_launch, meter_download and meter_reset over a MeterShape; the
+// white-balance meter (rt_colour.h) is the second one.
 #include "../../../include/rsrt_exposure.h"
 
 #define RT_EX_BLOCK 256u
@@ -89,6 +91,62 @@ rsrt_status exposure_source(rsrt_context *ctx, const char *what, uint32_t source
     return resolve_image(ctx, what, "", source, sample_total, false, v);
 }
 
+// what differs between two ping-pong histogram meters: the kernel adds an image's `words` words into `hist`, which is zero, and zeroes
+// `next`, workgroups of `block` threads walking trips of block * ahead pixels; the two histograms lie `stride` words apart
+struct MeterShape {
+    uint32_t words, stride, block, ahead;
+    void (*kernel)(const float4 *img, size_t n, float total, uint32_t *hist, uint32_t *next);
+};
+const MeterShape kExposureMeter = {RSRT_EXPOSURE_WORDS, RT_EX_STRIDE, RT_EX_BLOCK, RT_EX_AHEAD, rt_exposure_hist_kernel};
+
+// the histogram of v into the one of m's two that is zero: one launch, at most one workgroup a CU
+rsrt_status meter_launch(rsrt_context *ctx, HistMeter &m, const MeterShape &s, const ImageView &v, hipStream_t stream)
+{
+    rsrt_status st;
+    const size_t n = v.pixels();
+    if (!m.hist || m.dirty) { // both histograms zero: once, and after a launch that failed
+        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+        if (!m.hist) HIP_TRY(ctx, hipMalloc(&m.hist, 2u * s.stride * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMemset(m.hist, 0, 2u * s.stride * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipDeviceSynchronize()); // (the memset is enqueued on the null stream, which the kernel's stream does not wait for)
+        m.cur = 0;
+        m.dirty = m.have = false;
+    }
+    if ((st = begin_work(ctx, stream))) return st;
+    const size_t trip = (size_t)s.block * s.ahead, want = (n + trip - 1u) / trip;
+    uint32_t *const now = m.hist + (m.cur ^ 1u) * s.stride, *const old = m.hist + m.cur * s.stride;
+    m.have = false; // (a failed launch leaves no histogram, and neither buffer known to be zero)
+    m.dirty = true;
+    s.kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(s.block), 0, stream>>>(v.img, n, v.total, now, old);
+    HIP_TRY(ctx, hipGetLastError());
+    m.cur ^= 1u;
+    m.dirty = false;
+    m.have = true;
+    return end_work(ctx, stream);
+}
+
+// m's last histogram (there is one) into host_hist, or into a buffer of its own where that is NULL; then result(the words)
+template <class Result>
+rsrt_status meter_download(rsrt_context *ctx, const HistMeter &m, const MeterShape &s, uint32_t *host_hist, Result result)
+{
+    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
+    std::vector<uint32_t> own;
+    if (!host_hist) {
+        own.resize(s.words);
+        host_hist = own.data();
+    }
+    HIP_TRY(ctx, hipMemcpy(host_hist, m.hist + m.cur * s.stride, s.words * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    result(host_hist);
+    return RSRT_OK;
+}
+
+rsrt_status meter_reset(rsrt_context *ctx, HistMeter &m, const char *what)
+{
+    { rsrt_status st0 = whole_frame(ctx, what); if (st0) return st0; }
+    m.have = false;
+    return RSRT_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -98,29 +156,8 @@ rsrt_status rsrt_exposure_meter(rsrt_context *ctx, uint32_t source, uint32_t sam
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     ImageView v;
-    rsrt_status st = exposure_source(ctx, "exposure_meter", source, sample_total, &v);
-    if (st) return st;
-    const hipStream_t stream = stream_of(ctx, hip_stream);
-    const size_t n = v.pixels();
-    if (!ctx->ex_hist || ctx->ex_dirty) { // both histograms zero: once, and after a launch that failed
-        { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-        if (!ctx->ex_hist) HIP_TRY(ctx, hipMalloc(&ctx->ex_hist, 2u * RT_EX_STRIDE * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipMemset(ctx->ex_hist, 0, 2u * RT_EX_STRIDE * sizeof(uint32_t)));
-        HIP_TRY(ctx, hipDeviceSynchronize()); // (the memset is enqueued on the null stream, which the kernel's stream does not wait for)
-        ctx->ex_cur = 0;
-        ctx->ex_dirty = ctx->ex_have = false;
-    }
-    if ((st = begin_work(ctx, stream))) return st;
-    const size_t trip = (size_t)RT_EX_BLOCK * RT_EX_AHEAD, want = (n + trip - 1u) / trip;
-    uint32_t *const now = ctx->ex_hist + (ctx->ex_cur ^ 1u) * RT_EX_STRIDE, *const old = ctx->ex_hist + ctx->ex_cur * RT_EX_STRIDE;
-    ctx->ex_have = false; // (a failed launch leaves no histogram, and neither buffer known to be zero)
-    ctx->ex_dirty = true;
-    rt_exposure_hist_kernel<<<dim3((unsigned)(want < (size_t)ctx->cus ? want : (size_t)ctx->cus)), dim3(RT_EX_BLOCK), 0, stream>>>(v.img, n, v.total, now, old);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->ex_cur ^= 1u;
-    ctx->ex_dirty = false;
-    ctx->ex_have = true;
-    return end_work(ctx, stream);
+    const rsrt_status st = exposure_source(ctx, "exposure_meter", source, sample_total, &v);
+    return st ? st : meter_launch(ctx, ctx->ex, kExposureMeter, v, stream_of(ctx, hip_stream));
 }
 
 rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params *params, uint32_t *host_hist, size_t n_words, rsrt_exposure_result *out)
@@ -134,21 +171,16 @@ rsrt_status rsrt_exposure_download(rsrt_context *ctx, const rsrt_exposure_params
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: want low_permille < high_permille <= 1000, key and 0 < min_exposure <= max_exposure finite and > 0, "
                                                      "blend in [0, 1], previous_exposure 0 or finite and > 0");
     if (host_hist && n_words != RSRT_EXPOSURE_WORDS) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "exposure_download: expected %u words", RSRT_EXPOSURE_WORDS);
-    if (!ctx->ex_have) return fail(ctx, RSRT_ERR_NOT_READY, "no exposure histogram (rsrt_exposure_meter first)");
-    { rsrt_status st0 = sync_all(ctx); if (st0) return st0; }
-    uint32_t own[RSRT_EXPOSURE_WORDS];
-    if (!host_hist) host_hist = own;
-    HIP_TRY(ctx, hipMemcpy(host_hist, ctx->ex_hist + ctx->ex_cur * RT_EX_STRIDE, RSRT_EXPOSURE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (out) rsrt_exposure_from_histogram(host_hist, params, out);
-    return RSRT_OK;
+    if (!ctx->ex.have) return fail(ctx, RSRT_ERR_NOT_READY, "no exposure histogram (rsrt_exposure_meter first)");
+    return meter_download(ctx, ctx->ex, kExposureMeter, host_hist, [&](const uint32_t *hist) {
+        if (out) rsrt_exposure_from_histogram(hist, params, out);
+    });
 }
 
 rsrt_status rsrt_exposure_reset(rsrt_context *ctx)
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
-    { rsrt_status st0 = whole_frame(ctx, "exposure_reset"); if (st0) return st0; }
-    ctx->ex_have = false;
-    return RSRT_OK;
+    return meter_reset(ctx, ctx->ex, "exposure_reset");
 }
 
 rsrt_status rsrt_display_exposed_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, uint8_t *host_rgba8, size_t n_bytes)

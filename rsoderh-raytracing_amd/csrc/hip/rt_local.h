@@ -15,7 +15,9 @@
 //  rt_display_local_kernel   rt_display_exposed_kernel with the slice inside and, with intensity > 0, rt_display_bloomed_kernel's four
 //  rt_local_gain_kernel      taps; the second writes the f32 gain instead of bytes.  A workgroup takes RT_LC_TW x RT_LC_TH pixels; the
 //                            eight corners come through L2 (staging the tile's columns in LDS was no faster: DESIGN.md §17).
-#include "../../../include/rsrt_local.h"
+// The tiled displays — these two, rt_display_colour_kernel and rt_display_finish_kernel — share DisplayChain, the struct they take by value,
+// rt_display_gather, which reads a pixel's inputs from it, and display_chain, which makes their entry points' checks and fills it.
+#include "../../../include/rsrt_finish.h" // (the whole display chain: display_chain below checks every stage's parameters)
 
 #define RT_LC_PW 64
 #define RT_LC_PH 64
@@ -91,39 +93,56 @@ __global__ __launch_bounds__(RT_LC_BLOCK) void rt_local_blur_kernel(const uint2 
     dst[i] = s;
 }
 
-// img: w x h sums; grid: the blurred grid of it; b: bw x bh, looked at only with intensity > 0; out: uchar4 a pixel, or (GAIN) a float
+// what the tiled display kernels read; a piece that is not asked for is not looked at, and its fields are zero
+struct DisplayChain {
+    const float4 *img; // w x h sums of `total` samples
+    int w, h;
+    float total, exposure;
+    bool graded; // the local gain: the blurred grid of img, gx x gy x 32 cells of `cell` pixels
+    rsrt_local_params local;
+    const uint32_t *grid;
+    uint32_t gx, gy, cell;
+    float intensity; // > 0: the bloom image, bw x bh
+    const rsrt_bloom_texel *bloom;
+    int bw, bh;
+    rsrt_colour_params colour; // lut_strength > 0: the LUT of n^3 nodes
+    const float4 *lut;
+    uint32_t n;
+};
+
+// a pixel's inputs to the chain: the sums of (x, y), 0 <= x < w, 0 <= y < h, its gain (1 without a grade) and up(B) at it (0 without bloom).
+// graded: c.graded, or true where the grade is not optional: known at compile time, the luminance's divisions are the mean's, made once
+__device__ __forceinline__ void rt_display_gather(const DisplayChain &c, bool graded, int x, int y, float sum[3], float *gain, rsrt_bloom_rgb *up_b)
+{
+    const float4 a = c.img[(size_t)y * (size_t)c.w + (size_t)x];
+    sum[0] = a.x; sum[1] = a.y; sum[2] = a.z;
+    *gain = graded ? rsrt_local_gain_at(c.grid, c.gx, c.gy, c.cell, x, y, rsrt_local_q_of(sum, c.total), rsrt_local_mid(c.local.key, c.exposure), &c.local) : 1.0f;
+    *up_b = c.intensity > 0.0f ? rsrt_bloom_up_at(c.bloom, c.bw, c.bh, x, y) : rsrt_bloom_make(0.0f, 0.0f, 0.0f);
+}
+
+// out: uchar4 a pixel, or (GAIN) a float
 template <bool GAIN>
-__device__ __forceinline__ void rt_local_display_tile(const float4 *img, int w, int h, float total, float exposure, rsrt_local_params p, const uint32_t *grid,
-                                                      uint32_t gx, uint32_t gy, uint32_t cell, float intensity, const rsrt_bloom_texel *b, int bw, int bh, void *out)
+__device__ __forceinline__ void rt_local_display_tile(const DisplayChain &c, void *out)
 {
     const int bx = (int)blockIdx.x * RT_LC_TW, by = (int)blockIdx.y * RT_LC_TH;
     const int x = bx + (int)threadIdx.x % RT_LC_TW, y = by + (int)threadIdx.x / RT_LC_TW;
-    if (x >= w || y >= h) return;
-    const size_t i = (size_t)y * (size_t)w + (size_t)x;
-    const float4 a = img[i];
-    const float sum[3] = {a.x, a.y, a.z};
-    const float gain = rsrt_local_gain_at(grid, gx, gy, cell, x, y, rsrt_local_q_of(sum, total), rsrt_local_mid(p.key, exposure), &p);
+    if (x >= c.w || y >= c.h) return;
+    const size_t i = (size_t)y * (size_t)c.w + (size_t)x;
+    float sum[3], gain;
+    rsrt_bloom_rgb up_b;
+    rt_display_gather(c, true, x, y, sum, &gain, &up_b);
     if (GAIN) {
         static_cast<float *>(out)[i] = gain;
         return;
     }
     unsigned char rgb[3];
-    rsrt_display_pixel_local(sum, total, exposure, intensity, intensity > 0.0f ? rsrt_bloom_up_at(b, bw, bh, x, y) : rsrt_bloom_make(0.0f, 0.0f, 0.0f), gain, rgb);
+    rsrt_display_pixel_local(sum, c.total, c.exposure, c.intensity, up_b, gain, rgb);
     static_cast<uchar4 *>(out)[i] = make_uchar4(rgb[0], rgb[1], rgb[2], 255);
 }
 
-__global__ __launch_bounds__(RT_LC_BLOCK) void rt_display_local_kernel(const float4 *img, int w, int h, float total, float exposure, rsrt_local_params p,
-                                                                       const uint32_t *grid, uint32_t gx, uint32_t gy, uint32_t cell, float intensity,
-                                                                       const rsrt_bloom_texel *b, int bw, int bh, uchar4 *out)
-{
-    rt_local_display_tile<false>(img, w, h, total, exposure, p, grid, gx, gy, cell, intensity, b, bw, bh, out);
-}
+__global__ __launch_bounds__(RT_LC_BLOCK) void rt_display_local_kernel(DisplayChain c, uchar4 *out) { rt_local_display_tile<false>(c, out); }
 
-__global__ __launch_bounds__(RT_LC_BLOCK) void rt_local_gain_kernel(const float4 *img, int w, int h, float total, float exposure, rsrt_local_params p,
-                                                                    const uint32_t *grid, uint32_t gx, uint32_t gy, uint32_t cell, float *out)
-{
-    rt_local_display_tile<true>(img, w, h, total, exposure, p, grid, gx, gy, cell, 0.0f, nullptr, 0, 0, out);
-}
+__global__ __launch_bounds__(RT_LC_BLOCK) void rt_local_gain_kernel(DisplayChain c, float *out) { rt_local_display_tile<true>(c, out); }
 
 namespace {
 
@@ -133,42 +152,57 @@ size_t local_words(const rsrt_context *ctx) { return 2u * (size_t)rsrt_local_cel
 // the blurred grid: the second half
 uint32_t *local_blurred(const rsrt_context *ctx) { return static_cast<uint32_t *>(ctx->lc_grid.p) + local_words_max(ctx->lc_grid.w, ctx->lc_grid.h); }
 
-// rsrt_display_local_srgb8 (host_gain NULL) and rsrt_local_gain_download (host_rgba8 NULL)
-rsrt_status local_display(rsrt_context *ctx, const char *what, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *params,
-                          float intensity, uint8_t *host_rgba8, float *host_gain, size_t n_out)
+// display_chain's `demands`: the params an entry point refuses as NULL (others are off when NULL); CHAIN_FLOATS: it writes a float a pixel, not bytes
+enum : uint32_t { CHAIN_LOCAL = 1u, CHAIN_COLOUR = 2u, CHAIN_FINISH = 4u, CHAIN_FLOATS = 8u };
+
+// Every check of the tiled displays, in the order the faults are reported in: the source, the local, colour and finish params, the bloom
+// intensity, the output's size, then what the context has to hold where it is asked for: the grid, the bloom image, the LUT.  Fills c.
+rsrt_status display_chain(rsrt_context *ctx, const char *what, uint32_t demands, uint32_t source, uint32_t sample_total, float exposure,
+                          const rsrt_local_params *local, const rsrt_colour_params *colour, const rsrt_finish_params *finish, float intensity, const void *host,
+                          size_t n_out, DisplayChain *c)
 {
     ImageView v;
     rsrt_status st = bloom_source(ctx, what, source, sample_total, exposure, &v);
     if (st) return st;
-    const size_t n = v.pixels();
-    if (!params) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: params is NULL", what);
-    if (!rsrt_local_params_ok(params))
+    if ((demands & CHAIN_LOCAL) && !local) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: params is NULL", what);
+    if (local && !rsrt_local_params_ok(local))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want shadows and highlights in [0, 1], key finite and > 0, max_stops in [0, 16], flags 0", what);
+    if ((demands & CHAIN_COLOUR) && !colour) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: colour is NULL", what);
+    if (colour && !rsrt_colour_params_ok(colour)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want white finite and > 0, lut_strength in [0, 1], flags 0", what);
+    if ((demands & CHAIN_FINISH) && !finish) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: finish is NULL", what);
+    if (finish && !rsrt_finish_params_ok(finish))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want sharpness, grain and dither in [0, 1], flags RSRT_FINISH_NOISE_AWARE or 0", what);
     if (!rsrt_bloom_finite_nonneg(intensity)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: bloom_intensity must be finite and >= 0", what);
-    if (host_gain ? n_out != n : (!host_rgba8 || n_out != n * 4))
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu %s", what, host_gain ? n : n * 4, host_gain ? "floats" : "bytes");
-    if (!ctx->lc_have) return fail(ctx, RSRT_ERR_NOT_READY, "no local exposure grid (rsrt_local_exposure first)");
-    if (!ctx->lc_grid.is(v.w, v.h))
-        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the grid was built for %ux%u, the source is %ux%u", what, ctx->lc_grid.w, ctx->lc_grid.h, v.w, v.h);
-    if (intensity > 0.0f) {
-        if (!ctx->bl_have) return fail(ctx, RSRT_ERR_NOT_READY, "no bloom image (rsrt_bloom first)");
-        if (!ctx->bl_pyr.is(v.w, v.h))
-            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: the bloom image was built for %ux%u, the source is %ux%u", what, ctx->bl_pyr.w, ctx->bl_pyr.h, v.w, v.h);
+    const bool floats = demands & CHAIN_FLOATS;
+    const size_t want = floats ? v.pixels() : v.pixels() * 4;
+    if (!host || n_out != want) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu %s", what, want, floats ? "floats" : "bytes");
+    *c = DisplayChain{}; // (what is not asked for stays zero)
+    c->img = v.img; c->w = (int)v.w; c->h = (int)v.h; c->total = v.total; c->exposure = exposure;
+    if (local) {
+        if (!ctx->lc_have) return fail(ctx, RSRT_ERR_NOT_READY, "no local exposure grid (rsrt_local_exposure first)");
+        if ((st = built_for(ctx, what, "grid", ctx->lc_grid, v))) return st;
+        c->graded = true;
+        c->local = *local;
+        c->grid = local_blurred(ctx);
+        c->cell = ctx->lc_cell;
+        c->gx = rsrt_local_cells(v.w, c->cell); c->gy = rsrt_local_cells(v.h, c->cell);
     }
-    const uint32_t cell = ctx->lc_cell, gx = rsrt_local_cells(v.w, cell), gy = rsrt_local_cells(v.h, cell);
-    const dim3 tiles((v.w + RT_LC_TW - 1u) / RT_LC_TW, (v.h + RT_LC_TH - 1u) / RT_LC_TH);
-    return read_back(ctx, host_gain ? static_cast<void *>(host_gain) : host_rgba8, n * 4u, 0, [&](void *tmp) {
-        if (host_gain)
-            rt_local_gain_kernel<<<tiles, dim3(RT_LC_BLOCK), 0, ctx->stream>>>(v.img, (int)v.w, (int)v.h, v.total, exposure, *params, local_blurred(ctx), gx, gy, cell,
-                                                                              static_cast<float *>(tmp));
-        else
-            rt_display_local_kernel<<<tiles, dim3(RT_LC_BLOCK), 0, ctx->stream>>>(v.img, (int)v.w, (int)v.h, v.total, exposure, *params, local_blurred(ctx), gx, gy, cell,
-                                                                                 intensity, static_cast<const rsrt_bloom_texel *>(ctx->bl_pyr.p),
-                                                                                 (int)rsrt_bloom_level_size(v.w, 1), (int)rsrt_bloom_level_size(v.h, 1),
-                                                                                 static_cast<uchar4 *>(tmp));
-        return RSRT_OK;
-    });
+    c->intensity = intensity;
+    if (intensity > 0.0f) {
+        if ((st = bloom_ready(ctx, what, v))) return st;
+        c->bloom = static_cast<const rsrt_bloom_texel *>(ctx->bl_pyr.p);
+        c->bw = (int)rsrt_bloom_level_size(v.w, 1); c->bh = (int)rsrt_bloom_level_size(v.h, 1);
+    }
+    c->colour = colour ? *colour : rsrt_colour_params{{1.0f, 1.0f, 1.0f}, 0.0f, 0u, {0u, 0u, 0u}};
+    if (c->colour.lut_strength > 0.0f) {
+        if (!ctx->cl_n) return fail(ctx, RSRT_ERR_NOT_READY, "no colour LUT (rsrt_colour_lut_build or rsrt_colour_lut_upload first)");
+        c->lut = ctx->cl_lut;
+        c->n = ctx->cl_n;
+    }
+    return RSRT_OK;
 }
+
+dim3 display_tiles(const DisplayChain &c) { return dim3(((uint32_t)c.w + RT_LC_TW - 1u) / RT_LC_TW, ((uint32_t)c.h + RT_LC_TH - 1u) / RT_LC_TH); }
 
 } // namespace
 
@@ -236,7 +270,14 @@ rsrt_status rsrt_local_gain_download(rsrt_context *ctx, uint32_t source, uint32_
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     if (!host_gain) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "local_gain_download: host_gain is NULL");
-    return local_display(ctx, "local_gain_download", source, sample_total, exposure, params, 0.0f, nullptr, host_gain, n_floats);
+    DisplayChain c;
+    const rsrt_status st = display_chain(ctx, "local_gain_download", CHAIN_LOCAL | CHAIN_FLOATS, source, sample_total, exposure, params, nullptr, nullptr, 0.0f, host_gain,
+                                         n_floats, &c);
+    if (st) return st;
+    return read_back(ctx, host_gain, n_floats * sizeof(float), 0, [&](void *tmp) {
+        rt_local_gain_kernel<<<display_tiles(c), dim3(RT_LC_BLOCK), 0, ctx->stream>>>(c, static_cast<float *>(tmp));
+        return RSRT_OK;
+    });
 }
 
 rsrt_status rsrt_display_local_srgb8(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *params,
@@ -244,7 +285,14 @@ rsrt_status rsrt_display_local_srgb8(rsrt_context *ctx, uint32_t source, uint32_
 {
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
-    return local_display(ctx, "display_local_srgb8", source, sample_total, exposure, params, bloom_intensity, host_rgba8, nullptr, n_bytes);
+    DisplayChain c;
+    const rsrt_status st = display_chain(ctx, "display_local_srgb8", CHAIN_LOCAL, source, sample_total, exposure, params, nullptr, nullptr, bloom_intensity, host_rgba8,
+                                         n_bytes, &c);
+    if (st) return st;
+    return read_back(ctx, host_rgba8, n_bytes, 0, [&](void *tmp) {
+        rt_display_local_kernel<<<display_tiles(c), dim3(RT_LC_BLOCK), 0, ctx->stream>>>(c, static_cast<uchar4 *>(tmp));
+        return RSRT_OK;
+    });
 }
 
 } // extern "C"

@@ -491,6 +491,28 @@ class State:
         if rc != 0:
             raise RsrtError("%s failed (%d): %s" % (what, rc, self._L.rsrt_last_error(self._ctx).decode()), rc)
 
+    def _total(self, sample_total):
+        """The samples in the accumulator a pass is told of: sample_count unless given."""
+        return self.sample_count if sample_total is None else sample_total
+
+    def _source_total(self, source, sample_total):
+        """(source id, sample total) as the image passes' entry points take them: `source` a name of ALL_SOURCES or an id."""
+        return ALL_SOURCES.get(source, source), self._total(sample_total)
+
+    def _displayed(self, name, source, sample_total, *args):
+        """The display `name`(ctx, source, sample_total, *args, bytes, their number) into [H, W, 4] uint8 of the source's own shape."""
+        out = np.empty(self._source_shape(source) + (4,), np.uint8)
+        self._check(getattr(self._L, name)(self._ctx, *self._source_total(source, sample_total), *args, _p(out), out.size), name)
+        return out
+
+    def _colour_params(self, white, lut_strength):
+        """rsrt_colour_params: `white` (None: the remembered white point, else (1, 1, 1)), lut_strength (None: 1 with a LUT, 0 without)."""
+        if white is None:
+            white = (1.0, 1.0, 1.0) if self.white is None else self.white
+        if lut_strength is None:
+            lut_strength = 1.0 if self._has_colour_lut() else 0.0
+        return ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
+
     def close(self):
         if self._ctx:
             self._L.rsrt_context_destroy(self._ctx)
@@ -673,7 +695,7 @@ class State:
             sigma_color = VARIANCE_SIGMA_L
         p = DenoiseParams(pick(iterations, "iterations"), flags, pick(sigma_color, "sigma_color"), pick(sigma_normal, "sigma_normal"),
                           pick(sigma_depth, "sigma_depth"))
-        n = self.sample_count if sample_total is None else sample_total
+        n = self._total(sample_total)
         na = self.aov_sample_count if aov_sample_total is None else aov_sample_total
         self._check(self._L.rsrt_denoise(self._ctx, n, na, C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
                                          C.c_void_p(stream) if stream else None), "rsrt_denoise")
@@ -731,7 +753,7 @@ class State:
             raise ValueError("upsample: source is 'mean', 'denoised' or 'temporal', not %r" % (source,))
         p = UpsampleParams((UPSAMPLE_DEMODULATE if pick(demodulate, "demodulate") else 0) | src[source], pick(sigma_normal, "sigma_normal"),
                            pick(sigma_depth, "sigma_depth"))
-        n = self.sample_count if sample_total is None else sample_total
+        n = self._total(sample_total)
         na = self.aov_sample_count if aov_sample_total is None else aov_sample_total
         ng = self.guide_sample_count if guide_sample_total is None else guide_sample_total
         self._check(self._L.rsrt_upsample(self._ctx, n, na, ng, C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
@@ -764,16 +786,14 @@ class State:
     # -- noise estimate (include/rsrt.h "noise estimate") --------------------------------------------
     def noise_snapshot(self, sample_total=None, stream=None):
         """rsrt_noise_snapshot: keeps a copy of the accumulator, the sum of sample_total (default: sample_count) samples."""
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_noise_snapshot(self._ctx, n, C.c_void_p(stream) if stream else None), "rsrt_noise_snapshot")
+        self._check(self._L.rsrt_noise_snapshot(self._ctx, self._total(sample_total), C.c_void_p(stream) if stream else None), "rsrt_noise_snapshot")
 
     def noise_estimate(self, tile=(16, 16), threshold=0.0, sample_total=None, stream=None, download=True):
         """rsrt_noise_estimate of the accumulator (sample_total samples, default sample_count) against the last noise_snapshot():
         (tile map [tiles_y, tiles_x] float32, summary dict with max_error, mean_error, tiles_x, tiles_y, tiles_above), or None with
         download=False (noise_download() fetches it later)."""
         p = NoiseParams(tile[0], tile[1], threshold, 0)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_noise_estimate(self._ctx, n, C.byref(p), C.c_void_p(stream) if stream else None), "rsrt_noise_estimate")
+        self._check(self._L.rsrt_noise_estimate(self._ctx, self._total(sample_total), C.byref(p), C.c_void_p(stream) if stream else None), "rsrt_noise_estimate")
         return self.noise_download() if download else None
 
     def noise_download(self):
@@ -822,8 +842,7 @@ class State:
     def exposure_meter(self, source="mean", sample_total=None, stream=None):
         """rsrt_exposure_meter: builds the luminance histogram of `source` ("mean": the accumulator over sample_total, default
         sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device.  Asynchronous."""
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_exposure_meter(self._ctx, ALL_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None),
+        self._check(self._L.rsrt_exposure_meter(self._ctx, *self._source_total(source, sample_total), C.c_void_p(stream) if stream else None),
                     "rsrt_exposure_meter")
 
     def exposure_download(self, **params):
@@ -858,11 +877,7 @@ class State:
             if self.exposure is None:
                 raise RsrtError("display_exposed_srgb8: no remembered exposure (auto_exposure first)", NOT_READY)
             exposure = self.exposure
-        out = np.empty(self._source_shape(source) + (4,), np.uint8)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_exposed_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, exposure, _p(out), out.size),
-                    "rsrt_display_exposed_srgb8")
-        return out
+        return self._displayed("rsrt_display_exposed_srgb8", source, sample_total, exposure)
 
     # -- bloom (include/rsrt.h "bloom") -----------------------------------------------------------------
     def _exposure_or_one(self, exposure):
@@ -874,8 +889,7 @@ class State:
         BLOOM_DEFAULTS otherwise; karis: the firefly weighting of the first downsample.  Asynchronous."""
         p = BloomParams(BLOOM_DEFAULTS["levels"] if levels is None else levels, BLOOM_KARIS if karis else 0,
                         BLOOM_DEFAULTS["threshold"] if threshold is None else threshold, 0.0)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_bloom(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_bloom(self._ctx, *self._source_total(source, sample_total), self._exposure_or_one(exposure), C.byref(p),
                                        C.c_void_p(stream) if stream else None), "rsrt_bloom")
 
     def bloom_download(self):
@@ -894,20 +908,15 @@ class State:
         """rsrt_display_bloomed_srgb8: `source` through the display pass at `exposure` (None: the remembered one, else 1 — what
         bloom() took) with `intensity` (BLOOM_DEFAULTS otherwise) times the doubled bloom image added before the tone map:
         [H, W, 4] uint8, of the source's own size ("upsampled": the guide's; "lens", "motion": their source's)."""
-        out = np.empty(self._source_shape(source) + (4,), np.uint8)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_bloomed_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
-                                                       BLOOM_DEFAULTS["intensity"] if intensity is None else intensity, _p(out), out.size),
-                    "rsrt_display_bloomed_srgb8")
-        return out
+        return self._displayed("rsrt_display_bloomed_srgb8", source, sample_total, self._exposure_or_one(exposure),
+                               BLOOM_DEFAULTS["intensity"] if intensity is None else intensity)
 
     # -- local exposure (include/rsrt.h "local exposure") ---------------------------------------------------
     def local_exposure(self, source="mean", cell=None, sample_total=None, stream=None):
         """rsrt_local_exposure: builds the blurred bilateral grid of `source` ("mean": the accumulator over sample_total, default
         sample_count; "denoised", "temporal", "upsampled", "lens": the last depth_of_field(), "motion": the last motion_blur()) on the device, in cells of `cell` pixels (8, 16, 32 or 64; LOCAL_DEFAULTS
         otherwise).  The grid is of the unexposed image.  Asynchronous."""
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_exposure(self._ctx, ALL_SOURCES.get(source, source), n, LOCAL_DEFAULTS["cell"] if cell is None else cell,
+        self._check(self._L.rsrt_local_exposure(self._ctx, *self._source_total(source, sample_total), LOCAL_DEFAULTS["cell"] if cell is None else cell,
                                                 C.c_void_p(stream) if stream else None), "rsrt_local_exposure")
 
     def local_exposure_download(self):
@@ -949,8 +958,7 @@ class State:
         remembered one, else 1), [H, W] float32.  params: key, max_stops; LOCAL_DEFAULTS otherwise."""
         p = self._local_params(shadows, highlights, params)
         out = np.empty(self._source_shape(source), np.float32)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_local_gain_download(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
+        self._check(self._L.rsrt_local_gain_download(self._ctx, *self._source_total(source, sample_total), self._exposure_or_one(exposure), C.byref(p),
                                                      _p(out), out.size), "rsrt_local_gain_download")
         return out
 
@@ -959,18 +967,13 @@ class State:
         gain of the last local_exposure() and, with bloom_intensity > 0, the last bloom() added before it: [H, W, 4] uint8, of the
         source's own size.  shadows, highlights and params (key, max_stops): LOCAL_DEFAULTS otherwise."""
         p = self._local_params(shadows, highlights, params)
-        out = np.empty(self._source_shape(source) + (4,), np.uint8)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_local_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure), C.byref(p),
-                                                     bloom_intensity, _p(out), out.size), "rsrt_display_local_srgb8")
-        return out
+        return self._displayed("rsrt_display_local_srgb8", source, sample_total, self._exposure_or_one(exposure), C.byref(p), bloom_intensity)
 
     # -- white balance and colour grading (include/rsrt.h "white balance and colour grading") ---------------
     def white_meter(self, source="mean", sample_total=None, stream=None):
         """rsrt_white_meter: builds the chroma histogram of `source` ("mean": the accumulator over sample_total, default sample_count;
         "denoised", "temporal", "upsampled", "lens", "motion") on the device.  Asynchronous."""
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_white_meter(self._ctx, ALL_SOURCES.get(source, source), n, C.c_void_p(stream) if stream else None), "rsrt_white_meter")
+        self._check(self._L.rsrt_white_meter(self._ctx, *self._source_total(source, sample_total), C.c_void_p(stream) if stream else None), "rsrt_white_meter")
 
     def white_download(self, **params):
         """rsrt_white_download of the last white_meter(): (histogram, 4097 uint32: 64 x 64 bins, v-major, and the skipped pixels; result
@@ -1032,17 +1035,9 @@ class State:
         with them (LOCAL_DEFAULTS for the one left None; params: key, max_stops); bloom_intensity > 0 adds the last bloom().
         [H, W, 4] uint8, of the source's own size."""
         local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
-        if white is None:
-            white = (1.0, 1.0, 1.0) if self.white is None else self.white
-        if lut_strength is None:
-            lut_strength = 1.0 if self._has_colour_lut() else 0.0
-        c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
-        out = np.empty(self._source_shape(source) + (4,), np.uint8)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_colour_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
-                                                      C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), _p(out), out.size),
-                    "rsrt_display_colour_srgb8")
-        return out
+        c = self._colour_params(white, lut_strength)
+        return self._displayed("rsrt_display_colour_srgb8", source, sample_total, self._exposure_or_one(exposure),
+                               C.byref(local) if local is not None else None, bloom_intensity, C.byref(c))
 
     # -- finished display (include/rsrt.h "finished display") -----------------------------------------------
     def display_finished_srgb8(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
@@ -1053,20 +1048,12 @@ class State:
         of any size or sign, of which the low 32 bits are used);
         noise_aware: the sharpener's limiter (FINISH_NOISE_AWARE).  [H, W, 4] uint8, of the source's own size."""
         local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
-        if white is None:
-            white = (1.0, 1.0, 1.0) if self.white is None else self.white
-        if lut_strength is None:
-            lut_strength = 1.0 if self._has_colour_lut() else 0.0
-        c = ColourParams((C.c_float * 3)(*white), lut_strength, 0, (C.c_uint32 * 3)())
+        c = self._colour_params(white, lut_strength)
         d = FINISH_DEFAULTS
         f = FinishParams(d["sharpness"] if sharpness is None else sharpness, d["grain"] if grain is None else grain, d["dither"] if dither is None else dither,
                          (d["seed"] if seed is None else int(seed)) & 0xFFFFFFFF, d["flags"] | (FINISH_NOISE_AWARE if noise_aware else 0), (C.c_uint32 * 3)())
-        out = np.empty(self._source_shape(source) + (4,), np.uint8)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_display_finished_srgb8(self._ctx, ALL_SOURCES.get(source, source), n, self._exposure_or_one(exposure),
-                                                        C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(f), _p(out), out.size),
-                    "rsrt_display_finished_srgb8")
-        return out
+        return self._displayed("rsrt_display_finished_srgb8", source, sample_total, self._exposure_or_one(exposure),
+                               C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(f))
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------
     def depth_of_field(self, source="mean", focus_distance=None, aperture=None, max_radius=None, sample_total=None, stream=None, out_ptr=None):
@@ -1079,8 +1066,7 @@ class State:
         if focus_distance is None:
             focus_distance = d["focus_distance"] if self.focus_distance is None else self.focus_distance
         p = DofParams(focus_distance, d["aperture"] if aperture is None else aperture, d["max_radius"] if max_radius is None else max_radius, 0)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_dof(self._ctx, ALL_SOURCES.get(source, source), n, _p(self.camera), C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
+        self._check(self._L.rsrt_dof(self._ctx, *self._source_total(source, sample_total), _p(self.camera), C.byref(p), C.c_void_p(out_ptr) if out_ptr else None,
                                      C.c_void_p(stream) if stream else None), "rsrt_dof")
 
     def dof_download(self):
@@ -1123,8 +1109,7 @@ class State:
         if previous is None:
             previous = self.camera if self.motion_camera is None else self.motion_camera
         previous = np.ascontiguousarray(previous)
-        n = self.sample_count if sample_total is None else sample_total
-        self._check(self._L.rsrt_motion_blur(self._ctx, ALL_SOURCES.get(source, source), n, _p(self.camera), _p(previous), C.byref(p),
+        self._check(self._L.rsrt_motion_blur(self._ctx, *self._source_total(source, sample_total), _p(self.camera), _p(previous), C.byref(p),
                                              C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None), "rsrt_motion_blur")
         self.motion_camera = self.camera.copy()
 
@@ -1200,9 +1185,8 @@ class State:
         upsample=True: rsrt_fog_apply_upsampled — the records are smaller than the source (render_fog(size=...), half the size say) and
         the fog image is rebuilt from them and the source's first-hit records (the guide for "upsampled", the AOV buffer otherwise; of
         record_sample_total samples, default guide_sample_count / aov_sample_count) with the remembered fog_params."""
-        n = self.sample_count if sample_total is None else sample_total
+        src, n = self._source_total(source, sample_total)
         nf = self.fog_sample_count if fog_sample_total is None else fog_sample_total
-        src = ALL_SOURCES.get(source, source)
         out, on = C.c_void_p(out_ptr) if out_ptr else None, C.c_void_p(stream) if stream else None
         if upsample:
             if self.fog_params is None:
@@ -1294,8 +1278,7 @@ class State:
     def download_mean_f16(self, sample_total=None):
         """out_texture: [H, W, 4] float16 mean radiance."""
         out = np.empty((self.height, self.width, 4), np.float16)
-        n = sample_total if sample_total is not None else self.sample_count
-        self._check(self._L.rsrt_resolve_mean_f16(self._ctx, n, _p(out), out.size), "rsrt_resolve_mean_f16")
+        self._check(self._L.rsrt_resolve_mean_f16(self._ctx, self._total(sample_total), _p(out), out.size), "rsrt_resolve_mean_f16")
         return out
 
     def debug_view(self, dev_index, out_texture=None, sample_count=None, environment_index=None):
@@ -1311,8 +1294,7 @@ class State:
     def display_srgb8(self, sample_total=None):
         """What the reference shows on screen: [H, W, 4] uint8 (ACES tonemap of the f16 mean, sRGB encoded)."""
         out = np.empty((self.height, self.width, 4), np.uint8)
-        n = sample_total if sample_total is not None else self.sample_count
-        self._check(self._L.rsrt_display_srgb8(self._ctx, n, _p(out), out.size), "rsrt_display_srgb8")
+        self._check(self._L.rsrt_display_srgb8(self._ctx, self._total(sample_total), _p(out), out.size), "rsrt_display_srgb8")
         return out
 
     def stats(self):
