@@ -947,6 +947,52 @@ rsrt_status rsrt_display_finished_srgb8(rsrt_context *ctx, uint32_t source, uint
                                         float bloom_intensity, const rsrt_colour_params *colour, const rsrt_finish_params *finish, uint8_t *host_rgba8,
                                         size_t n_bytes);
 
+/* -- HDR display: PQ 10-bit and scRGB output with content light levels (no reference counterpart) ----------------------------------
+ * Every display above ends in rsrt_aces_tone_map and an sRGB byte.  rsrt_display_hdr is the colour display's chain up to the tone map —
+ * the f16-rounded mean times exposure, plus the bloom, times the local gain, times the white point: linear Rec.709 in units of paper
+ * white — and then, instead of the tone map, a hue-preserving shoulder between knee * peak and peak, the scale to nits and one of two
+ * encodings for an HDR surface: RSRT_HDR_PQ10, Rec.2020 primaries (BT.2087's matrix) under the SMPTE ST 2084 curve, three 10-bit codes
+ * packed R | G << 10 | B << 20 | 3 << 30 into one uint32 a pixel (HDR10 on wgpu Rgb10a2Unorm, DXGI R10G10B10A2, Vulkan
+ * A2B10G10R10_PACK32), optionally with rsrt_display_finished_srgb8's triangular dither over the PQ thresholds; or RSRT_HDR_SCRGB16F,
+ * linear Rec.709 with 1.0 = 80 cd/m^2 as four binary16 a pixel, alpha 1 (scRGB on Rgba16Float).  The same call can return the frame's
+ * content light levels (CTA-861.3 MaxCLL and MaxFALL, HDR10's static metadata), reduced on the device in integers.  The arithmetic is
+ * published in include/rsrt_hdr.h and is bitwise reproducible.  The colour LUT is display-referred SDR and does not apply: lut_strength
+ * > 0 is refused.  There is no HDR IMAGE: the result exists only as output words, and no other pass can take it as a source.  Whole
+ * frame only.  Nothing here writes any buffer the context holds.  A refused call launches nothing.
+ * rsrt_hdr_params defaults: paper white 203 cd/m^2 (BT.2408), peak 1000, knee 0.5, dither 0, seed 0, RSRT_HDR_PQ10, flags 0
+ * (RSRT_HDR_* in include/rsrt_hdr.h). */
+#define RSRT_HDR_PQ10 0u     /* rsrt_hdr_params.encoding: 4 bytes a pixel */
+#define RSRT_HDR_SCRGB16F 1u /* 8 bytes a pixel */
+typedef struct rsrt_hdr_params {
+    float paper_white_nits; /* 1 .. 10000: the luminance of a linear 1.0 (diffuse white) */
+    float peak_nits;        /* paper_white_nits .. 10000: the display's peak; no channel leaves the call brighter */
+    float knee;             /* 0 .. 0.95: the share of the peak below which a pixel passes unchanged */
+    float dither;           /* 0 .. 1: the dither's amplitude in codes (RSRT_HDR_PQ10 only); 0 is the hard quantiser */
+    uint32_t seed;          /* of the dither's noise */
+    uint32_t encoding;      /* RSRT_HDR_PQ10 or RSRT_HDR_SCRGB16F */
+    uint32_t flags;         /* 0 */
+    uint32_t _pad;
+} rsrt_hdr_params;
+typedef struct rsrt_hdr_levels {
+    uint64_t sum_q;  /* the sum over the frame's pixels of q = (uint32_t)(max(R, G, B) in nits * 64), in the encoding's primaries */
+    uint32_t max_q;  /* the largest q */
+    float max_cll;   /* max_q / 64: CTA-861.3 MaxCLL, cd/m^2 */
+    float max_fall;  /* sum_q / (64 * pixels): MaxFALL of this one frame, cd/m^2 */
+    uint32_t _pad;
+} rsrt_hdr_levels;
+/* `source` through the HDR display pass: rsrt_hdr_pixel_nits, then rsrt_hdr_pack_pq10 or rsrt_hdr_pack_scrgb per pixel
+ * (include/rsrt_hdr.h).  n_bytes: pixels * 4 for RSRT_HDR_PQ10 (host_out holds uint32 words), pixels * 8 for RSRT_HDR_SCRGB16F (four
+ * uint16 a pixel).  levels_out may be NULL: the reduction is then not run.  Sources, `local`, bloom_intensity, `colour`, readiness and
+ * errors exactly as for rsrt_display_colour_srgb8, and RSRT_ERR_INVALID_ARGUMENT for NULL hdr, one rsrt_hdr_params_ok refuses (a value
+ * outside the ranges above or not finite, peak below paper white, an unknown encoding or flag, dither > 0 with RSRT_HDR_SCRGB16F),
+ * colour->lut_strength > 0, NULL host_out or another n_bytes.  A refused call writes neither host_out nor *levels_out.
+ * Rust: pub fn rsrt_display_hdr(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                               local: *const RsrtLocalParams, bloom_intensity: f32, colour: *const RsrtColourParams,
+ *                               hdr: *const RsrtHdrParams, host_out: *mut c_void, n_bytes: usize, levels_out: *mut RsrtHdrLevels) -> i32; */
+rsrt_status rsrt_display_hdr(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                             float bloom_intensity, const rsrt_colour_params *colour, const rsrt_hdr_params *hdr, void *host_out, size_t n_bytes,
+                             rsrt_hdr_levels *levels_out);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

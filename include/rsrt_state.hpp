@@ -16,6 +16,7 @@
 #include "rsrt_bloom.h"
 #include "rsrt_colour.h"
 #include "rsrt_finish.h"
+#include "rsrt_hdr.h"
 #include "rsrt_dof.h"
 #include "rsrt_motion.h"
 #include "rsrt_exposure.h"
@@ -487,6 +488,22 @@ public:
     {
         const rsrt_colour_params c = colour_params(white, lut_strength);
         return displayed(rsrt_display_finished_srgb8, source, exposure_or_one(exposure), local, bloom_intensity, &c, &finish);
+    }
+    // -- HDR display (rsrt.h "HDR display"): one device, like the denoiser -------------------------------------------------
+    static rsrt_hdr_params hdr_defaults()
+    {
+        return rsrt_hdr_params{RSRT_HDR_PAPER_WHITE, RSRT_HDR_PEAK, RSRT_HDR_KNEE, RSRT_HDR_DITHER, RSRT_HDR_SEED, RSRT_HDR_ENCODING, RSRT_HDR_FLAGS, 0u};
+    }
+    // display_colour's chain up to its tone map (whose arguments source .. bloom_intensity are; there is no LUT here) under hdr.peak_nits
+    // and encoded as hdr.encoding says: the bytes of one uint32 a pixel (RSRT_HDR_PQ10) or of four binary16 a pixel (RSRT_HDR_SCRGB16F).
+    // levels: NULL, or where the frame's content light levels go
+    std::vector<uint8_t> display_hdr(const rsrt_hdr_params &hdr = hdr_defaults(), rsrt_hdr_levels *levels = nullptr, uint32_t source = RSRT_EXPOSURE_MEAN,
+                                     float exposure = 0.0f, const float *white = nullptr, const rsrt_local_params *local = nullptr, float bloom_intensity = 0.0f)
+    {
+        const rsrt_colour_params c = colour_params(white, 0.0f);
+        std::vector<uint8_t> out(source_pixels(source) * (hdr.encoding == RSRT_HDR_SCRGB16F ? 8u : 4u));
+        check_ctx(rsrt_display_hdr(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &hdr, out.data(), out.size(), levels));
+        return out;
     }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------
     static rsrt_dof_params dof_defaults() { return rsrt_dof_params{RSRT_DOF_FOCUS_DISTANCE, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS}; }

@@ -1969,3 +1969,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_motion.h"
 #include "rt_fog.h"
 #include "rt_finish.h"
+#include "rt_hdr.h"

@@ -220,7 +220,7 @@ rsrt_status rsrt_display_colour_srgb8(rsrt_context *ctx, uint32_t source, uint32
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     DisplayChain c;
-    const rsrt_status st = display_chain(ctx, "display_colour_srgb8", CHAIN_COLOUR, source, sample_total, exposure, local, colour, nullptr, bloom_intensity, host_rgba8,
+    const rsrt_status st = display_chain(ctx, "display_colour_srgb8", CHAIN_COLOUR, source, sample_total, exposure, local, colour, nullptr, nullptr, bloom_intensity, host_rgba8,
                                          n_bytes, &c);
     if (st) return st;
     return read_back(ctx, host_rgba8, n_bytes, 0, [&](void *tmp) {

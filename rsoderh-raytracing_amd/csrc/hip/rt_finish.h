@@ -93,7 +93,7 @@ rsrt_status rsrt_display_finished_srgb8(rsrt_context *ctx, uint32_t source, uint
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     DisplayChain c;
-    const rsrt_status st = display_chain(ctx, "display_finished_srgb8", CHAIN_COLOUR | CHAIN_FINISH, source, sample_total, exposure, local, colour, finish, bloom_intensity,
+    const rsrt_status st = display_chain(ctx, "display_finished_srgb8", CHAIN_COLOUR | CHAIN_FINISH, source, sample_total, exposure, local, colour, finish, nullptr, bloom_intensity,
                                          host_rgba8, n_bytes, &c);
     if (st) return st;
     const auto kernel = finish->sharpness > 0.0f ? rt_display_finish_kernel<true> : rt_display_finish_kernel<false>;

@@ -15,9 +15,9 @@
 //  rt_display_local_kernel   rt_display_exposed_kernel with the slice inside and, with intensity > 0, rt_display_bloomed_kernel's four
 //  rt_local_gain_kernel      taps; the second writes the f32 gain instead of bytes.  A workgroup takes RT_LC_TW x RT_LC_TH pixels; the
 //                            eight corners come through L2 (staging the tile's columns in LDS was no faster: DESIGN.md §17).
-// The tiled displays — these two, rt_display_colour_kernel and rt_display_finish_kernel — share DisplayChain, the struct they take by value,
+// The tiled displays — these two, rt_display_colour_kernel, rt_display_finish_kernel and rt_display_hdr_kernel — share DisplayChain, the struct they take by value,
 // rt_display_gather, which reads a pixel's inputs from it, and display_chain, which makes their entry points' checks and fills it.
-#include "../../../include/rsrt_finish.h" // (the whole display chain: display_chain below checks every stage's parameters)
+#include "../../../include/rsrt_hdr.h" // (the whole display chain: display_chain below checks every stage's parameters)
 
 #define RT_LC_PW 64
 #define RT_LC_PH 64
@@ -152,14 +152,15 @@ size_t local_words(const rsrt_context *ctx) { return 2u * (size_t)rsrt_local_cel
 // the blurred grid: the second half
 uint32_t *local_blurred(const rsrt_context *ctx) { return static_cast<uint32_t *>(ctx->lc_grid.p) + local_words_max(ctx->lc_grid.w, ctx->lc_grid.h); }
 
-// display_chain's `demands`: the params an entry point refuses as NULL (others are off when NULL); CHAIN_FLOATS: it writes a float a pixel, not bytes
-enum : uint32_t { CHAIN_LOCAL = 1u, CHAIN_COLOUR = 2u, CHAIN_FINISH = 4u, CHAIN_FLOATS = 8u };
+// display_chain's `demands`: the params an entry point refuses as NULL (others are off when NULL); CHAIN_FLOATS: it writes a float a pixel, not
+// bytes; CHAIN_HDR: it writes what hdr->encoding says, 4 or 8 bytes a pixel, and takes no LUT
+enum : uint32_t { CHAIN_LOCAL = 1u, CHAIN_COLOUR = 2u, CHAIN_FINISH = 4u, CHAIN_FLOATS = 8u, CHAIN_HDR = 16u };
 
-// Every check of the tiled displays, in the order the faults are reported in: the source, the local, colour and finish params, the bloom
+// Every check of the tiled displays, in the order the faults are reported in: the source, the local, colour, finish and hdr params, the bloom
 // intensity, the output's size, then what the context has to hold where it is asked for: the grid, the bloom image, the LUT.  Fills c.
 rsrt_status display_chain(rsrt_context *ctx, const char *what, uint32_t demands, uint32_t source, uint32_t sample_total, float exposure,
-                          const rsrt_local_params *local, const rsrt_colour_params *colour, const rsrt_finish_params *finish, float intensity, const void *host,
-                          size_t n_out, DisplayChain *c)
+                          const rsrt_local_params *local, const rsrt_colour_params *colour, const rsrt_finish_params *finish, const rsrt_hdr_params *hdr,
+                          float intensity, const void *host, size_t n_out, DisplayChain *c)
 {
     ImageView v;
     rsrt_status st = bloom_source(ctx, what, source, sample_total, exposure, &v);
@@ -172,9 +173,15 @@ rsrt_status display_chain(rsrt_context *ctx, const char *what, uint32_t demands,
     if ((demands & CHAIN_FINISH) && !finish) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: finish is NULL", what);
     if (finish && !rsrt_finish_params_ok(finish))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want sharpness, grain and dither in [0, 1], flags RSRT_FINISH_NOISE_AWARE or 0", what);
+    if ((demands & CHAIN_HDR) && !hdr) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: hdr is NULL", what);
+    if (hdr && !rsrt_hdr_params_ok(hdr))
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want paper_white_nits in [1, 10000], peak_nits from there to 10000, knee in [0, 0.95], dither in [0, 1] "
+                                                     "and 0 with RSRT_HDR_SCRGB16F, encoding RSRT_HDR_PQ10 or RSRT_HDR_SCRGB16F, flags 0", what);
+    if (hdr && colour && colour->lut_strength > 0.0f)
+        return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: lut_strength must be 0 (the colour LUT is display-referred SDR and does not apply to HDR output)", what);
     if (!rsrt_bloom_finite_nonneg(intensity)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: bloom_intensity must be finite and >= 0", what);
     const bool floats = demands & CHAIN_FLOATS;
-    const size_t want = floats ? v.pixels() : v.pixels() * 4;
+    const size_t want = floats ? v.pixels() : v.pixels() * (hdr && hdr->encoding == RSRT_HDR_SCRGB16F ? 8 : 4);
     if (!host || n_out != want) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu %s", what, want, floats ? "floats" : "bytes");
     *c = DisplayChain{}; // (what is not asked for stays zero)
     c->img = v.img; c->w = (int)v.w; c->h = (int)v.h; c->total = v.total; c->exposure = exposure;
@@ -271,7 +278,7 @@ rsrt_status rsrt_local_gain_download(rsrt_context *ctx, uint32_t source, uint32_
     DeviceGuard g(ctx->device);
     if (!host_gain) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "local_gain_download: host_gain is NULL");
     DisplayChain c;
-    const rsrt_status st = display_chain(ctx, "local_gain_download", CHAIN_LOCAL | CHAIN_FLOATS, source, sample_total, exposure, params, nullptr, nullptr, 0.0f, host_gain,
+    const rsrt_status st = display_chain(ctx, "local_gain_download", CHAIN_LOCAL | CHAIN_FLOATS, source, sample_total, exposure, params, nullptr, nullptr, nullptr, 0.0f, host_gain,
                                          n_floats, &c);
     if (st) return st;
     return read_back(ctx, host_gain, n_floats * sizeof(float), 0, [&](void *tmp) {
@@ -286,7 +293,7 @@ rsrt_status rsrt_display_local_srgb8(rsrt_context *ctx, uint32_t source, uint32_
     if (!ctx) return RSRT_ERR_INVALID_ARGUMENT;
     DeviceGuard g(ctx->device);
     DisplayChain c;
-    const rsrt_status st = display_chain(ctx, "display_local_srgb8", CHAIN_LOCAL, source, sample_total, exposure, params, nullptr, nullptr, bloom_intensity, host_rgba8,
+    const rsrt_status st = display_chain(ctx, "display_local_srgb8", CHAIN_LOCAL, source, sample_total, exposure, params, nullptr, nullptr, nullptr, bloom_intensity, host_rgba8,
                                          n_bytes, &c);
     if (st) return st;
     return read_back(ctx, host_rgba8, n_bytes, 0, [&](void *tmp) {

@@ -45,7 +45,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_fog_apply_upsampled",
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
-            "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8", "rsrt_display_finished_srgb8"]
+            "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8", "rsrt_display_finished_srgb8",
+            "rsrt_display_hdr"]
 
 
 class RsrtError(RuntimeError):
@@ -208,6 +209,27 @@ FINISH_DEFAULTS = {"sharpness": 0.5, "grain": 0.0, "dither": 1.0, "seed": 0, "fl
 
 class FinishParams(C.Structure):
     _fields_ = [("sharpness", C.c_float), ("grain", C.c_float), ("dither", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+# the HDR display (include/rsrt.h "HDR display", include/rsrt_hdr.h): its encodings, its defaults, its parameters and its light levels
+HDR_PQ10, HDR_SCRGB16F = 0, 1
+HDR_ENCODINGS = {"pq10": HDR_PQ10, "scrgb16f": HDR_SCRGB16F}
+HDR_DEFAULTS = {"paper_white": 203.0, "peak": 1000.0, "knee": 0.5, "dither": 0.0, "seed": 0, "encoding": "pq10", "flags": 0}
+
+
+class HdrParams(C.Structure):
+    _fields_ = [("paper_white_nits", C.c_float), ("peak_nits", C.c_float), ("knee", C.c_float), ("dither", C.c_float), ("seed", C.c_uint32),
+                ("encoding", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class HdrLevels(C.Structure):
+    _fields_ = [("sum_q", C.c_uint64), ("max_q", C.c_uint32), ("max_cll", C.c_float), ("max_fall", C.c_float), ("_pad", C.c_uint32)]
+
+
+def hdr_unpack_pq10(words):
+    """The 10-bit codes of RSRT_HDR_PQ10 words (R | G << 10 | B << 20 | 3 << 30): [H, W] uint32 -> [H, W, 3] uint16."""
+    w = np.asarray(words, np.uint32)
+    return np.stack([(w >> np.uint32(10 * c)) & np.uint32(1023) for c in range(3)], axis=-1).astype(np.uint16)
 
 
 # the procedural daylight sky (include/rsrt.h rsrt_environment_sky, include/rsrt_sky.h): its defaults (RSRT_SKY_*) and its parameters.
@@ -436,6 +458,7 @@ def lib():
         L.rsrt_colour_lut_reset.argtypes = [C.c_void_p]
         L.rsrt_display_colour_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_finished_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_display_hdr.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         _lib = L
     return _lib
 
@@ -1054,6 +1077,31 @@ class State:
                          (d["seed"] if seed is None else int(seed)) & 0xFFFFFFFF, d["flags"] | (FINISH_NOISE_AWARE if noise_aware else 0), (C.c_uint32 * 3)())
         return self._displayed("rsrt_display_finished_srgb8", source, sample_total, self._exposure_or_one(exposure),
                                C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(f))
+
+    # -- HDR display (include/rsrt.h "HDR display") ----------------------------------------------------------
+    def display_hdr(self, source="mean", exposure=None, white=None, shadows=None, highlights=None, bloom_intensity=0.0, paper_white=None, peak=None,
+                    knee=None, encoding="pq10", dither=None, seed=None, levels=False, sample_total=None, **params):
+        """rsrt_display_hdr: display_colour_srgb8's chain up to its tone map (whose arguments `source` .. `bloom_intensity`, sample_total and
+        params are; there is no LUT here) brought under `peak` cd/m^2 by a hue-preserving shoulder that begins at `knee` of it, with a
+        linear 1.0 at `paper_white` cd/m^2 (None: HDR_DEFAULTS), and encoded for an HDR surface.  encoding "pq10": [H, W] uint32, Rec.2020
+        PQ codes packed R | G << 10 | B << 20 | 3 << 30 (hdr_unpack_pq10 takes them apart), dithered at `dither` with the noise of `seed`
+        (an integer of any size or sign, of which the low 32 bits are used); "scrgb16f": [H, W, 4] float16, linear Rec.709, 1.0 = 80
+        cd/m^2, alpha 1.  Of the source's own size.  levels=True: (image, {"max_cll", "max_fall" in cd/m^2, "max_q", "sum_q"}), the
+        frame's CTA-861.3 content light levels."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        c = self._colour_params(white, 0.0)
+        d = HDR_DEFAULTS
+        enc = HDR_ENCODINGS.get(encoding, encoding)
+        p = HdrParams(d["paper_white"] if paper_white is None else paper_white, d["peak"] if peak is None else peak, d["knee"] if knee is None else knee,
+                      d["dither"] if dither is None else dither, (d["seed"] if seed is None else int(seed)) & 0xFFFFFFFF, enc, d["flags"], 0)
+        shape = self._source_shape(source)
+        out = np.empty(shape + (4,), np.uint16) if enc == HDR_SCRGB16F else np.empty(shape, np.uint32)
+        lv = HdrLevels()
+        self._check(self._L.rsrt_display_hdr(self._ctx, *self._source_total(source, sample_total), self._exposure_or_one(exposure),
+                                             C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(p), _p(out), out.nbytes,
+                                             C.byref(lv) if levels else None), "rsrt_display_hdr")
+        img = out.view(np.float16) if enc == HDR_SCRGB16F else out
+        return (img, {"max_cll": lv.max_cll, "max_fall": lv.max_fall, "max_q": lv.max_q, "sum_q": lv.sum_q}) if levels else img
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------
     def depth_of_field(self, source="mean", focus_distance=None, aperture=None, max_radius=None, sample_total=None, stream=None, out_ptr=None):

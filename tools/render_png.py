@@ -1,4 +1,4 @@
-"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [foghalf=on] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] [finish=SHARPNESS[,GRAIN[,DITHER]]] — render
+"""python tools/render_png.py <scene> <w> <h> <spp | noise=X[,MAX]> <bounces> <out.png> [--denoise] [sky=ELEV_DEG,AZIMUTH_DEG[,TURBIDITY]] [exposure=auto | exposure=X] [bloom=on | bloom=INTENSITY] [local=on | local=SHADOWS,HIGHLIGHTS] [dof=FOCUS,APERTURE[,RADIUS] | dof=auto,APERTURE[,RADIUS]] [motion=YAW_DEG,DOLLY[,SHUTTER[,RADIUS]]] [fog=DENSITY[,G[,STEPS]]] [foghalf=on] [wb=auto | wb=R,G,B] [cdl=SLOPE,OFFSET,POWER,SAT] [finish=SHARPNESS[,GRAIN[,DITHER]]] [hdr=pq[,PAPER_WHITE[,PEAK]]] — render
 through the product path and write the display image; noise=X in place of a sample count: render until the largest 16x16 tile's noise
 estimate is at most X (State.render_to_noise, at most MAX samples, default 1024) and print the rounds; --denoise: the AOV pass over the
 same samples and the default filter, the denoised display image instead; exposure=auto: meter the picture that is written
@@ -30,8 +30,12 @@ the tone-mapped picture through it.  Either one sends the picture through the co
 composes with exposure= (1 without), bloom=, local=, dof= and sky=:  house 960 540 64 8 out.png sky=8,120 exposure=auto wb=auto
 finish=SHARPNESS[,GRAIN[,DITHER]]: the final display goes through the finished display (State.display_finished_srgb8) with whatever
 exposure=, wb=, cdl=, local= and bloom= were given: the sharpener at SHARPNESS (0 .. 1), film grain at GRAIN (default 0) and the dithered
-quantiser at DITHER (default 1), seed 0."""
-import os, sys
+quantiser at DITHER (default 1), seed 0.
+hdr=pq[,PAPER_WHITE[,PEAK]]: the final display is the HDR display (State.display_hdr, PQ10, a linear 1.0 at PAPER_WHITE cd/m^2 under a peak of
+PEAK, defaults 203 and 1000) with whatever exposure=, wb=, local= and bloom= were given (cdl= and finish= are display-referred SDR and do not
+compose with it), written as a 16-bit RGB PNG of the 10-bit codes (code << 6 | code >> 4) with a cICP chunk (BT.2020 primaries 9, PQ
+transfer 16, RGB matrix 0, full range 1) and a cLLi chunk holding the frame's MaxCLL and MaxFALL:  house 960 540 64 8 out.png exposure=auto hdr=pq"""
+import os, struct, sys, zlib
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import rsoderh_raytracing_amd as R
@@ -56,7 +60,25 @@ if wb is not None and wb != "auto":
     wb = tuple(float(v) for v in wb.split(","))
 cdl = next((tuple(float(v) for v in a[len("cdl="):].split(",")) for a in sys.argv[1:] if a.startswith("cdl=")), None)
 finish = next((tuple(float(v) for v in a[len("finish="):].split(",")) for a in sys.argv[1:] if a.startswith("finish=")), None)
-args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "foghalf=", "sky=", "wb=", "cdl=", "finish="))]
+hdr = next((a[len("hdr="):].split(",") for a in sys.argv[1:] if a.startswith("hdr=")), None)
+if hdr is not None and (hdr[0] != "pq" or cdl is not None or finish is not None):
+    sys.exit("render_png.py: hdr= is hdr=pq[,PAPER_WHITE[,PEAK]] and takes neither cdl= nor finish=")
+args = [a for a in sys.argv[1:] if a != "--denoise" and not a.startswith(("exposure=", "bloom=", "local=", "dof=", "motion=", "fog=", "foghalf=", "sky=", "wb=", "cdl=", "finish=", "hdr="))]
+
+
+def write_hdr_png(path, codes, levels):
+    """codes [H, W, 3] 10-bit Rec.2020 PQ codes -> a 16-bit RGB PNG tagged with cICP (9, 16, 0, 1) and cLLi (MaxCLL, MaxFALL in 0.0001 cd/m^2)."""
+    import numpy as np
+    c = codes.astype(np.uint16)
+    rows = ((c << 6) | (c >> 4)).astype(">u2").reshape(c.shape[0], -1)
+    raw = b"".join(b"\0" + r.tobytes() for r in rows)  # filter 0 on every row
+    chunk = lambda kind, data: struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)  # noqa: E731
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", c.shape[1], c.shape[0], 16, 2, 0, 0, 0)) + chunk(b"cICP", bytes([9, 16, 0, 1])) +
+                chunk(b"cLLi", struct.pack(">II", round(levels["max_cll"] * 10000), round(levels["max_fall"] * 10000))) + chunk(b"IDAT", zlib.compress(raw, 6)) +
+                chunk(b"IEND", b""))
+
+
 name, w, h, mb, out = args[0], int(args[1]), int(args[2]), int(args[4]), args[5]
 sc = R.Scene.load_toml(os.path.join(ROOT, 'tests', 'golden', 'assets', 'scenes', name + '.toml'))
 if sky:
@@ -112,7 +134,7 @@ if exposure == "auto":
     r = st.auto_exposure(source)
     print("metered exposure %.6g, average luminance %.6g (%d pixels metered, %d skipped)" % (r["exposure"], r["average_luminance"], r["metered"], r["skipped"]))
     exposure = r["exposure"]
-if wb is not None or cdl is not None or finish is not None:
+if wb is not None or cdl is not None or finish is not None or hdr is not None:
     if wb == "auto":
         r = st.auto_white_balance(source)
         print("white point %.4f %.4f %.4f (illuminant %.4f 1 %.4f; %d of %d pixels in the window%s)" % (r["white"] + (r["illuminant"][0], r["illuminant"][2], r["gated"],
@@ -125,6 +147,14 @@ if wb is not None or cdl is not None or finish is not None:
     if local is not None:
         st.local_exposure(source)
         strengths = {"shadows": R.state.LOCAL_DEFAULTS["shadows"] if local[0] is None else local[0], "highlights": local[1]}
+    if hdr is not None:
+        words, levels = st.display_hdr(source, 1.0 if exposure is None else exposure, wb or (1.0, 1.0, 1.0), bloom_intensity=bloom or 0.0,
+                                       paper_white=float(hdr[1]) if len(hdr) > 1 else None, peak=float(hdr[2]) if len(hdr) > 2 else None, levels=True,
+                                       **(strengths if local is not None else {}))
+        print("hdr: PQ10, MaxCLL %.6g cd/m^2, MaxFALL %.6g cd/m^2" % (levels["max_cll"], levels["max_fall"]))
+        write_hdr_png(out, R.state.hdr_unpack_pq10(words), levels)
+        g = st.stats(); print(name, 'kernel ms', g['kernel_ms'], 'rays', g['ext_rays'] + g['shadow_rays'])
+        sys.exit(0)
     show = st.display_colour_srgb8
     if finish is not None:
         knobs = dict(zip(("sharpness", "grain", "dither"), finish))
