@@ -77,6 +77,37 @@ def test_synthetic_frames_equal_the_numpy_restatement_word_for_word(h, w):
         st.close()
 
 
+def test_the_levels_of_272_workgroups_and_of_a_sum_past_32_bits():
+    """136 x 512: 17 x 16 = 272 workgroups, so rt_hdr_levels_kernel's loop over the pairs takes a second, partial trip (lanes 0 .. 15).
+    (a) every pixel at a peak of 10000 cd/m^2: sum q = 69632 x 640000 = 4.46e10, which carries out of the low half of the 64-bit sum on
+    its way down the shuffles; (b) tests/frame_chain.py's lognormal frame at the default settings: pairs that differ from workgroup to
+    workgroup, and the frame's only pixel at the peak in workgroup 271, which only the second trip reads.  No local exposure, no bloom."""
+    import frame_chain as FC
+    bright, (lognormal, (y, x)) = FC.levels_bright(), FC.levels_lognormal()
+    h, w = FC.LEVELS_H, FC.LEVELS_W
+    st = R.State()
+    devs = []  # (both frames' device memory lives until the context is closed)
+    try:
+        for sums, total, hdr in ((bright, 3, FC.LEVELS_BRIGHT), (lognormal, 1, {})):
+            dev = DeviceArray(sums)
+            devs.append(dev)
+            st.bind_accumulator(dev.data_ptr(), w, h)
+            for enc in (PQ10, SCRGB16F):
+                kw = dict(hdr, encoding=enc)
+                want, want_lv = hdr_ref.display(sums, total, 1.0, **kw)
+                if sums is bright:
+                    assert want_lv["sum_q"] > 2 ** 32 and want_lv["max_fall"] == want_lv["max_cll"] == 10000.0
+                else:
+                    assert FC.workgroup_of(y, x) == 271 and want_lv["max_q"] == int(hdr_ref.level_q(hdr_ref.nits_of(hdr_ref.linear(sums, 1, 1.0), encoding=enc))[y, x])
+                got, lv = shown(st, "mean", 1.0, kw, total)
+                assert got.shape == want.shape and np.array_equal(got, want), kw
+                assert lv == want_lv, (kw, lv, want_lv)
+                assert np.array_equal(shown(st, "mean", 1.0, kw, total, levels=False)[0], got)  # the variant without the levels: the same words
+            assert util.same_bits_or_nan(dev.numpy(), sums)  # the kernels read only
+    finally:
+        st.close()
+
+
 @pytest.fixture(scope="module")
 def house():
     """House at 96 x 54 and 4 spp with the denoised and the upsampled (192 x 108) image."""
