@@ -799,7 +799,7 @@ std::unique_ptr<BuildNode> build_sah(PrimInfo *prims, size_t n, std::vector<Prim
             else { end_index--; std::swap(prims[split_index], prims[end_index]); }
         }
     }
-    if (split_index == 0 || split_index == n) { // :317-326, unreachable (buckets 0 and 11 never empty)
+    if (split_index == 0 || split_index == n) { // :317-326: reached when max_c - min_c overflows to inf (every item in bucket 0), never for a finite span
         size_t mid = n / 2;
         std::nth_element(prims, prims + mid, prims + n, [&](const PrimInfo &a, const PrimInfo &b) {
             return comp(b_center(a.bounds), axis) < comp(b_center(b.bounds), axis);

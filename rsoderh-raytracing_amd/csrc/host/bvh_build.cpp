@@ -124,7 +124,13 @@ int build_bvh(std::vector<Item> &items, std::vector<rsrt_primitive_info> &prims_
             if (bucket_of(p[split].centroid[axis], lo, hi) <= best) split++;
             else std::swap(p[split], p[--end]);
         }
-        if (split == 0 || split == n) { // reference's median fallback (:317-326); unreachable in practice
+        // The reference's median fallback (:317-326).  Reached when hi - lo overflows to inf (centroids from -3e38 to 3e38): (c - lo) / inf
+        // is 0 or NaN, every item lands in bucket 0, every cost is NaN, bucket 0 is chosen and split == n.  A finite hi - lo never gets
+        // here: the item at lo is in bucket 0, the one at hi in bucket 11.  The reference selects with Rust's select_nth_unstable_by,
+        // this with std::nth_element: both put the median in place and partition around it, but the order INSIDE the two halves is each
+        // library's own, so below such a node the tree is a valid one and not promised to be the reference's (which, as written, would
+        // stop before it: Bounds3::from_bounds asserts over the empty buckets, scene.rs:96).  The device builder refuses instead.
+        if (split == 0 || split == n) {
             split = n / 2;
             std::nth_element(p, p + split, p + n, [axis](const Item &a, const Item &b) { return a.centroid[axis] < b.centroid[axis]; });
         }

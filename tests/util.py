@@ -53,14 +53,17 @@ def same_bits_or_nan(a, b):
     return bool(np.array_equal(na, nb) and np.array_equal(bits(a)[~na], bits(b)[~nb]))
 
 
-def probe_modes(name, flat=None):
+def probe_modes(name, flat=None, wide=True):
     """Every way rsrt_cast_rays can run a query (include/rsrt.h): traversal 0 threaded / 1 stack / 2 typed leaf loops /
     3 flat (what house, default and cube run in production; suzanne's 968 triangles do not qualify) / 4 fixed-order walk
     / 5 wide walk (4-wide nodes, one ray a lane) / 6 cooperative wide walk (the same nodes, a wave's rays as work items on two LDS stacks: what
     suzanne and anything bigger run), x scene read from global memory or from LDS as the production kernel stages
-    it for that traversal (bit 4), x cast_ray / cast_ray_bvh (bit 0).  flat: whether the scene qualifies for traversal 3 (default: by name)."""
+    it for that traversal (bit 4), x cast_ray / cast_ray_bvh (bit 0).  flat: whether the scene qualifies for traversal 3 (default: by name).
+    wide: whether it qualifies for traversals 5 and 6."""
     flat = (name != "suzanne") if flat is None else flat
-    sels = [0, 1, 2, 4, 5, 6] + ([3] if flat else [])  # (5, 6: the wide walks — every builder-made tree qualifies)
+    # 5, 6: the wide walks take the trees of the shipped scenes, not every tree the builder makes: equal centroids give leaves of any
+    # length (more than the 8 records a wide node's leaf slot holds), and a tree of one node has no wide tree (tests/edge_trees.py)
+    sels = [0, 1, 2, 4] + ([5, 6] if wide else []) + ([3] if flat else [])
     return [(sel << 1) | lds | bvh_only for sel in sels for lds in (0, 16) for bvh_only in (0, 1)]
 
 
