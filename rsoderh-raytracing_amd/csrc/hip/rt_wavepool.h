@@ -4,8 +4,9 @@
 // ~13 of 64 lanes active per VALU instruction (profiles/r01_v1_*): lanes wait for each other across
 // stages of very different length.  Here a WAVE owns a pool of POOL path slots, every slot carries a
 // stage tag, and the wave repeatedly
-//     1. counts the slots waiting in each stage (wave64 ballots over the tag column),
-//     2. picks the fullest stage,
+//     1. counts the slots waiting in each stage (wave64 ballots over the tag column; the flat kernel keeps the counts from trip to
+//        trip and only moves the slots that ran),
+//     2. picks the fullest stage (rt_pool_pick.h),
 //     3. compacts that stage's slot ids into a dense list (ballot + prefix popcount) — lane i
 //        takes list[i] — and runs ONLY that stage's code for up to 64 slots at once.
 // A path's arithmetic is untouched (same functions, same order), so the image is bit-identical;
@@ -48,6 +49,7 @@
 #include "rt_device.h"
 #include "rt_coop.h"
 #include "rt_cold_layout.h"
+#include "rt_pool_pick.h"
 
 enum HotField { H_OX, H_OY, H_OZ, H_EX, H_EY, H_EZ, H_SX, H_SY, H_SZ, H_T, H_CT, H_COUNT };
 // H_CT: stage tag (3 bits) | flags (4 bits) | cursor of the traversal in progress, or the record of the hit it found (25 bits)
@@ -68,6 +70,7 @@ static_assert(kColdWideStack == RT_WSTACK && kColdWideStateWords == RT_WSTATE_WO
               "rt_cold_layout.h sizes the walks' columns by the walks' own constants");
 enum PoolTag { TAG_FREE = 0, TAG_TRACE = 1, TAG_MISS = 2, TAG_SHADE = 3, TAG_FINISH = 4, TAG_IDLE = 6 };
 enum PoolStage { ST_GEN = 0, ST_TRACE = 1, ST_MISS = 2, ST_SHADE = 3, ST_FINISH = 4, ST_COUNT = 5 };
+static_assert(ST_COUNT == kPoolPickStages, "rt_pool_pick.h picks among these stages, in this order");
 
 // What a wave keeps in LDS: its hot columns (TRAV 6: twelve, rt_coop.h CoopCols — the result cell is two dwords wide), the compaction list
 // (TRAV 6: every waiting ray is traced at once, so the list holds a whole pool — and the walk's leaf stack uses the same words afterwards) and,
@@ -150,6 +153,13 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
     constexpr bool kFlatVote = kRngHot && kBounceInCt; // a TRACE call may return a flat traversal unfinished
     constexpr bool kPackedMiss = TRAV == 2 || TRAV == 6; // MISS reads an escaping ray's pmf from the texels' alpha (rt_device.h)
     constexpr bool kGenTrace = TRAV >= 2 && !kCoop; // GEN traces the camera ray it has built (the near-first tree walks, kept for RSRT_FLAG_PRUNE, would spill)
+    // The flat kernel's scheduler trip, the same decisions in about 80 instructions instead of about 140 (profiles/scheduler_trip_ab.txt): the
+    // stage counts are kept from trip to trip instead of counted over every tag (settle, below), the stage is picked on packed keys
+    // (rt_pool_pick.h), and a slot's place in the list comes from v_mbcnt instead of a per-lane prefix mask held in two registers through
+    // every stage.  The walks keep the census, the scan and the mask: they compile to the instructions they had, at their 128 registers.
+    constexpr bool kKeptCounts = TRAV == 2;
+    constexpr bool kKeyPick = TRAV == 2;
+    constexpr bool kMbcnt = TRAV == 2;
     const DevScene &sc = P.scene;
     if (SV != 0) stage_scene_lds(sc);
     const typename PoolView<SV>::type S = PoolView<SV>::make(sc);
@@ -189,6 +199,8 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
 
     uint32_t chunk_next = 0, chunk_left = 0, chunk_tile_slot0 = 0, chunk_tx0 = 0, chunk_ty0 = 0, chunk_s0 = 0, chunk_p0 = 0;
     bool exhausted = false;
+    uint32_t kept[ST_COUNT] = {POOL, 0u, 0u, 0u, 0u}; // kKeptCounts: how many slots wait in each stage (wave-uniform) — all are FREE, GEN's
+    (void)kept;
     unsigned long long n_paths = 0, n_ext = 0, n_shadow = 0;
     uint32_t n_work = 0; // box steps + primitive tests of the tree walks (per lane; widened in the final reduction)
 #ifdef RT_INSTRUMENT
@@ -266,27 +278,51 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
         if (kCoop) asm volatile("" : "+v"(lane));
         RT_MARK(0);
         DBG_STAMP(21); // previous stage's tail is charged below; this resets the clock for the census
-        // ---------------- 1. census of the stage tags (each lane looks at its kSlotsPerLane slots)
+        // ---------------- 1. the stage tags (each lane looks at its kSlotsPerLane slots) and how many slots wait in each stage
         uint32_t tags[L::kSlotsPerLane];
         uint32_t count[ST_COUNT] = {};
-        for (uint32_t k = 0; k < L::kSlotsPerLane; k++) {
-            tags[k] = (lane + 64u * k < POOL) ? TAG_OF(lane + 64u * k) : (uint32_t)TAG_IDLE;
-            const uint32_t st = stage_of_tag(tags[k]);
-            for (uint32_t s = 0; s < ST_COUNT; s++) count[s] += (uint32_t)__popcll(__ballot(st == s));
+        if constexpr (kKeptCounts) { // the counts are kept from trip to trip (settle, below): the tags are read for the compaction alone
+            for (uint32_t k = 0; k < L::kSlotsPerLane; k++)
+                tags[k] = (lane + 64u * k < POOL) ? TAG_OF(lane + 64u * k) : (uint32_t)TAG_IDLE;
+            for (uint32_t s = 0; s < ST_COUNT; s++) count[s] = kept[s];
+#ifdef RT_INSTRUMENT
+            // (diagnostic build: the kept counts against a census of every tag, trip by trip; counter 26 is the cooperative walk's otherwise)
+            for (uint32_t s = 0; s < ST_COUNT; s++) {
+                uint32_t n = 0;
+                for (uint32_t k = 0; k < L::kSlotsPerLane; k++) n += (uint32_t)__popcll(__ballot(stage_of_tag(tags[k]) == s));
+                if (lane == 0 && !(exhausted && s == ST_GEN) && n != count[s]) DBG_ADD(26, 1);
+            }
+#endif
+        } else { // census: a ballot per (slot row, stage)
+            for (uint32_t k = 0; k < L::kSlotsPerLane; k++) {
+                tags[k] = (lane + 64u * k < POOL) ? TAG_OF(lane + 64u * k) : (uint32_t)TAG_IDLE;
+                const uint32_t st = stage_of_tag(tags[k]);
+                for (uint32_t s = 0; s < ST_COUNT; s++) count[s] += (uint32_t)__popcll(__ballot(st == s));
+            }
         }
-        if (exhausted) count[ST_GEN] = 0;
-        // ---------------- 2. which stage: the fullest (ties: the later stage, which drains paths)
+        // ---------------- 2. which stage: the fullest (ties: the later stage, which drains paths); never GEN once the work is handed out
         uint32_t best = ST_COUNT, best_n = 0;
-        for (uint32_t s = 0; s < ST_COUNT; s++)
-            if (count[s] >= best_n && count[s] > 0) { best = s; best_n = count[s]; }
-        if (best == ST_COUNT) break; // nothing left anywhere
+        if constexpr (kKeyPick) {
+            const PoolPick pick = pool_pick(count[ST_GEN], count[ST_TRACE], count[ST_MISS], count[ST_SHADE], count[ST_FINISH], exhausted);
+            best = pick.best; best_n = pick.best_n;
+        } else {
+            if (exhausted) count[ST_GEN] = 0;
+            for (uint32_t s = 0; s < ST_COUNT; s++)
+                if (count[s] >= best_n && count[s] > 0) { best = s; best_n = count[s]; }
+        }
+        // nothing left anywhere (the pick's "no stage" and "no slots" are one fact; tested as the count, it stays a scalar compare)
+        if (kKeyPick ? best_n == 0u : best == ST_COUNT) break;
         // ---------------- 3. compaction: dense list of the chosen stage's slots
         uint32_t base = 0;
         for (uint32_t k = 0; k < L::kSlotsPerLane; k++) {
             const bool mine = stage_of_tag(tags[k]) == best;
             const unsigned long long m = __ballot(mine);
-            const uint32_t pos = base + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (mine && pos < L::kListDwords) list[pos] = lane + 64u * k;
+            // (v_mbcnt counts the mask's bits below the lane: no per-lane prefix mask (1 << lane) - 1 kept in two registers through every stage)
+            const uint32_t below = kMbcnt ? __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))
+                                          : (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            const uint32_t pos = base + below;
+            // (the first row's positions are lane counts, below 64: the compiler saw that in the prefix mask, not in v_mbcnt)
+            if (mine && ((kMbcnt && k == 0u && L::kListDwords >= 64u) || pos < L::kListDwords)) list[pos] = lane + 64u * k;
             base += (uint32_t)__popcll(m);
         }
         RT_WAVE_HANDOVER(); // list[] is read by other lanes than wrote it
@@ -298,6 +334,26 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
         if (lane == 0) { DBG_ADD(dbg_stage, 1); DBG_ADD(5 + dbg_stage, (kCoop && best == ST_TRACE) ? best_n : n_run); }
         DBG_STAMP(22); // census + compaction
         RT_MARK(1);
+        // What a stage ends with (kKeptCounts): only the n_run slots that ran can have changed stage.  They leave `from`; lanes [0, n_run)
+        // read back the tag of the slot they ran, and a ballot per stage of `exits` — the stages `from` can leave a slot in — says where to.
+        // With `rest`, the last of the exits takes whoever is left and needs no ballot (GEN cannot: the slots it parks as IDLE count nowhere).
+        // A slot GEN left FREE counts as GEN's again.
+        auto settle = [&](const uint32_t from, const uint32_t exits, const bool rest) __attribute__((always_inline)) {
+            if constexpr (kKeptCounts) {
+                RT_WAVE_HANDOVER();
+                const uint32_t now = on ? TAG_OF(slot) : (uint32_t)TAG_IDLE;
+                kept[from] -= n_run;
+                uint32_t left = n_run;
+                for (uint32_t s = 0; s < ST_COUNT; s++) {
+                    if (!((exits >> s) & 1u)) continue;
+                    if (rest && (exits >> (s + 1u)) == 0u) { kept[s] += left; break; }
+                    const uint32_t n = (uint32_t)__popcll(__ballot(stage_of_tag(now) == s));
+                    kept[s] += n;
+                    left -= n;
+                }
+            }
+        };
+#define EXIT(st) (1u << (st))
 
         if (best == ST_GEN) {
             // ---------------- GEN: hand out (pixel, sample) items of the wave's chunk
@@ -364,6 +420,8 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 for (uint32_t k = 0; k < L::kSlotsPerLane; k++)
                     if (lane + 64u * k < POOL && TAG_OF(lane + 64u * k) == TAG_FREE) SET_TAG(lane + 64u * k, TAG_IDLE);
             }
+            settle(ST_GEN, EXIT(ST_GEN) | EXIT(ST_TRACE) | EXIT(ST_MISS) | EXIT(ST_SHADE), false); // (a camera ray has no shadow ray: never FINISH)
+            if (exhausted) kept[ST_GEN] = 0u; // every FREE slot is parked; the pick masks GEN from here on, whatever becomes FREE later
         } else if (kCoop && best == ST_TRACE) {
             // ---------------- TRACE, cooperative wide walk: EVERY slot that waits in TRACE (the list holds them all), its shadow ray and its
             // extension ray at once, as items on the wave's two stacks (rt_coop.h); when the stacks are empty every ray is done
@@ -416,6 +474,7 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 const V3 d = v3(HOTF(dcol, slot), HOTF(dcol + 1u, slot), HOTF(dcol + 2u, slot));
                 trace_slot(slot, ct, o, d, false);
             }
+            settle(ST_TRACE, EXIT(ST_TRACE) | EXIT(ST_MISS) | EXIT(ST_SHADE) | EXIT(ST_FINISH), true);
         } else if (best == ST_MISS) {
             // ---------------- MISS: brute-force fallback of cast_ray (shader.wgsl:583-598), then escape
             RT_MARK2(0);
@@ -495,6 +554,7 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                     SET_TAG(slot, TAG_FREE);
                 }
             }
+            settle(ST_MISS, EXIT(ST_GEN) | EXIT(ST_SHADE), true);
         } else if (best == ST_SHADE) {
             // ---------------- SHADE: one whole iteration of trace_ray's loop body at a hit (shader.wgsl:1233-1299)
             RT_MARK2(4);
@@ -618,6 +678,7 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                            (want_shadow ? (uint32_t)F_SHADOW : 0u) | (finished ? 0u : (uint32_t)F_EXT) | (nee_counts ? (uint32_t)F_NEE : 0u), TAG_TRACE);
                 }
             }
+            settle(ST_SHADE, EXIT(ST_GEN) | EXIT(ST_TRACE), true);
         } else {
             // ---------------- FINISH: the path ended at its last vertex; its shadow ray is back
             RT_MARK2(7);
@@ -628,11 +689,13 @@ __global__ __launch_bounds__(BLOCK, RT_POOL_WAVES_PER_SIMD) void rt_render_pool_
                 store_sample(P.sample_buf + (size_t)COLD(C_OUT, slot) * 3u, Lr);
                 SET_TAG(slot, TAG_FREE);
             }
+            settle(ST_FINISH, EXIT(ST_GEN), true);
         }
         RT_MARK(15);
         RT_WAVE_HANDOVER(); // tags, hot and cold columns: the next census / stage reads them from other lanes
         DBG_STAMP(16 + dbg_stage); // the stage just run
     }
+#undef EXIT
 #undef HOT
 #undef HOTF
 #undef SETHU

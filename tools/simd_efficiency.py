@@ -25,6 +25,8 @@ for i, n in enumerate(names):
     if c[i]:
         print('  stage %-5s invocations %12.0f  avg lanes %.1f / 64' % (n, c[i], c[5 + i] / c[i]))
 rays = g['ext_rays'] + g['shadow_rays']
+if g['traversal_steps'] == 0:  # the flat kernel keeps its stage counts from trip to trip; this build checks them against a census of every tag
+    print('  scheduler: %d trips, kept stage counts differed from the census on %d (counter 26; must be 0)' % (sum(c[0:5]), c[26]))
 print('  trace: outer trips/wave-invocation %.2f' % (c[14] / max(c[1], 1)))
 print('  descend loop: wave trips %.3e, lane trips %.3e -> efficiency %.1f%% of 64 lanes ; nodes/ray %.2f' % (c[10], c[11], 100 * c[11] / max(64 * c[10], 1), c[11] / rays))
 print('  leaf loop   : wave trips %.3e, lane trips %.3e -> efficiency %.1f%% ; prim tests/ray %.2f' % (c[12], c[13], 100 * c[13] / max(64 * c[12], 1), c[13] / rays))
