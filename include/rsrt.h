@@ -993,6 +993,54 @@ rsrt_status rsrt_display_hdr(rsrt_context *ctx, uint32_t source, uint32_t sample
                              float bloom_intensity, const rsrt_colour_params *colour, const rsrt_hdr_params *hdr, void *host_out, size_t n_bytes,
                              rsrt_hdr_levels *levels_out);
 
+/* -- video output: Y'CbCr 4:2:0 frames at 8 and 10 bits (no reference counterpart) -------------------------------------------------
+ * What an encoder, a stream or a player takes.  rsrt_display_video is the colour display's chain (RSRT_VIDEO_BT709: up to and with the
+ * tone map and the LUT, the colour rsrt_display_colour_srgb8 quantises) or the HDR display's (RSRT_VIDEO_HDR10: rsrt_display_hdr's
+ * Rec.2020 nits behind the shoulder), then per pixel a continuous transfer code over the sRGB or the PQ thresholds (no pow), the
+ * BT.709 or the BT.2020 non-constant-luminance matrix, a 2 x 2 chroma reduction at one of three sitings, a quantiser at 8 or 10 bits
+ * in limited or full range with an optional triangular dither, and a semi-planar (NV12, P010) or planar (I420, yuv420p10le) frame of a
+ * third to three quarters of the RGB words' size.  The arithmetic is published in include/rsrt_video.h and is bitwise reproducible;
+ * rsrt_video_planes there gives the frame's byte count and where its planes lie.  There is no video IMAGE: the frame exists only as
+ * output bytes, and no pass takes it as a source.  Whole frame only.  Nothing here writes any buffer the context holds.  A refused
+ * call launches nothing.  H.273 tags of the result: RSRT_VIDEO_BT709 colour primaries 1, transfer 13 (sRGB), matrix 1;
+ * RSRT_VIDEO_HDR10 9, 16, 9; chroma sample location type = siting.
+ * rsrt_video_params defaults: RSRT_VIDEO_BT709, 8 bits, RSRT_VIDEO_SEMIPLANAR, RSRT_VIDEO_LIMITED, RSRT_VIDEO_SITING_LEFT, dither 0,
+ * seed 0, flags 0 (RSRT_VIDEO_DEFAULT_* in include/rsrt_video.h). */
+#define RSRT_VIDEO_BT709 0u          /* rsrt_video_params.standard: SDR, sRGB transfer, BT.709 matrix */
+#define RSRT_VIDEO_HDR10 1u          /* Rec.2020 primaries, PQ transfer, BT.2020 NCL matrix; 10 bits only */
+#define RSRT_VIDEO_SEMIPLANAR 0u     /* .layout: a Y plane, then one plane of interleaved Cb, Cr: NV12 at 8 bits, P010 (code << 6) at 10 */
+#define RSRT_VIDEO_PLANAR 1u         /* Y, Cb, Cr planes: I420 at 8 bits, yuv420p10le (code in the low bits) at 10 */
+#define RSRT_VIDEO_LIMITED 0u        /* .range: luma 16 .. 235, chroma 16 .. 240 (times 4 at 10 bits) */
+#define RSRT_VIDEO_FULL 1u           /* 0 .. 2^depth - 1 */
+#define RSRT_VIDEO_SITING_LEFT 0u    /* .siting, H.273 chroma sample location type 0: MPEG-2, H.264, HEVC default */
+#define RSRT_VIDEO_SITING_CENTRE 1u  /* type 1: JPEG, MPEG-1 */
+#define RSRT_VIDEO_SITING_TOPLEFT 2u /* type 2: HDR10, UHD */
+typedef struct rsrt_video_params {
+    uint32_t standard; /* RSRT_VIDEO_BT709 or RSRT_VIDEO_HDR10 */
+    uint32_t depth;    /* 8 or 10 bits a sample; RSRT_VIDEO_HDR10: 10 */
+    uint32_t layout;   /* RSRT_VIDEO_SEMIPLANAR or RSRT_VIDEO_PLANAR */
+    uint32_t range;    /* RSRT_VIDEO_LIMITED or RSRT_VIDEO_FULL */
+    uint32_t siting;   /* RSRT_VIDEO_SITING_* */
+    float dither;      /* 0 .. 1: the dither's amplitude in codes; 0 is the hard quantiser */
+    uint32_t seed;     /* of the dither's noise */
+    uint32_t flags;    /* 0 */
+} rsrt_video_params;
+/* `source` through the video pass (include/rsrt_video.h) into host_out, n_bytes = rsrt_video_planes(width, height, video, ..) of the
+ * source's size.  hdr: NULL with RSRT_VIDEO_BT709; required with RSRT_VIDEO_HDR10, its encoding RSRT_HDR_PQ10, its dither and seed not
+ * looked at.  levels_out: may be non-NULL only with RSRT_VIDEO_HDR10, and then holds the very integers rsrt_display_hdr gives for the
+ * same parameters.  Sources, `local`, bloom_intensity, `colour`, readiness and errors exactly as for rsrt_display_colour_srgb8 and
+ * rsrt_display_hdr (colour->lut_strength > 0 is refused with RSRT_VIDEO_HDR10), and RSRT_ERR_INVALID_ARGUMENT for NULL video, one
+ * rsrt_video_params_ok refuses (an unknown enumerator, a depth other than 8 or 10, RSRT_VIDEO_HDR10 at 8 bits, a dither outside
+ * [0, 1] or not finite, a flag), hdr or levels_out where they do not belong, NULL host_out or another n_bytes.  A refused call writes
+ * neither host_out nor *levels_out.
+ * Rust: pub fn rsrt_display_video(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                 local: *const RsrtLocalParams, bloom_intensity: f32, colour: *const RsrtColourParams,
+ *                                 hdr: *const RsrtHdrParams, video: *const RsrtVideoParams, host_out: *mut c_void, n_bytes: usize,
+ *                                 levels_out: *mut RsrtHdrLevels) -> i32; */
+rsrt_status rsrt_display_video(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                               float bloom_intensity, const rsrt_colour_params *colour, const rsrt_hdr_params *hdr, const rsrt_video_params *video,
+                               void *host_out, size_t n_bytes, rsrt_hdr_levels *levels_out);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

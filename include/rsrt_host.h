@@ -16,6 +16,7 @@
  *   rsrt_camera_(de)serialize Camera::serialize / deserialize (--state)  src/camera.rs:30-89
  *   rsrt_display_srgb8_host  hdr.wgsl aces_tone_map + sRGB surface write  src/shaders/hdr.wgsl:3-22
  *   rsrt_write_png/_pfm      image output (the reference only presents to a window)
+ *   rsrt_y4m_write           video output: the frames of rsrt_display_video as a YUV4MPEG2 sequence
  *   rsrt_synth_environment   stand-in for the two HDRIs the checkout lacks (state.rs:119-122;
  *                            .MISSING_LARGE_BLOBS) — deterministic formula, DESIGN.md §env
  *   rsrt_sky_fill            the procedural daylight sky of include/rsrt_sky.h on the CPU (no reference counterpart;
@@ -105,6 +106,17 @@ void rsrt_display_srgb8_host(const float *sum_rgba, size_t n_pixels, uint32_t sa
 /* Image files: 8-bit RGBA PNG (stored deflate), 32-bit float PFM from a buffer with `stride_floats` per pixel. */
 int rsrt_write_png(const char *path, uint32_t width, uint32_t height, const uint8_t *rgba8);
 int rsrt_write_pfm(const char *path, uint32_t width, uint32_t height, const float *rgb, uint32_t stride_floats);
+/* A frame of rsrt_display_video (include/rsrt.h "video output") into a YUV4MPEG2 file, the uncompressed sequence every encoder and player
+ * reads.  append 0: the file is created and gets the stream header first — W, H, F fps_num:fps_den, Ip, A1:1, the colour space tag
+ * (8 bits: C420mpeg2 for RSRT_VIDEO_SITING_LEFT, C420jpeg for RSRT_VIDEO_SITING_CENTRE; RSRT_VIDEO_SITING_TOPLEFT has no tag of its own
+ * and gets the closest, C420mpeg2, which agrees along x; 10 bits: C420p10, the one 10-bit 4:2:0 tag there is, which names no siting),
+ * XCOLORRANGE=LIMITED or FULL, and the comment fields XRSRT_SITING=LEFT | CENTRE | TOPLEFT and XRSRT_STANDARD=BT709 | HDR10, which say
+ * what the tag cannot — ; append 1: the file must exist, and the caller keeps size, rate and video the same.  Then "FRAME" and the three
+ * planes of planar_frame, n_bytes = rsrt_video_planes(width, height, video, ..).  video->layout must be RSRT_VIDEO_PLANAR: the format has
+ * no interleaved chroma.  0: written; 1: an argument is refused; 2: the file cannot be opened; 3: a write failed. */
+struct rsrt_video_params;
+int rsrt_y4m_write(const char *path, int append, uint32_t width, uint32_t height, uint32_t fps_num, uint32_t fps_den, const struct rsrt_video_params *video,
+                   const void *planar_frame, size_t n_bytes);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 #include "rsrt_colour.h"
 #include "rsrt_finish.h"
 #include "rsrt_hdr.h"
+#include "rsrt_video.h"
 #include "rsrt_dof.h"
 #include "rsrt_motion.h"
 #include "rsrt_exposure.h"
@@ -505,6 +506,26 @@ public:
         check_ctx(rsrt_display_hdr(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &hdr, out.data(), out.size(), levels));
         return out;
     }
+    // -- video output (rsrt.h "video output"): one device, like the denoiser ----------------------------------------------
+    static rsrt_video_params video_defaults()
+    {
+        return rsrt_video_params{RSRT_VIDEO_DEFAULT_STANDARD, RSRT_VIDEO_DEFAULT_DEPTH, RSRT_VIDEO_DEFAULT_LAYOUT, RSRT_VIDEO_DEFAULT_RANGE, RSRT_VIDEO_DEFAULT_SITING,
+                                 RSRT_VIDEO_DEFAULT_DITHER, RSRT_VIDEO_DEFAULT_SEED, RSRT_VIDEO_DEFAULT_FLAGS};
+    }
+    // display_colour's chain with its LUT (video.standard RSRT_VIDEO_BT709: hdr NULL) or display_hdr's (RSRT_VIDEO_HDR10: hdr given, no LUT) as
+    // a Y'CbCr 4:2:0 frame: the bytes rsrt_video_planes lays out for the source's size.  levels: NULL, or (RSRT_VIDEO_HDR10) where the frame's
+    // content light levels go.  lut_strength < 0: 1 with a LUT, 0 without or with hdr
+    std::vector<uint8_t> display_video(const rsrt_video_params &video = video_defaults(), const rsrt_hdr_params *hdr = nullptr, rsrt_hdr_levels *levels = nullptr,
+                                       uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const float *white = nullptr, float lut_strength = -1.0f,
+                                       const rsrt_local_params *local = nullptr, float bloom_intensity = 0.0f)
+    {
+        const rsrt_colour_params c = colour_params(white, hdr && lut_strength < 0.0f ? 0.0f : lut_strength);
+        uint32_t w = 0, h = 0;
+        source_size(source, &w, &h);
+        std::vector<uint8_t> out(rsrt_video_planes(w, h, &video, nullptr));
+        check_ctx(rsrt_display_video(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, hdr, &video, out.data(), out.size(), levels));
+        return out;
+    }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------
     static rsrt_dof_params dof_defaults() { return rsrt_dof_params{RSRT_DOF_FOCUS_DISTANCE, RSRT_DOF_APERTURE, RSRT_DOF_RADIUS, RSRT_DOF_FLAGS}; }
     // the lens image of `source` (RSRT_EXPOSURE_MEAN .. _UPSAMPLED) seen through the state's camera, built on the device; a
@@ -819,6 +840,22 @@ private:
         }
         const bool up = source == RSRT_EXPOSURE_UPSAMPLED;
         return (size_t)(up ? guide_width_ : width_) * (up ? guide_height_ : height_);
+    }
+    // ... and its width and height (a fogged image is of the guide's size when that is the size the last fog() composed, else of the state's own)
+    void source_size(uint32_t source, uint32_t *w, uint32_t *h)
+    {
+        if (source == RSRT_EXPOSURE_MOTION) {
+            check_ctx(rsrt_motion_download(context(0), nullptr, 0, w, h));
+            return;
+        }
+        if (source == RSRT_EXPOSURE_LENS) {
+            check_ctx(rsrt_dof_download(context(0), nullptr, 0, w, h));
+            return;
+        }
+        const size_t own = (size_t)width_ * height_, guide = (size_t)guide_width_ * guide_height_;
+        const bool up = source == RSRT_EXPOSURE_UPSAMPLED || (source == RSRT_EXPOSURE_FOG && fog_pixels_ == guide && guide != own);
+        *w = up ? guide_width_ : width_;
+        *h = up ? guide_height_ : height_;
     }
     // a display into a vector: display(context, source, sample_count, args..., bytes, their number), RGBA8 of the source's own size
     template <class Display, class... Args>

@@ -1970,3 +1970,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_fog.h"
 #include "rt_finish.h"
 #include "rt_hdr.h"
+#include "rt_video.h"

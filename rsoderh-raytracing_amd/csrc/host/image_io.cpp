@@ -9,6 +9,7 @@
 //                          [pos.xyz, yaw, pitch, fov_y] as standard base64 (the --state flag, src/cli.rs:39-43).
 //  rsrt_write_png / rsrt_write_pfm
 //                          image output (the reference only presents to a window).
+//  rsrt_y4m_write          video output: rsrt_display_video's planar frames as a YUV4MPEG2 sequence.
 //  rsrt_display_srgb8_host the display transform of include/rsrt_tonemap.h on the CPU, for hosts that
 //                          downloaded the f32 sums.
 #include <cmath>
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../../include/rsrt_host.h"
+#include "../../../include/rsrt_video.h"
 #include "../../../include/rsrt_tonemap.h"
 
 namespace {
@@ -201,6 +203,27 @@ int rsrt_write_pfm(const char *path, uint32_t width, uint32_t height, const floa
     }
     std::fclose(f);
     return 0;
+}
+
+// YUV4MPEG2: a text header line, then "FRAME\n" and the Y, Cb, Cr planes of every frame, rows tightly packed, 10-bit samples as
+// little-endian uint16 with the code in the low bits: the very bytes of a RSRT_VIDEO_PLANAR frame
+int rsrt_y4m_write(const char *path, int append, uint32_t width, uint32_t height, uint32_t fps_num, uint32_t fps_den, const rsrt_video_params *video,
+                   const void *planar_frame, size_t n_bytes)
+{
+    if (!path || !video || !planar_frame || fps_num == 0 || fps_den == 0 || !rsrt_video_params_ok(video) || video->layout != RSRT_VIDEO_PLANAR) return 1;
+    const size_t want = rsrt_video_planes(width, height, video, nullptr);
+    if (want == 0 || n_bytes != want) return 1;
+    FILE *f = std::fopen(path, append ? "r+b" : "wb"); // ("r+b": an append to a file that is not there fails instead of writing frames without a header)
+    if (!f) return 2;
+    bool ok = !append || std::fseek(f, 0, SEEK_END) == 0;
+    if (ok && !append) {
+        static const char *const sitings[] = {"LEFT", "CENTRE", "TOPLEFT"};
+        const char *const tag = video->depth == 10u ? "420p10" : (video->siting == RSRT_VIDEO_SITING_CENTRE ? "420jpeg" : "420mpeg2");
+        ok = std::fprintf(f, "YUV4MPEG2 W%u H%u F%u:%u Ip A1:1 C%s XCOLORRANGE=%s XRSRT_SITING=%s XRSRT_STANDARD=%s\n", width, height, fps_num, fps_den, tag,
+                          video->range == RSRT_VIDEO_FULL ? "FULL" : "LIMITED", sitings[video->siting], video->standard == RSRT_VIDEO_HDR10 ? "HDR10" : "BT709") > 0;
+    }
+    ok = ok && std::fputs("FRAME\n", f) >= 0 && std::fwrite(planar_frame, 1, n_bytes, f) == n_bytes;
+    return (std::fclose(f) == 0 && ok) ? 0 : 3;
 }
 
 void rsrt_display_srgb8_host(const float *sum_rgba, size_t n_pixels, uint32_t sample_total, uint8_t *out_rgba8)

@@ -46,6 +46,8 @@ def lib():
         L.rsrt_write_png.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.rsrt_write_pfm.restype = C.c_int
         L.rsrt_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
+        L.rsrt_y4m_write.restype = C.c_int
+        L.rsrt_y4m_write.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_srgb8_host.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
@@ -267,6 +269,17 @@ def write_png(path, rgba8):
     assert rgba8.ndim == 3 and rgba8.shape[2] == 4
     if lib().rsrt_write_png(os.fsencode(path), rgba8.shape[1], rgba8.shape[0], _p(rgba8)) != 0:
         raise OSError("rsrt_write_png failed: " + str(path))
+
+
+def write_y4m(path, frame, fps=(30, 1), append=False):
+    """rsrt_y4m_write: a planar State.display_video frame (layout "i420" or "i420p10") into a YUV4MPEG2 file — created with its header, or
+    appended to with append=True.  fps: (numerator, denominator)."""
+    data = np.ascontiguousarray(frame.data, np.uint8)
+    rc = lib().rsrt_y4m_write(os.fsencode(path), 1 if append else 0, frame.width, frame.height, fps[0], fps[1], C.byref(frame.params), _p(data), data.nbytes)
+    if rc == 1:
+        raise ValueError("rsrt_y4m_write: want a planar frame of the size's byte count and a frame rate above 0")
+    if rc != 0:
+        raise OSError("rsrt_y4m_write failed: " + str(path))
 
 
 def write_pfm(path, rgb):

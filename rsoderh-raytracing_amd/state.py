@@ -46,7 +46,7 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
             "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8", "rsrt_display_finished_srgb8",
-            "rsrt_display_hdr"]
+            "rsrt_display_hdr", "rsrt_display_video"]
 
 
 class RsrtError(RuntimeError):
@@ -230,6 +230,64 @@ def hdr_unpack_pq10(words):
     """The 10-bit codes of RSRT_HDR_PQ10 words (R | G << 10 | B << 20 | 3 << 30): [H, W] uint32 -> [H, W, 3] uint16."""
     w = np.asarray(words, np.uint32)
     return np.stack([(w >> np.uint32(10 * c)) & np.uint32(1023) for c in range(3)], axis=-1).astype(np.uint16)
+
+
+# the video pass (include/rsrt.h "video output", include/rsrt_video.h): its enumerators, its defaults, its parameters and its frame
+VIDEO_BT709, VIDEO_HDR10 = 0, 1
+VIDEO_SEMIPLANAR, VIDEO_PLANAR = 0, 1
+VIDEO_LIMITED, VIDEO_FULL = 0, 1
+VIDEO_SITING_LEFT, VIDEO_SITING_CENTRE, VIDEO_SITING_TOPLEFT = 0, 1, 2  # H.273 chroma sample location types
+VIDEO_STANDARDS = {"bt709": VIDEO_BT709, "hdr10": VIDEO_HDR10}
+VIDEO_LAYOUTS = {"nv12": (VIDEO_SEMIPLANAR, 8), "i420": (VIDEO_PLANAR, 8), "p010": (VIDEO_SEMIPLANAR, 10), "i420p10": (VIDEO_PLANAR, 10)}  # (layout, depth)
+VIDEO_RANGES = {"limited": VIDEO_LIMITED, "full": VIDEO_FULL}
+VIDEO_SITINGS = {"left": VIDEO_SITING_LEFT, "centre": VIDEO_SITING_CENTRE, "topleft": VIDEO_SITING_TOPLEFT}
+VIDEO_DEFAULTS = {"standard": "bt709", "depth": 8, "layout": "nv12", "range": "limited", "siting": "left", "dither": 0.0, "seed": 0, "flags": 0}
+
+
+class VideoParams(C.Structure):
+    _fields_ = [("standard", C.c_uint32), ("depth", C.c_uint32), ("layout", C.c_uint32), ("range", C.c_uint32), ("siting", C.c_uint32),
+                ("dither", C.c_float), ("seed", C.c_uint32), ("flags", C.c_uint32)]
+
+
+def video_planes(width, height, depth=8, layout=VIDEO_SEMIPLANAR):
+    """rsrt_video_planes: (the frame's byte count, [(offset, pitch, width, height) of each plane, in bytes and samples]).  layout: a
+    VIDEO_* enumerator or a name of VIDEO_LAYOUTS, whose depth then counts.  The interleaved plane's width counts both of a pair."""
+    if layout in VIDEO_LAYOUTS:
+        layout, depth = VIDEO_LAYOUTS[layout]
+    if width < 1 or height < 1 or depth not in (8, 10) or layout not in (VIDEO_SEMIPLANAR, VIDEO_PLANAR):
+        raise ValueError("video_planes: want a size of at least 1 x 1, depth 8 or 10, a known layout")
+    cw, ch, b = (width + 1) // 2, (height + 1) // 2, 2 if depth == 10 else 1
+    sizes = [(width, height), (2 * cw, ch)] if layout == VIDEO_SEMIPLANAR else [(width, height), (cw, ch), (cw, ch)]
+    planes, at = [], 0
+    for w, h in sizes:
+        planes.append((at, w * b, w, h))
+        at += w * b * h
+    return at, planes
+
+
+class VideoFrame:
+    """A frame of State.display_video: `data` the bytes as laid out (uint8 [n]: what an encoder or rsrt_y4m_write takes), `y` [H, W], `cb`,
+    `cr` [ceil(H / 2), ceil(W / 2)] numpy views of the codes (a copy with the shift removed for P010, whose words are code << 6), `width`,
+    `height` and `params` (the VideoParams of the call)."""
+
+    def __init__(self, data, width, height, params):
+        self.data, self.width, self.height, self.params = data, width, height, params
+
+    def _planes(self):
+        p = self.params
+        _, planes = video_planes(self.width, self.height, p.depth, p.layout)
+        t = np.dtype("<u2") if p.depth == 10 else np.dtype(np.uint8)
+        views = [self.data[at:at + pitch * h].view(t).reshape(h, w) for at, pitch, w, h in planes]
+        if p.layout == VIDEO_SEMIPLANAR:
+            c = views[1].reshape(views[1].shape[0], -1, 2)
+            views = [views[0], c[..., 0], c[..., 1]]
+            if p.depth == 10:
+                views = [v >> 6 for v in views]
+        return views
+
+    y = property(lambda self: self._planes()[0])
+    cb = property(lambda self: self._planes()[1])
+    cr = property(lambda self: self._planes()[2])
 
 
 # the procedural daylight sky (include/rsrt.h rsrt_environment_sky, include/rsrt_sky.h): its defaults (RSRT_SKY_*) and its parameters.
@@ -459,6 +517,8 @@ def lib():
         L.rsrt_display_colour_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_finished_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_hdr.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_display_video.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                         C.c_void_p]
         _lib = L
     return _lib
 
@@ -1102,6 +1162,49 @@ class State:
                                              C.byref(lv) if levels else None), "rsrt_display_hdr")
         img = out.view(np.float16) if enc == HDR_SCRGB16F else out
         return (img, {"max_cll": lv.max_cll, "max_fall": lv.max_fall, "max_q": lv.max_q, "sum_q": lv.sum_q}) if levels else img
+
+    # -- video output (include/rsrt.h "video output") --------------------------------------------------------
+    def display_video(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
+                      standard="bt709", depth=None, layout=None, range=None, siting=None, dither=None, seed=None, paper_white=None, peak=None, knee=None,
+                      levels=False, sample_total=None, **params):
+        """rsrt_display_video: `source` as a Y'CbCr 4:2:0 frame.  standard "bt709": display_colour_srgb8's chain (whose arguments `source`
+        .. `bloom_intensity`, sample_total and params are) with the LUT, under the sRGB transfer and the BT.709 matrix; "hdr10":
+        display_hdr's (paper_white, peak, knee: HDR_DEFAULTS where None; no LUT: lut_strength must be None or 0) as Rec.2020 PQ under the
+        BT.2020 matrix, 10 bits only.  layout "nv12", "i420" (8 bits), "p010", "i420p10" (10 bits) or a VIDEO_* enumerator with `depth`
+        (None: the layout's, else VIDEO_DEFAULTS'; hdr10's default layout is "p010"); range "limited" or "full"; siting "left", "centre"
+        or "topleft"; the quantiser dithered at `dither` with the noise of `seed` (an integer of any size or sign, of which the low 32
+        bits are used).  Returns a VideoFrame; levels=True (hdr10): (frame, display_hdr's levels dict)."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        d = VIDEO_DEFAULTS
+        std = VIDEO_STANDARDS.get(standard, standard)
+        if layout is None:
+            layout = "p010" if std == VIDEO_HDR10 and depth in (None, 10) else VIDEO_LAYOUTS[d["layout"]][0]
+        lay, lay_depth = VIDEO_LAYOUTS.get(layout, (layout, None))
+        if depth is None:
+            depth = d["depth"] if lay_depth is None else lay_depth
+        elif lay_depth is not None and depth != lay_depth:
+            raise ValueError("display_video: layout %r is %d bits a sample, not %d" % (layout, lay_depth, depth))
+        v = VideoParams(std, depth, lay, VIDEO_RANGES.get(d["range"] if range is None else range, range), VIDEO_SITINGS.get(d["siting"] if siting is None else siting, siting),
+                        d["dither"] if dither is None else dither, (d["seed"] if seed is None else int(seed)) & 0xFFFFFFFF, d["flags"])
+        hdr10 = std == VIDEO_HDR10
+        c = self._colour_params(white, 0.0 if hdr10 and lut_strength is None else lut_strength)
+        h = HDR_DEFAULTS
+        hp = HdrParams(h["paper_white"] if paper_white is None else paper_white, h["peak"] if peak is None else peak, h["knee"] if knee is None else knee,
+                       0.0, 0, HDR_PQ10, 0, 0) if hdr10 else None
+        if not hdr10 and not (paper_white is None and peak is None and knee is None):
+            raise ValueError("display_video: paper_white, peak and knee belong to standard \"hdr10\"")
+        height, width = self._source_shape(source)
+        try:
+            n = video_planes(width, height, depth, lay)[0]
+        except ValueError:
+            n = 1  # (the library names what is wrong)
+        out = np.empty(n, np.uint8)
+        lv = HdrLevels()
+        self._check(self._L.rsrt_display_video(self._ctx, *self._source_total(source, sample_total), self._exposure_or_one(exposure),
+                                               C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(hp) if hp is not None else None,
+                                               C.byref(v), _p(out), out.nbytes, C.byref(lv) if levels else None), "rsrt_display_video")
+        frame = VideoFrame(out, width, height, v)
+        return (frame, {"max_cll": lv.max_cll, "max_fall": lv.max_fall, "max_q": lv.max_q, "sum_q": lv.sum_q}) if levels else frame
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------
     def depth_of_field(self, source="mean", focus_distance=None, aperture=None, max_radius=None, sample_total=None, stream=None, out_ptr=None):
