@@ -769,7 +769,13 @@ rsrt_status rsrt_motion_reset(rsrt_context *ctx); /* drops the motion image */
  * Nothing here writes the accumulator, the AOV buffer, the guide or any other image of the context.  A refused call launches nothing
  * and leaves records and image as they were.
  * rsrt_fog_params (include/rsrt_types.h) defaults: density 0.05, albedo 1, anisotropy 0.6, ambient 0, max_distance 50, steps 16,
- * flags RSRT_FOG_JITTER (RSRT_FOG_* in include/rsrt_fog.h); the light has no default: rsrt_fog_light_from_sky there gives a sky's sun. */
+ * flags RSRT_FOG_JITTER (RSRT_FOG_* in include/rsrt_fog.h); the light has no default: rsrt_fog_light_from_sky there gives a sky's sun.
+ * rsrt_fog_params_ok (there) accepts each field within the range rsrt_types.h gives it, and of those sets the ones for which one
+ * sample stays finite ("Finiteness" in rsrt_fog.h): with S = (s * phase_hi) * max light_irradiance + s * max ambient, s = density *
+ * max albedo, phase_hi the phase function at cos = +-1 with q's lower bound, and W_hi = min(max_distance, delta_hi + 1 / (density +
+ * density^2 * delta_hi / 2)), delta_hi = max_distance / steps, it wants steps * S and S * W_hi at most 0.99 of the largest float.  The
+ * largest irradiance beside density 1e6, or beside |anisotropy| 0.95 at density 1, is refused; either alone is not.  Every record of
+ * an accepted set is finite sample by sample; summed over very many samples it may reach +inf, never NaN. */
 enum { RSRT_EXPOSURE_FOG = 6 }; /* the last rsrt_fog_apply output: a source of the lens, the shutter, the meters, bloom, local exposure and the displays */
 /* Adds the fog of samples [sample_begin, sample_begin + sample_count) of a width x height frame seen through `camera` to the fog
  * records.  Asynchronous on hip_stream, NULL = the context's stream, ordered after everything enqueued so far.

@@ -33,9 +33,25 @@
  * infinity altogether, so the light reaches every unoccluded point at full strength; light_irradiance is what arrives.  Nor is there
  * multiple scattering, a height or density field, or fog inside the integrator: surfaces are lit as if the air were clear.
  *
- * Every quantity is finite for every parameter set rsrt_fog_params_ok accepts and a unit ray direction: q >= (1 - |g|)^2 - 2 |g| 1e-3
- * > 1.3e-3 for |g| <= 0.95 and a light_dir within the accepted length, sigma' * t <= sigma' * max_distance (1 + 2^-22), which
- * rsrt_fog_params_ok holds finite, and rsrt_sky_exp2 returns exactly 0 below its clamp.
+ * Finiteness.  One sample's every quantity — q, phase, S_sun, S_amb, T_i, the running sum, inscatter, transmittance — is finite for
+ * every parameter set rsrt_fog_params_ok accepts and a unit ray direction.  Each field within its own range is not enough (S_sun
+ * overflows to inf for density 1e6 and the largest irradiance, and T_i is exactly 0 beyond rsrt_sky_exp2's clamp: 0 * inf), so
+ * rsrt_fog_params_ok also bounds the products, from the expressions above:
+ *   sigma' t  <= sigma' * max_distance (1 + 2^-22), held to half the largest float; rsrt_sky_exp2 returns exactly 0 below its clamp.
+ *   q         |d . light_dir| <= 1.001 for a unit d and a light_dir within the accepted length (len <= 1.0005), so
+ *             q >= q_lo = ((1 + g g) - 2 |g|) - (2 |g|) * 1e-3,  which is > 5.9e-4 for |g| <= 0.95.
+ *   phase     <= phase_hi = phase_norm / (q_lo * rsrt_sqrtf(q_lo)):  the phase at cos = +-1 with q's lower bound in place of q.
+ *   source    S_sun[c] + S_amb[c] <= S = (s * phase_hi) * max_c light_irradiance[c] + s * max_c ambient[c],  s = density * max_c albedo[c].
+ *   sum       T_i <= 1, so sum[c] <= (float)steps * S: also what a hit at t = 0 (delta = 0, every T_i = 1) multiplies by 0.
+ *   inscatter sum[c] * delta <= S * W with W = delta * (T_0 + T_1 + ...), delta = L / steps <= delta_hi = max_distance / (float)steps.
+ *             W <= steps * delta = L <= max_distance.  And T_0 <= 1, while for i >= 1, xi >= 0 and the convex e^(-sigma t) the term
+ *             delta e^(-sigma i delta) is at most the integral over [(i - 1/2) delta, (i + 1/2) delta], so the terms after the first sum
+ *             to at most e^(-sigma delta / 2) / sigma <= 1 / (sigma + sigma^2 delta / 2)  (e^-x <= 1 / (1 + x)); the bound grows with
+ *             delta, so  W <= W_hi = min(max_distance, delta_hi + 1 / (density + (density * density) * (0.5 * delta_hi))).
+ * rsrt_fog_params_ok requires (float)steps * S <= RSRT_FOG_HEADROOM * largest float and S * W_hi <= the same; the one per cent of
+ * headroom is far above what the f32 roundings of the march (64 terms) and rsrt_sky_exp2's 2^-17 can add.  (density 0: W_hi =
+ * max_distance, S = 0.)  A record is a sum over samples of such non-negative finite terms: over very many samples it may overflow, and
+ * then it is +inf, never NaN; rsrt_fog_apply then shows +inf in that channel.
  */
 #ifndef RSRT_FOG_H
 #define RSRT_FOG_H
@@ -62,6 +78,7 @@
 #define RSRT_FOG_MAX_ANISOTROPY 0.95f
 #define RSRT_FOG_UNIT_TOLERANCE 1.0e-3f
 #define RSRT_FOG_LARGEST 3.40282346638528859812e38f /* the largest finite float */
+#define RSRT_FOG_HEADROOM 0.99f /* of it: what the bounds of one sample's sum and inscatter may reach ("Finiteness" above) */
 
 /* everything that depends on the parameters alone: rsrt_fog_prepare makes it once on the host, the kernel takes it by value */
 typedef struct rsrt_fog_constants {
@@ -82,6 +99,34 @@ typedef struct rsrt_fog_constants {
 RSRT_HD int rsrt_fog_amount(float x) { return x >= 0.0f && x <= RSRT_FOG_LARGEST; }
 RSRT_HD int rsrt_fog_unit_interval(float x) { return x >= 0.0f && x <= 1.0f; }
 
+RSRT_HD float rsrt_fog_max3(const float v[3])
+{
+    const float m = v[0] > v[1] ? v[0] : v[1];
+    return m > v[2] ? m : v[2];
+}
+/* S of "Finiteness" above: no channel's S_sun + S_amb exceeds it.  |anisotropy| <= RSRT_FOG_MAX_ANISOTROPY is the caller's to check */
+RSRT_HD float rsrt_fog_source_bound(const rsrt_fog_params *p)
+{
+    const float g = p->anisotropy, two_a = 2.0f * (g < 0.0f ? -g : g);
+    const float q_lo = ((1.0f + g * g) - two_a) - two_a * RSRT_FOG_UNIT_TOLERANCE;
+    const float phase_hi = ((1.0f - g * g) / (4.0f * RSRT_PIF)) / (q_lo * rsrt_sqrtf(q_lo));
+    const float s = p->density * rsrt_fog_max3(p->albedo);
+    return (s * phase_hi) * rsrt_fog_max3(p->light_irradiance) + s * rsrt_fog_max3(p->ambient);
+}
+/* W_hi of "Finiteness" above: delta times the sum of a march's transmittances does not exceed it */
+RSRT_HD float rsrt_fog_length_bound(const rsrt_fog_params *p)
+{
+    const float delta_hi = p->max_distance / (float)p->steps;
+    const float w = delta_hi + 1.0f / (p->density + (p->density * p->density) * (0.5f * delta_hi));
+    return w < p->max_distance ? w : p->max_distance;
+}
+/* one sample's running sum and inscatter stay finite; the ranges of the single fields are the caller's to check first */
+RSRT_HD int rsrt_fog_sample_finite(const rsrt_fog_params *p)
+{
+    const float S = rsrt_fog_source_bound(p), limit = RSRT_FOG_HEADROOM * RSRT_FOG_LARGEST;
+    return (float)p->steps * S <= limit && S * rsrt_fog_length_bound(p) <= limit;
+}
+
 RSRT_HD int rsrt_fog_params_ok(const rsrt_fog_params *p)
 {
     const float len2 = (p->light_dir[0] * p->light_dir[0] + p->light_dir[1] * p->light_dir[1]) + p->light_dir[2] * p->light_dir[2];
@@ -92,7 +137,7 @@ RSRT_HD int rsrt_fog_params_ok(const rsrt_fog_params *p)
            rsrt_fog_amount(p->light_irradiance[1]) && rsrt_fog_amount(p->light_irradiance[2]) && rsrt_fog_amount(p->ambient[0]) &&
            rsrt_fog_amount(p->ambient[1]) && rsrt_fog_amount(p->ambient[2]) && p->max_distance > 0.0f && p->max_distance <= RSRT_FOG_LARGEST &&
            (p->density * RSRT_SKY_LOG2E) * p->max_distance <= 0.5f * RSRT_FOG_LARGEST && p->steps >= 1u && p->steps <= RSRT_FOG_MAX_STEPS &&
-           (p->flags & ~RSRT_FOG_JITTER) == 0u;
+           (p->flags & ~RSRT_FOG_JITTER) == 0u && rsrt_fog_sample_finite(p);
 }
 
 /* p must pass rsrt_fog_params_ok */

@@ -119,7 +119,8 @@ typedef struct rsrt_sky_params {
 
 /* The participating medium of the fog pass (rsrt_fog_render in rsrt.h; the model is include/rsrt_fog.h): a homogeneous medium lit by
  * single scattering from one directional light plus a constant isotropic ambient term.  68 bytes.  Defaults: RSRT_FOG_* in
- * include/rsrt_fog.h. */
+ * include/rsrt_fog.h.  Beside the range of each field, rsrt_fog_params_ok there bounds the products density * albedo * phase *
+ * light_irradiance and density * albedo * ambient, times steps and times the march's length, so that one sample stays finite. */
 typedef struct rsrt_fog_params {
     float density;             /* the extinction coefficient sigma_t per scene unit: finite, 0 .. 1e6, and density * max_distance finite */
     float albedo[3];           /* the single-scattering albedo, each in [0, 1] */

@@ -167,7 +167,9 @@ rsrt_status rsrt_fog_render(rsrt_context *ctx, const rsrt_camera *camera, uint32
     if (!rsrt_fog_params_ok(params))
         return fail(ctx, RSRT_ERR_INVALID_ARGUMENT,
                     "fog_render: want density in [0, 1e6] with density * max_distance finite, albedo in [0, 1], |anisotropy| <= 0.95, light_dir a unit "
-                    "vector, light_irradiance and ambient finite and >= 0, max_distance finite and > 0, steps in 1..%u, flags 0 or RSRT_FOG_JITTER",
+                    "vector, light_irradiance and ambient finite and >= 0, max_distance finite and > 0, steps in 1..%u, flags 0 or RSRT_FOG_JITTER, "
+                    "and one sample's sum and inscatter finite (rsrt_fog.h: density * albedo * (phase * light_irradiance + ambient), times steps and "
+                    "times the march's length)",
                     RSRT_FOG_MAX_STEPS);
     if (width == 0 || height == 0 || (uint64_t)width * height > 0x7fffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "bad resolution %ux%u", width, height);
     if ((uint64_t)sample_begin + sample_count > 0xffffffffull) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "sample range overflows u32");

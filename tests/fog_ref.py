@@ -18,6 +18,7 @@ MAX_DENSITY = F(1.0e6)
 MAX_ANISOTROPY = F(0.95)
 UNIT_TOLERANCE = F(1.0e-3)
 LARGEST = np.finfo(F).max
+HEADROOM = F(0.99)
 LOG2E = sky_ref.LOG2E
 PIF = sky_ref.PIF
 DEFAULTS = {"density": 0.05, "albedo": (1.0, 1.0, 1.0), "anisotropy": 0.6, "light_dir": (0.0, 1.0, 0.0), "light_irradiance": (1.0, 1.0, 1.0),
@@ -45,6 +46,40 @@ def unit(v):
     return tuple(float(x) for x in (v / np.sqrt((v * v).sum())).astype(F))
 
 
+def source_bound(p):
+    """rsrt_fog_source_bound: S, which no channel's S_sun + S_amb exceeds."""
+    with np.errstate(all="ignore"):
+        g = F(p["anisotropy"])
+        two_a = F(F(2) * (-g if g < F(0) else g))
+        q_lo = F(F(F(F(1) + F(g * g)) - two_a) - F(two_a * UNIT_TOLERANCE))
+        phase_hi = F(F(F(F(1) - F(g * g)) / F(F(4) * PIF)) / F(q_lo * np.sqrt(q_lo)))
+        s = F(F(p["density"]) * max3(p["albedo"]))
+        return F(F(F(s * phase_hi) * max3(p["light_irradiance"])) + F(s * max3(p["ambient"])))
+
+
+def max3(v):
+    """rsrt_fog_max3."""
+    v = np.asarray(v, F)
+    m = v[0] if v[0] > v[1] else v[1]
+    return m if m > v[2] else v[2]
+
+
+def length_bound(p):
+    """rsrt_fog_length_bound: W_hi, which delta times the sum of a march's transmittances does not exceed."""
+    with np.errstate(all="ignore"):
+        den, dist = F(p["density"]), F(p["max_distance"])
+        delta_hi = F(dist / F(p["steps"]))
+        w = F(delta_hi + F(F(1) / F(den + F(F(den * den) * F(F(0.5) * delta_hi)))))
+        return w if w < dist else dist
+
+
+def sample_finite(p):
+    """rsrt_fog_sample_finite."""
+    with np.errstate(all="ignore"):
+        S, limit = source_bound(p), F(HEADROOM * LARGEST)
+        return bool(F(F(p["steps"]) * S) <= limit and F(S * length_bound(p)) <= limit)
+
+
 def params_ok(p):
     """rsrt_fog_params_ok."""
     with np.errstate(all="ignore"):
@@ -55,7 +90,7 @@ def params_ok(p):
         return bool(F(0) <= den <= MAX_DENSITY and all(F(0) <= F(a) <= F(1) for a in p["albedo"]) and -MAX_ANISOTROPY <= g <= MAX_ANISOTROPY and
                     -UNIT_TOLERANCE <= off <= UNIT_TOLERANCE and all(amount(v) for v in p["light_irradiance"]) and all(amount(v) for v in p["ambient"]) and
                     F(0) < dist <= LARGEST and F(F(den * LOG2E) * dist) <= F(F(0.5) * LARGEST) and 1 <= p["steps"] <= MAX_STEPS and
-                    (p["flags"] & ~JITTER) == 0)
+                    (p["flags"] & ~JITTER) == 0 and sample_finite(p))
 
 
 def prepare(p):

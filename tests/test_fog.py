@@ -144,6 +144,11 @@ def test_params_ok_accepts_and_rejects(host):
             {"light_dir": (1.0, 0.0, 0.0)}, {"light_dir": (1.0004, 0.0, 0.0)}, {"light_dir": (0.0, -0.9996, 0.0)}, {"light_irradiance": 0.0},
             {"light_irradiance": 3.0e38}, {"ambient": 3.0e38}, {"max_distance": 1.0e-30}, {"max_distance": 3.0e38}, {"steps": 1}, {"steps": 64}, {"flags": 0},
             {"flags": 1}, {"density": 1.0e6, "max_distance": 1.0e30}]
+    largest = float(fog_ref.LARGEST)
+    # one sample's sum and inscatter must stay finite (rsrt_fog.h "Finiteness"): the nearest accepted neighbours of the sets refused below
+    good += [{"density": 1.0e6, "light_irradiance": 2.6e31}, {"density": 1.0e6, "ambient": 2.1e31}, {"density": 1.0, "anisotropy": 0.95, "light_irradiance": 3.9e34},
+             {"density": 0.0768, "light_irradiance": largest}, {"density": 0.0197, "ambient": largest}, {"density": 0.0, "light_irradiance": largest, "ambient": largest},
+             {"albedo": 0.0, "density": 1.0e6, "light_irradiance": largest, "ambient": largest}, {"ambient": 3.0e38, "steps": 16}]
     bad = [{"density": v} for v in (-1e-30, -1.0, 1.0001e6, nan, inf, -inf)]
     bad += [{"albedo": v} for v in (-0.001, 1.001, nan, inf, (0.5, 0.5, 1.5), (nan, 0.5, 0.5), (0.5, -1.0, 0.5))]
     bad += [{"anisotropy": v} for v in (0.951, -0.951, 1.0, nan, inf)]
@@ -154,6 +159,9 @@ def test_params_ok_accepts_and_rejects(host):
     bad += [{"steps": v} for v in (0, 65, 0xffffffff)]
     bad += [{"flags": v} for v in (2, 3, 0x80000000, 0x80000001)]
     bad += [{"density": 1.0e6, "max_distance": 3.0e38}, {"density": 2.0, "max_distance": 3.0e38}]  # density * max_distance must stay finite
+    bad += [{"density": 1.0e6, "light_irradiance": largest}, {"density": 1.0e6, "ambient": largest}, {"density": 1.0, "anisotropy": 0.95, "light_irradiance": largest},
+            {"density": 1.0e6, "light_irradiance": 2.7e31}, {"density": 1.0e6, "ambient": 2.2e31}, {"density": 1.0, "anisotropy": 0.95, "light_irradiance": 4.0e34},
+            {"density": 0.077, "light_irradiance": largest}, {"density": 0.0199, "ambient": largest}, {"ambient": 3.0e38, "steps": 1}]
     for kw in good:
         p = fog_ref.params(**kw)
         assert host.fog_params_ok(C.byref(c_params(p))) and fog_ref.params_ok(p), kw

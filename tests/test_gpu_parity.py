@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import coop_lists as M
+import foreign_trees
 import oracle
 import util
 import rsoderh_raytracing_amd as R
@@ -480,15 +481,7 @@ def test_bvh_whose_boxes_do_not_nest_keeps_the_tree_walk(big_env):
     """The flat small-scene loop is only valid when every child box lies inside its parent's.  Shrink an interior
     node's box so that its children stick out: the reference (and the oracle) then skip that subtree for rays that
     miss the shrunken box although they would hit a child — and so must the product."""
-    base = R.Scene.load_toml(util.scene_path("default"))
-    nodes = base.bvh_nodes.copy()
-    interior = [i for i in range(1, len(nodes)) if nodes[i]["primitives_len"] == 0]
-    i = interior[0]
-    mid = (nodes[i]["bounds_min"] + nodes[i]["bounds_max"]) * np.float32(0.5)
-    nodes[i]["bounds_min"] = mid + (nodes[i]["bounds_min"] - mid) * np.float32(0.5)
-    nodes[i]["bounds_max"] = mid + (nodes[i]["bounds_max"] - mid) * np.float32(0.5)
-    sc = R.Scene(base.materials, base.spheres, base.plane_descs, base.vertices, base.normals, base.triangles, base.camera_desc,
-                 planes=base.planes, primitives=base.primitives, bvh_nodes=nodes, bvh_depth=base.bvh_depth)
+    base, sc = foreign_trees.base(), foreign_trees.shrunken_box_scene()
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
     intact, _ = oracle.render(util.oracle_scene(base), util.oracle_env(big_env), base.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
     assert not np.array_equal(util.bits(ref), util.bits(intact))  # the shrunken box does change the picture
@@ -512,34 +505,7 @@ def test_twin_records_in_different_leaves_tie_by_visiting_order(traversal, big_e
         monkeypatch.setenv("RSRT_FLAT", "0")
     if traversal.endswith("q100"):
         monkeypatch.setenv("RSRT_FLAT_QUORUM", "100")
-    base = R.Scene.load_toml(util.scene_path("default"))
-    nodes, prims = base.bvh_nodes.copy(), base.primitives
-    k = next(i for i, p in enumerate(prims) if int(p["primitive_type"]) == 0)  # a sphere record ...
-    src = int(prims[k]["index"])
-    last = max((i for i in range(len(nodes)) if nodes[i]["primitives_len"] > 0), key=lambda i: int(nodes[i]["primitives_or_second_child_index"]))
-    assert not (int(nodes[last]["primitives_or_second_child_index"]) <= k < int(nodes[last]["primitives_or_second_child_index"]) + int(nodes[last]["primitives_len"]))  # ... of another leaf
-    spheres = np.zeros(len(base.spheres) + 1, T.SPHERE)  # (np.concatenate would drop the struct's padding)
-    spheres[:-1] = base.spheres
-    spheres[-1] = base.spheres[src]
-    spheres[-1]["material_id"] = (int(spheres[src]["material_id"]) + 1) % len(base.materials)
-    new_prims = np.concatenate([prims, np.array([(0, len(spheres) - 1)], prims.dtype)])
-    lo = np.asarray(spheres[-1]["pos"], np.float32) - np.float32(spheres[-1]["radius"])
-    hi = np.asarray(spheres[-1]["pos"], np.float32) + np.float32(spheres[-1]["radius"])
-    nodes[last]["primitives_len"] += 1
-    parent = {}
-    for i in range(len(nodes)):
-        if nodes[i]["primitives_len"] == 0:
-            parent[i + 1] = i
-            parent[int(nodes[i]["primitives_or_second_child_index"])] = i
-    i = last
-    while True:
-        nodes[i]["bounds_min"] = np.minimum(nodes[i]["bounds_min"], lo)
-        nodes[i]["bounds_max"] = np.maximum(nodes[i]["bounds_max"], hi)
-        if i == 0:
-            break
-        i = parent[i]
-    sc = R.Scene(base.materials, spheres, base.plane_descs, base.vertices, base.normals, base.triangles, base.camera_desc,
-                 planes=base.planes, primitives=new_prims, bvh_nodes=nodes, bvh_depth=base.bvh_depth)
+    base, sc = foreign_trees.base(), foreign_trees.twin_sphere_scene()
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 128, 80, 0, 4, 10)
     plain, _ = oracle.render(util.oracle_scene(base), util.oracle_env(big_env), base.camera_uniform().view(oracle.CAMERA), 128, 80, 0, 4, 10)
     assert not np.array_equal(util.bits(ref), util.bits(plain))  # the twin does win somewhere
@@ -553,29 +519,14 @@ def test_leaves_that_share_records_or_too_many_fallback_records_keep_the_tree_wa
     """The flat loop carries a hit as a 6-bit record index and gives every record ONE visiting rank.  A foreign BVH
     whose leaves overlap (a record in two leaves: the reference simply tests it twice), or a scene with more than 64
     spheres behind a 64-record BVH, must fall back to the tree walk and still match the oracle."""
-    from rsoderh_raytracing_amd import types as T
-    base = R.Scene.load_toml(util.scene_path("default"))
-    nodes = base.bvh_nodes.copy()
-    leaves = [i for i in range(len(nodes)) if nodes[i]["primitives_len"] > 1]
-    b_ = next(i for i in leaves[1:] if nodes[i]["primitives_or_second_child_index"] > 0)
-    nodes[b_]["primitives_or_second_child_index"] -= 1  # leaf b now also holds its left neighbour's last record ...
-    nodes[b_]["primitives_len"] += 1                    # (boxes untouched: they still nest, only the sharing disqualifies)
-    sc = R.Scene(base.materials, base.spheres, base.plane_descs, base.vertices, base.normals, base.triangles, base.camera_desc,
-                 planes=base.planes, primitives=base.primitives, bvh_nodes=nodes, bvh_depth=base.bvh_depth)
+    base, sc = foreign_trees.base(), foreign_trees.shared_record_scene()  # a leaf also holds its left neighbour's last record
     ref, ost = oracle.render(util.oracle_scene(sc), util.oracle_env(big_env), sc.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
     img, st = gpu_render(sc, big_env, 96, 64, 0, 4, 10)
     assert np.array_equal(util.bits(img), util.bits(ref))
     assert (st["ext_rays"], st["shadow_rays"]) == (ost["ext_rays"], ost["shadow_rays"])
     # 70 spheres, of which the BVH (and so `primitives`) knows only the first 10: cast_ray's brute-force loop still
     # visits all 70 after a BVH miss (shader.wgsl:583-590), and a hit on sphere 64.. does not fit 6 bits
-    spheres = np.zeros(70, T.SPHERE)
-    spheres[:10] = base.spheres
-    for i in range(10, 70):
-        spheres[i]["pos"] = (-6.0 + 0.2 * i, 2.5 + 0.03 * i, -4.0)
-        spheres[i]["radius"] = 0.12
-        spheres[i]["material_id"] = i % len(base.materials)
-    sc2 = R.Scene(base.materials, spheres, base.plane_descs, base.vertices, base.normals, base.triangles, base.camera_desc,
-                  planes=base.planes, primitives=base.primitives, bvh_nodes=base.bvh_nodes, bvh_depth=base.bvh_depth)
+    sc2 = foreign_trees.hidden_spheres_scene()
     ref2, ost2 = oracle.render(util.oracle_scene(sc2), util.oracle_env(big_env), sc2.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
     plain, _ = oracle.render(util.oracle_scene(base), util.oracle_env(big_env), base.camera_uniform().view(oracle.CAMERA), 96, 64, 0, 4, 10)
     assert not np.array_equal(util.bits(ref2), util.bits(plain))  # the extra spheres are seen (through the fallback only)
