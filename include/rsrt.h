@@ -1047,6 +1047,52 @@ rsrt_status rsrt_display_video(rsrt_context *ctx, uint32_t source, uint32_t samp
                                float bloom_intensity, const rsrt_colour_params *colour, const rsrt_hdr_params *hdr, const rsrt_video_params *video,
                                void *host_out, size_t n_bytes, rsrt_hdr_levels *levels_out);
 
+/* -- JPEG output: a baseline JPEG / JFIF file built on the device (no reference counterpart) --------------------------------------------
+ * What every viewer and browser opens.  rsrt_display_jpeg is the colour display's chain up to and with the tone map and the LUT (the
+ * colour rsrt_display_colour_srgb8 quantises), then JFIF's BT.601 full-range Y'CbCr, 4:2:0 at the centre siting or 4:4:4, an 8 x 8 f32
+ * DCT, the IJG-scaled Annex K quantisation tables and the Annex K Huffman tables: three launches (blocks, an exclusive scan of the
+ * blocks' bit counts, the packer) and a copy of the scan alone: at 1920 x 1080 a quality-90 file of a noisy 8-spp render measured a
+ * quarter of an NV12 frame's bytes, and the call 4.5 times the NV12 call (DESIGN.md 27 says where the time goes).  The arithmetic is
+ * published in include/rsrt_jpeg.h and is bitwise reproducible; the host writes the headers, stuffs the scan and ends the file.  Whole
+ * frame only.  Nothing here writes any buffer the context holds.  A refused call launches nothing and writes nothing.
+ * rsrt_jpeg_params defaults: quality 90, RSRT_JPEG_420, flags 0, reserved 0 (RSRT_JPEG_DEFAULT_* in include/rsrt_jpeg.h). */
+#define RSRT_JPEG_420 0u /* rsrt_jpeg_params.subsampling: MCU 16 x 16, four Y blocks, Cb, Cr */
+#define RSRT_JPEG_444 1u /* MCU 8 x 8: Y, Cb, Cr */
+typedef struct rsrt_jpeg_params {
+    uint32_t quality;     /* 1 .. 100, the IJG scale */
+    uint32_t subsampling; /* RSRT_JPEG_420 or RSRT_JPEG_444 */
+    uint32_t flags;       /* 0 */
+    uint32_t reserved;    /* 0 */
+} rsrt_jpeg_params;
+/* `source` as a complete JPEG file in host_out, *n_bytes_out its size.  capacity: host_out's room; rsrt_jpeg_max_bytes (rsrt_jpeg.h) of
+ * the source's size always suffices.  Sources, local, bloom_intensity, colour, readiness, the partition refusal and the order of the
+ * checks are rsrt_display_colour_srgb8's; RSRT_ERR_INVALID_ARGUMENT also for NULL jpeg, host_out or n_bytes_out, params
+ * rsrt_jpeg_params_ok refuses (quality outside 1 .. 100, an unknown subsampling, a flag, reserved != 0), and a frame whose worst case
+ * reaches 2^32 bits (rsrt_jpeg_size_ok in rsrt_jpeg.h).  A capacity smaller than the file: RSRT_ERR_INVALID_ARGUMENT with *n_bytes_out the size needed, host_out untouched
+ * (the kernels have run by then: the size is the coded scan's).
+ * Rust: pub fn rsrt_display_jpeg(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32, local: *const RsrtLocalParams,
+ *                                bloom_intensity: f32, colour: *const RsrtColourParams, jpeg: *const RsrtJpegParams,
+ *                                host_out: *mut c_void, capacity: usize, n_bytes_out: *mut usize) -> i32; */
+rsrt_status rsrt_display_jpeg(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                              float bloom_intensity, const rsrt_colour_params *colour, const rsrt_jpeg_params *jpeg, void *host_out,
+                              size_t capacity, size_t *n_bytes_out);
+/* The first stage alone: the quantised coefficients, int16 in zigzag order, 64 a block, blocks in scan order (DC as it is, not its
+ * difference).  n_values = 64 * rsrt_jpeg_blocks(width, height, subsampling).  Refusals as above.
+ * Rust: pub fn rsrt_display_jpeg_coefficients(ctx: *mut RsrtContext, source: u32, sample_total: u32, exposure: f32,
+ *                                             local: *const RsrtLocalParams, bloom_intensity: f32, colour: *const RsrtColourParams,
+ *                                             jpeg: *const RsrtJpegParams, host_coefs: *mut i16, n_values: usize) -> i32; */
+rsrt_status rsrt_display_jpeg_coefficients(rsrt_context *ctx, uint32_t source, uint32_t sample_total, float exposure, const rsrt_local_params *local,
+                                           float bloom_intensity, const rsrt_colour_params *colour, const rsrt_jpeg_params *jpeg, int16_t *host_coefs,
+                                           size_t n_values);
+/* The second and third stage on the caller's coefficients (that layout) of a width x height picture: the file that quality's tables
+ * and these coefficients make.  Needs no picture and no scene.  RSRT_ERR_INVALID_ARGUMENT also for a size of 0, another n_values and a
+ * value outside [-1023, 1023] (a DC: [-1024, 1023]), found before anything is launched; the capacity protocol is rsrt_display_jpeg's.
+ * Rust: pub fn rsrt_jpeg_encode_coefficients(ctx: *mut RsrtContext, width: u32, height: u32, jpeg: *const RsrtJpegParams,
+ *                                            host_coefs: *const i16, n_values: usize, host_out: *mut c_void, capacity: usize,
+ *                                            n_bytes_out: *mut usize) -> i32; */
+rsrt_status rsrt_jpeg_encode_coefficients(rsrt_context *ctx, uint32_t width, uint32_t height, const rsrt_jpeg_params *jpeg, const int16_t *host_coefs,
+                                          size_t n_values, void *host_out, size_t capacity, size_t *n_bytes_out);
+
 /* -- ray-query probe: cast_ray / cast_ray_bvh for a batch of rays (shader.wgsl:469-601) -------
  * Exists for parity tests of traversal + intersection without the RNG: out records are
  * {did_hit u32, distance f32, hit_point 3xf32, normal 3xf32, material_id u32} = 36 bytes.

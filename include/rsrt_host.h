@@ -118,6 +118,33 @@ struct rsrt_video_params;
 int rsrt_y4m_write(const char *path, int append, uint32_t width, uint32_t height, uint32_t fps_num, uint32_t fps_den, const struct rsrt_video_params *video,
                    const void *planar_frame, size_t n_bytes);
 
+/* JPEG output (include/rsrt.h "JPEG output") on the CPU: the whole of include/rsrt_jpeg.h, sequential — the reference the device's file is
+ * held to byte for byte.  sdr_rgb: display-referred linear RGB, 3 floats a pixel, rows top to bottom (what rsrt_finish_sdr gives: any
+ * float is legal).  out receives the file when capacity suffices; *n_bytes_out is its size either way (rsrt_jpeg_max_bytes always
+ * suffices; out may be NULL with capacity 0 to ask).  0: written; 1: an argument is refused (NULL, params rsrt_jpeg_params_ok refuses, a
+ * size rsrt_jpeg_size_ok refuses: a side of 0 or above 65535, a worst case of 2^32 bits, the device's own limit) and nothing is written; 2: capacity is too small, *n_bytes_out says what is needed, out is untouched.
+ * Rust: pub fn rsrt_jpeg_encode_host(sdr_rgb: *const f32, width: u32, height: u32, jpeg: *const RsrtJpegParams, out: *mut c_void,
+ *                                    capacity: usize, n_bytes_out: *mut usize) -> i32; */
+struct rsrt_jpeg_params;
+int rsrt_jpeg_encode_host(const float *sdr_rgb, uint32_t width, uint32_t height, const struct rsrt_jpeg_params *jpeg, void *out, size_t capacity,
+                          size_t *n_bytes_out);
+/* Steps 1 to 5 alone: the quantised coefficients, int16 in zigzag order, 64 a block, blocks in scan order;
+ * n_values = 64 * rsrt_jpeg_blocks(width, height, subsampling).  0 or 1 as above. */
+int rsrt_jpeg_coefficients_host(const float *sdr_rgb, uint32_t width, uint32_t height, const struct rsrt_jpeg_params *jpeg, int16_t *coefs_out, size_t n_values);
+/* The sequential entropy coder and the file alone, from coefficients in that layout; 1 also for another n_values and a value outside
+ * [-1023, 1023] (a DC: [-1024, 1023]).  What rsrt_jpeg_encode_coefficients computes on the device. */
+int rsrt_jpeg_from_coefficients(const int16_t *coefs, size_t n_values, uint32_t width, uint32_t height, const struct rsrt_jpeg_params *jpeg, void *out,
+                                size_t capacity, size_t *n_bytes_out);
+/* n_frames JPEG files of one size as one Motion-JPEG RIFF AVI 1.0 file, in one call: hdrl (avih; one strl: strh vids / MJPG, strf a
+ * BITMAPINFOHEADER with biCompression MJPG, 24 bits), movi with one 00dc chunk a frame, padded to even, and idx1 with every frame a key
+ * frame.  Stateless like rsrt_y4m_write: compressed frames are small enough to keep until the last is there.  0: written; 1: refused
+ * (NULL, n_frames 0, a NULL or empty frame, a size or rate of 0, a file that would reach 2 GiB); 2: the file cannot be opened; 3: a
+ * write failed.
+ * Rust: pub fn rsrt_avi_mjpeg_write(path: *const c_char, frames: *const *const c_void, sizes: *const usize, n_frames: usize,
+ *                                   width: u32, height: u32, fps_num: u32, fps_den: u32) -> i32; */
+int rsrt_avi_mjpeg_write(const char *path, const void *const *frames, const size_t *sizes, size_t n_frames, uint32_t width, uint32_t height, uint32_t fps_num,
+                         uint32_t fps_den);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@
 #include "rsrt_colour.h"
 #include "rsrt_finish.h"
 #include "rsrt_hdr.h"
+#include "rsrt_jpeg.h"
 #include "rsrt_video.h"
 #include "rsrt_dof.h"
 #include "rsrt_motion.h"
@@ -524,6 +525,31 @@ public:
         source_size(source, &w, &h);
         std::vector<uint8_t> out(rsrt_video_planes(w, h, &video, nullptr));
         check_ctx(rsrt_display_video(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, hdr, &video, out.data(), out.size(), levels));
+        return out;
+    }
+    // -- JPEG output (rsrt.h "JPEG output"): one device, like the denoiser -------------------------------------------------
+    static rsrt_jpeg_params jpeg_defaults()
+    {
+        return rsrt_jpeg_params{RSRT_JPEG_DEFAULT_QUALITY, RSRT_JPEG_DEFAULT_SUBSAMPLING, RSRT_JPEG_DEFAULT_FLAGS, RSRT_JPEG_DEFAULT_RESERVED};
+    }
+    // display_colour's chain with its LUT as a complete baseline JPEG file, coded on the device.  The buffer is sized from a guess, an eighth of
+    // the worst case, and the call is made once more with the size the library asks for.  lut_strength < 0: 1 with a LUT, 0 without
+    std::vector<uint8_t> display_jpeg(const rsrt_jpeg_params &jpeg = jpeg_defaults(), uint32_t source = RSRT_EXPOSURE_MEAN, float exposure = 0.0f, const float *white = nullptr,
+                                      float lut_strength = -1.0f, const rsrt_local_params *local = nullptr, float bloom_intensity = 0.0f)
+    {
+        const rsrt_colour_params c = colour_params(white, lut_strength);
+        uint32_t w = 0, h = 0;
+        source_size(source, &w, &h);
+        const size_t limit = rsrt_jpeg_max_bytes(w, h, jpeg.subsampling);
+        std::vector<uint8_t> out(limit ? RSRT_JPEG_HEADER_BYTES + 2u + limit / 8u : 1u);
+        size_t n = 0;
+        rsrt_status st = rsrt_display_jpeg(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &jpeg, out.data(), out.size(), &n);
+        if (st != RSRT_OK && n > out.size() && n <= limit) { // (refused for the room alone: n is the size needed)
+            out.resize(n);
+            st = rsrt_display_jpeg(context(0), source, sample_count_, exposure_or_one(exposure), local, bloom_intensity, &c, &jpeg, out.data(), out.size(), &n);
+        }
+        check_ctx(st);
+        out.resize(n);
         return out;
     }
     // -- depth of field (rsrt.h "depth of field"): one device, like the denoiser ----------------------------------------

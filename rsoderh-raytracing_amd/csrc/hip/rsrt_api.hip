@@ -852,6 +852,26 @@ rsrt_status read_back(rsrt_context *ctx, void *host, size_t bytes, size_t extra,
     return RSRT_OK;
 }
 
+// The same for a result whose size the device decides.  scratch has `scratch_bytes` bytes; enqueue(scratch) launches as above; then the
+// `count_bytes` bytes at scratch + count_at reach count_host, size_of() — which may read them — says how many bytes at scratch + data_at
+// are the result, and the call returns when `host`, sized to that, holds them.  Two copies and two waits: the second's size is the first's news.
+template <class Enqueue, class SizeOf>
+rsrt_status read_back_counted(rsrt_context *ctx, size_t scratch_bytes, Enqueue enqueue, size_t count_at, void *count_host, size_t count_bytes, size_t data_at, SizeOf size_of,
+                              std::vector<unsigned char> &host)
+{
+    rsrt_status st = ensure_scratch(ctx, scratch_bytes);
+    if (st || (st = begin_work(ctx, ctx->stream)) || (st = enqueue(ctx->scratch))) return st;
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipMemcpyAsync(count_host, static_cast<const char *>(ctx->scratch) + count_at, count_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if ((st = end_work(ctx, ctx->stream))) return st;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t n = size_of();
+    if (data_at + n > scratch_bytes) return fail(ctx, RSRT_ERR_HIP, "read_back_counted: the device counted %zu bytes, more than the scratch buffer's", n);
+    host.resize(n);
+    if (n) HIP_TRY(ctx, hipMemcpy(host.data(), static_cast<const char *>(ctx->scratch) + data_at, n, hipMemcpyDeviceToHost));
+    return RSRT_OK;
+}
+
 // the snapshot and the last estimate mean nothing any more (a cleared accumulator, a reset); the buffers stay
 void drop_noise(rsrt_context *ctx)
 {
@@ -1971,3 +1991,4 @@ rsrt_status rsrt_cast_rays(rsrt_context *ctx, uint32_t n, const float *origins, 
 #include "rt_finish.h"
 #include "rt_hdr.h"
 #include "rt_video.h"
+#include "rt_jpeg.h"

@@ -17,6 +17,7 @@
 //                            eight corners come through L2 (staging the tile's columns in LDS was no faster: DESIGN.md §17).
 // The tiled displays — these two, rt_display_colour_kernel, rt_display_finish_kernel and rt_display_hdr_kernel — share DisplayChain, the struct they take by value,
 // rt_display_gather, which reads a pixel's inputs from it, and display_chain, which makes their entry points' checks and fills it.
+#include "../../../include/rsrt_jpeg.h"
 #include "../../../include/rsrt_video.h" // (the whole display chain, rsrt_hdr.h and below: display_chain checks every stage's parameters)
 
 #define RT_LC_PW 64
@@ -154,14 +155,17 @@ uint32_t *local_blurred(const rsrt_context *ctx) { return static_cast<uint32_t *
 
 // display_chain's `demands`: the params an entry point refuses as NULL (others are off when NULL); CHAIN_FLOATS: it writes a float a pixel, not
 // bytes; CHAIN_HDR: it writes what hdr->encoding says, 4 or 8 bytes a pixel, and takes no LUT; CHAIN_VIDEO: it writes a frame of
-// rsrt_video_planes' size, and `video` says whether hdr belongs (RSRT_VIDEO_HDR10: required, RSRT_HDR_PQ10) or not (RSRT_VIDEO_BT709: NULL)
-enum : uint32_t { CHAIN_LOCAL = 1u, CHAIN_COLOUR = 2u, CHAIN_FINISH = 4u, CHAIN_FLOATS = 8u, CHAIN_HDR = 16u, CHAIN_VIDEO = 32u };
+// rsrt_video_planes' size, and `video` says whether hdr belongs (RSRT_VIDEO_HDR10: required, RSRT_HDR_PQ10) or not (RSRT_VIDEO_BT709: NULL);
+// CHAIN_JPEG: it writes a JPEG file into n_out bytes of room, whatever their number (the file's size is the coder's to say), or with
+// CHAIN_JPEG_COEFS the picture's 64 * rsrt_jpeg_blocks coefficients; `jpeg` is required and the picture must be one a file can hold
+enum : uint32_t { CHAIN_LOCAL = 1u, CHAIN_COLOUR = 2u, CHAIN_FINISH = 4u, CHAIN_FLOATS = 8u, CHAIN_HDR = 16u, CHAIN_VIDEO = 32u, CHAIN_JPEG = 64u, CHAIN_JPEG_COEFS = 128u };
 
 // Every check of the tiled displays, in the order the faults are reported in: the source, the local, colour, finish, hdr and video params, the bloom
 // intensity, the output's size, then what the context has to hold where it is asked for: the grid, the bloom image, the LUT.  Fills c.
 rsrt_status display_chain(rsrt_context *ctx, const char *what, uint32_t demands, uint32_t source, uint32_t sample_total, float exposure,
                           const rsrt_local_params *local, const rsrt_colour_params *colour, const rsrt_finish_params *finish, const rsrt_hdr_params *hdr,
-                          float intensity, const void *host, size_t n_out, DisplayChain *c, const rsrt_video_params *video = nullptr)
+                          float intensity, const void *host, size_t n_out, DisplayChain *c, const rsrt_video_params *video = nullptr,
+                          const rsrt_jpeg_params *jpeg = nullptr)
 {
     ImageView v;
     rsrt_status st = bloom_source(ctx, what, source, sample_total, exposure, &v);
@@ -188,10 +192,21 @@ rsrt_status display_chain(rsrt_context *ctx, const char *what, uint32_t demands,
         if (video->standard == RSRT_VIDEO_HDR10 ? !hdr || hdr->encoding != RSRT_HDR_PQ10 : hdr != nullptr)
             return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: hdr must be given with encoding RSRT_HDR_PQ10 for RSRT_VIDEO_HDR10 and be NULL for RSRT_VIDEO_BT709", what);
     }
+    if (demands & CHAIN_JPEG) {
+        if (!jpeg) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: jpeg is NULL", what);
+        if (!rsrt_jpeg_params_ok(jpeg)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: want quality in 1 .. 100, subsampling RSRT_JPEG_420 or RSRT_JPEG_444, flags 0, reserved 0", what);
+    }
     if (!rsrt_bloom_finite_nonneg(intensity)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: bloom_intensity must be finite and >= 0", what);
+    if (demands & CHAIN_JPEG) {
+        if (!rsrt_jpeg_size_ok(v.w, v.h, jpeg->subsampling))
+            return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: a %u x %u picture is more than a JPEG file of this library holds (sides to 65535, a worst case below 2^32 bits)", what, v.w, v.h);
+        const size_t values = (size_t)rsrt_jpeg_blocks(v.w, v.h, jpeg->subsampling) * 64u;
+        if (!host || ((demands & CHAIN_JPEG_COEFS) && n_out != values))
+            return (demands & CHAIN_JPEG_COEFS) ? fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu values", what, values) : fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: host_out is NULL", what);
+    }
     const bool floats = demands & CHAIN_FLOATS;
     const size_t want = (demands & CHAIN_VIDEO) ? rsrt_video_planes(v.w, v.h, video, nullptr) : floats ? v.pixels() : v.pixels() * (hdr && hdr->encoding == RSRT_HDR_SCRGB16F ? 8 : 4);
-    if (!host || n_out != want) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu %s", what, want, floats ? "floats" : "bytes");
+    if (!(demands & CHAIN_JPEG) && (!host || n_out != want)) return fail(ctx, RSRT_ERR_INVALID_ARGUMENT, "%s: expected %zu %s", what, want, floats ? "floats" : "bytes");
     *c = DisplayChain{}; // (what is not asked for stays zero)
     c->img = v.img; c->w = (int)v.w; c->h = (int)v.h; c->total = v.total; c->exposure = exposure;
     if (local) {

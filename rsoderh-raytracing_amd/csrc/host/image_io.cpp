@@ -10,6 +10,9 @@
 //  rsrt_write_png / rsrt_write_pfm
 //                          image output (the reference only presents to a window).
 //  rsrt_y4m_write          video output: rsrt_display_video's planar frames as a YUV4MPEG2 sequence.
+//  rsrt_jpeg_encode_host / rsrt_jpeg_from_coefficients / rsrt_avi_mjpeg_write
+//                          JPEG output: include/rsrt_jpeg.h on the CPU, sequential (the device's reference), and JPEG files
+//                          as one Motion-JPEG RIFF AVI.
 //  rsrt_display_srgb8_host the display transform of include/rsrt_tonemap.h on the CPU, for hosts that
 //                          downloaded the f32 sums.
 #include <cmath>
@@ -20,6 +23,7 @@
 #include <vector>
 
 #include "../../../include/rsrt_host.h"
+#include "../../../include/rsrt_jpeg.h"
 #include "../../../include/rsrt_video.h"
 #include "../../../include/rsrt_tonemap.h"
 
@@ -223,6 +227,130 @@ int rsrt_y4m_write(const char *path, int append, uint32_t width, uint32_t height
                           video->range == RSRT_VIDEO_FULL ? "FULL" : "LIMITED", sitings[video->siting], video->standard == RSRT_VIDEO_HDR10 ? "HDR10" : "BT709") > 0;
     }
     ok = ok && std::fputs("FRAME\n", f) >= 0 && std::fwrite(planar_frame, 1, n_bytes, f) == n_bytes;
+    return (std::fclose(f) == 0 && ok) ? 0 : 3;
+}
+
+// include/rsrt_jpeg.h steps 1 to 5 over a picture: the quantised coefficients of every block in scan order
+static void jpeg_coefficients(const float *sdr_rgb, uint32_t w, uint32_t h, const rsrt_jpeg_params *p, std::vector<int16_t> &coefs)
+{
+    const bool sub = p->subsampling == RSRT_JPEG_420;
+    const uint32_t side = rsrt_jpeg_mcu_side(p->subsampling), mw = rsrt_jpeg_mcus(w, p->subsampling), mh = rsrt_jpeg_mcus(h, p->subsampling);
+    coefs.assign((size_t)rsrt_jpeg_blocks(w, h, p->subsampling) * 64u, 0);
+    std::vector<float> s((size_t)3 * side * side); // the MCU's samples, three planes of side x side, pixels clamped to the picture
+    float blk[64], c[64];
+    int16_t *out = coefs.data();
+    for (uint32_t my = 0; my < mh; my++)
+        for (uint32_t mx = 0; mx < mw; mx++) {
+            for (uint32_t y = 0; y < side; y++)
+                for (uint32_t x = 0; x < side; x++) {
+                    const uint32_t px = mx * side + x < w ? mx * side + x : w - 1u, py = my * side + y < h ? my * side + y : h - 1u;
+                    float v[3];
+                    rsrt_jpeg_samples(sdr_rgb + ((size_t)py * w + px) * 3u, v);
+                    for (int k = 0; k < 3; k++) s[((size_t)k * side + y) * side + x] = v[k];
+                }
+            for (uint32_t b = 0; b < (sub ? 4u : 1u); b++, out += 64) { // Y00 Y01 Y10 Y11, or Y
+                for (uint32_t y = 0; y < 8u; y++)
+                    for (uint32_t x = 0; x < 8u; x++) blk[y * 8u + x] = s[((b / 2u) * 8u + y) * side + (b % 2u) * 8u + x];
+                rsrt_jpeg_fdct(blk, c);
+                rsrt_jpeg_quantise_block(c, 0u, p->quality, out);
+            }
+            for (uint32_t k = 1; k < 3u; k++, out += 64) { // Cb, Cr
+                const float *const pl = s.data() + (size_t)k * side * side;
+                for (uint32_t y = 0; y < 8u; y++)
+                    for (uint32_t x = 0; x < 8u; x++)
+                        blk[y * 8u + x] = sub ? rsrt_video_centre(pl[2u * y * side + 2u * x], pl[2u * y * side + 2u * x + 1u], pl[(2u * y + 1u) * side + 2u * x], pl[(2u * y + 1u) * side + 2u * x + 1u])
+                                              : pl[y * side + x];
+                rsrt_jpeg_fdct(blk, c);
+                rsrt_jpeg_quantise_block(c, 1u, p->quality, out);
+            }
+        }
+}
+
+int rsrt_jpeg_from_coefficients(const int16_t *coefs, size_t n_values, uint32_t width, uint32_t height, const rsrt_jpeg_params *jpeg, void *out, size_t capacity,
+                                size_t *n_bytes_out)
+{
+    if (!coefs || !jpeg || !n_bytes_out || (!out && capacity) || !rsrt_jpeg_params_ok(jpeg) || !rsrt_jpeg_size_ok(width, height, jpeg->subsampling)) return 1;
+    const uint64_t n_blocks = rsrt_jpeg_blocks(width, height, jpeg->subsampling);
+    if (n_values != n_blocks * 64u) return 1;
+    for (size_t i = 0; i < n_values; i++)
+        if (!rsrt_jpeg_value_ok(coefs[i], i % 64u == 0u)) return 1;
+    std::vector<uint8_t> scan((size_t)n_blocks * (RSRT_JPEG_BLOCK_BITS / 8u) + 1u, 0);
+    rsrt_jpeg_writer wr = {scan.data(), 0u};
+    for (uint64_t i = 0; i < n_blocks; i++) {
+        const int64_t pi = rsrt_jpeg_block_pred(i, jpeg->subsampling);
+        rsrt_jpeg_block_code(&wr, coefs + i * 64u, pi < 0 ? 0 : coefs[pi * 64], rsrt_jpeg_block_component(i, jpeg->subsampling) ? 1u : 0u);
+    }
+    *n_bytes_out = rsrt_jpeg_file(scan.data(), wr.n_bits, width, height, jpeg, static_cast<uint8_t *>(out), capacity);
+    return *n_bytes_out <= capacity && out ? 0 : 2;
+}
+
+int rsrt_jpeg_encode_host(const float *sdr_rgb, uint32_t width, uint32_t height, const rsrt_jpeg_params *jpeg, void *out, size_t capacity, size_t *n_bytes_out)
+{
+    if (!sdr_rgb || !jpeg || !n_bytes_out || (!out && capacity) || !rsrt_jpeg_params_ok(jpeg) || !rsrt_jpeg_size_ok(width, height, jpeg->subsampling)) return 1;
+    std::vector<int16_t> coefs;
+    jpeg_coefficients(sdr_rgb, width, height, jpeg, coefs);
+    return rsrt_jpeg_from_coefficients(coefs.data(), coefs.size(), width, height, jpeg, out, capacity, n_bytes_out);
+}
+
+int rsrt_jpeg_coefficients_host(const float *sdr_rgb, uint32_t width, uint32_t height, const rsrt_jpeg_params *jpeg, int16_t *coefs_out, size_t n_values)
+{
+    if (!sdr_rgb || !jpeg || !coefs_out || !rsrt_jpeg_params_ok(jpeg) || !rsrt_jpeg_size_ok(width, height, jpeg->subsampling)) return 1;
+    if (n_values != rsrt_jpeg_blocks(width, height, jpeg->subsampling) * 64u) return 1;
+    std::vector<int16_t> coefs;
+    jpeg_coefficients(sdr_rgb, width, height, jpeg, coefs);
+    std::memcpy(coefs_out, coefs.data(), n_values * sizeof(int16_t));
+    return 0;
+}
+
+// RIFF AVI 1.0: RIFF 'AVI ' { LIST hdrl { avih, LIST strl { strh, strf } }, LIST movi { 00dc .. }, idx1 }, every number little-endian
+int rsrt_avi_mjpeg_write(const char *path, const void *const *frames, const size_t *sizes, size_t n_frames, uint32_t width, uint32_t height, uint32_t fps_num,
+                         uint32_t fps_den)
+{
+    if (!path || !frames || !sizes || n_frames == 0 || width == 0 || height == 0 || fps_num == 0 || fps_den == 0) return 1;
+    uint64_t movi = 4u, largest = 0u; // 'movi', then the chunks
+    for (size_t i = 0; i < n_frames; i++) {
+        if (!frames[i] || sizes[i] == 0) return 1;
+        movi += 8u + sizes[i] + (sizes[i] & 1u);
+        largest = sizes[i] > largest ? sizes[i] : largest;
+        if (movi >= (1ull << 31)) return 1;
+    }
+    const uint64_t hdrl = 4u + (8u + 56u) + (8u + 4u + (8u + 56u) + (8u + 40u)), idx1 = 16u * (uint64_t)n_frames;
+    const uint64_t riff = 4u + (8u + hdrl) + (8u + movi) + (8u + idx1);
+    if (riff + 8u >= (1ull << 31)) return 1;
+    std::vector<uint8_t> h;
+    const auto u32 = [&h](uint64_t v) { for (int k = 0; k < 4; k++) h.push_back((uint8_t)(v >> (8 * k))); };
+    const auto u16 = [&h](uint32_t v) { h.push_back((uint8_t)v); h.push_back((uint8_t)(v >> 8)); };
+    const auto tag = [&h](const char *t) { h.insert(h.end(), t, t + 4); };
+    tag("RIFF"); u32(riff); tag("AVI ");
+    tag("LIST"); u32(hdrl); tag("hdrl");
+    tag("avih"); u32(56u);
+    u32((uint64_t)fps_den * 1000000ull / fps_num);                                              // dwMicroSecPerFrame
+    u32((largest * (uint64_t)fps_num + fps_den - 1u) / fps_den > 0xffffffffull ? 0xffffffffull : (largest * (uint64_t)fps_num + fps_den - 1u) / fps_den); // dwMaxBytesPerSec
+    u32(0u); u32(0x10u);                                                                        // dwPaddingGranularity, dwFlags = AVIF_HASINDEX
+    u32(n_frames); u32(0u); u32(1u); u32(largest); u32(width); u32(height);                     // frames, initial frames, streams, buffer, size
+    u32(0u); u32(0u); u32(0u); u32(0u);                                                         // reserved
+    tag("LIST"); u32(4u + (8u + 56u) + (8u + 40u)); tag("strl");
+    tag("strh"); u32(56u); tag("vids"); tag("MJPG");
+    u32(0u); u16(0u); u16(0u); u32(0u);                                                         // flags, priority, language, initial frames
+    u32(fps_den); u32(fps_num); u32(0u); u32(n_frames); u32(largest); u32(0xffffffffu); u32(0u); // scale, rate, start, length, buffer, quality, sample size
+    u16(0u); u16(0u); u16(width > 0xffffu ? 0xffffu : width); u16(height > 0xffffu ? 0xffffu : height); // rcFrame
+    tag("strf"); u32(40u);
+    u32(40u); u32(width); u32(height); u16(1u); u16(24u); tag("MJPG"); u32((uint64_t)width * height * 3u > 0xffffffffull ? 0xffffffffull : (uint64_t)width * height * 3u);
+    u32(0u); u32(0u); u32(0u); u32(0u);                                                         // pels per metre x, y, colours used, important
+    tag("LIST"); u32(movi); tag("movi");
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return 2;
+    bool ok = std::fwrite(h.data(), 1, h.size(), f) == h.size();
+    h.clear(); // (the index is built here next and written last)
+    uint64_t at = 4u; // a chunk's offset from 'movi'
+    for (size_t i = 0; ok && i < n_frames; i++) {
+        uint8_t head[8] = {'0', '0', 'd', 'c', (uint8_t)sizes[i], (uint8_t)(sizes[i] >> 8), (uint8_t)(sizes[i] >> 16), (uint8_t)(sizes[i] >> 24)};
+        ok = std::fwrite(head, 1, 8, f) == 8 && std::fwrite(frames[i], 1, sizes[i], f) == sizes[i] && (!(sizes[i] & 1u) || std::fputc(0, f) == 0);
+        tag("00dc"); u32(0x10u); u32(at); u32(sizes[i]); // AVIIF_KEYFRAME
+        at += 8u + sizes[i] + (sizes[i] & 1u);
+    }
+    const uint8_t ih[8] = {'i', 'd', 'x', '1', (uint8_t)idx1, (uint8_t)(idx1 >> 8), (uint8_t)(idx1 >> 16), (uint8_t)(idx1 >> 24)};
+    ok = ok && std::fwrite(ih, 1, 8, f) == 8 && std::fwrite(h.data(), 1, h.size(), f) == h.size();
     return (std::fclose(f) == 0 && ok) ? 0 : 3;
 }
 

@@ -48,6 +48,14 @@ def lib():
         L.rsrt_write_pfm.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32]
         L.rsrt_y4m_write.restype = C.c_int
         L.rsrt_y4m_write.argtypes = [C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_jpeg_encode_host.restype = C.c_int
+        L.rsrt_jpeg_encode_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_jpeg_coefficients_host.restype = C.c_int
+        L.rsrt_jpeg_coefficients_host.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_jpeg_from_coefficients.restype = C.c_int
+        L.rsrt_jpeg_from_coefficients.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_avi_mjpeg_write.restype = C.c_int
+        L.rsrt_avi_mjpeg_write.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
         L.rsrt_display_srgb8_host.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]
         _lib = L
     return _lib
@@ -280,6 +288,65 @@ def write_y4m(path, frame, fps=(30, 1), append=False):
         raise ValueError("rsrt_y4m_write: want a planar frame of the size's byte count and a frame rate above 0")
     if rc != 0:
         raise OSError("rsrt_y4m_write failed: " + str(path))
+
+
+def _jpeg_sized(what, call, width, height, params):
+    """call(out, capacity, byref(n)) of one of the host's JPEG functions: asked for the size first, then given the room.  bytes."""
+    n = C.c_size_t(0)
+    rc = call(None, 0, C.byref(n))
+    if rc == 2:
+        out = np.empty(n.value, np.uint8)
+        rc = call(_p(out), out.nbytes, C.byref(n))
+    if rc != 0:
+        raise ValueError("%s: want a picture of 1 .. 65535 a side, quality 1 .. 100, subsampling \"420\" or \"444\" and values in range (%d x %d, quality %d)"
+                         % (what, width, height, params.quality))
+    return out[:n.value].tobytes()
+
+
+def encode_jpeg(sdr_rgb, quality=None, subsampling=None):
+    """rsrt_jpeg_encode_host: display-referred linear RGB, [H, W, 3] f32 (any float is legal), as a baseline JPEG file: the whole of
+    include/rsrt_jpeg.h on the CPU, what State.display_jpeg's bytes are held to.  bytes."""
+    from .state import jpeg_params
+    sdr_rgb = np.ascontiguousarray(sdr_rgb, np.float32)
+    assert sdr_rgb.ndim == 3 and sdr_rgb.shape[2] == 3
+    j = jpeg_params(quality, subsampling)
+    h, w = sdr_rgb.shape[:2]
+    return _jpeg_sized("rsrt_jpeg_encode_host", lambda out, cap, n: lib().rsrt_jpeg_encode_host(_p(sdr_rgb), w, h, C.byref(j), out, cap, n), w, h, j)
+
+
+def jpeg_coefficients(sdr_rgb, quality=None, subsampling=None):
+    """rsrt_jpeg_coefficients_host: the quantised coefficients of that picture, int16 [blocks, 64], State.jpeg_coefficients' layout."""
+    from .state import jpeg_blocks, jpeg_params
+    sdr_rgb = np.ascontiguousarray(sdr_rgb, np.float32)
+    assert sdr_rgb.ndim == 3 and sdr_rgb.shape[2] == 3
+    j = jpeg_params(quality, subsampling)
+    h, w = sdr_rgb.shape[:2]
+    out = np.empty((jpeg_blocks(w, h, j.subsampling), 64), np.int16)
+    if lib().rsrt_jpeg_coefficients_host(_p(sdr_rgb), w, h, C.byref(j), _p(out), out.size) != 0:
+        raise ValueError("rsrt_jpeg_coefficients_host: want a picture of 1 .. 65535 a side, quality 1 .. 100, subsampling \"420\" or \"444\"")
+    return out
+
+
+def jpeg_from_coefficients(coefs, width, height, quality=None, subsampling=None):
+    """rsrt_jpeg_from_coefficients: the sequential entropy coder and the file from coefficients in State.jpeg_coefficients' layout.  bytes."""
+    from .state import jpeg_params
+    coefs = np.ascontiguousarray(coefs, np.int16)
+    j = jpeg_params(quality, subsampling)
+    return _jpeg_sized("rsrt_jpeg_from_coefficients", lambda out, cap, n: lib().rsrt_jpeg_from_coefficients(_p(coefs), coefs.size, width, height, C.byref(j), out, cap, n),
+                       width, height, j)
+
+
+def write_avi_mjpeg(path, frames, width, height, fps=(30, 1)):
+    """rsrt_avi_mjpeg_write: JPEG files (bytes, all width x height) as one Motion-JPEG AVI, written in one call.  fps: (numerator,
+    denominator)."""
+    frames = [bytes(f) for f in frames]
+    ptrs = (C.c_char_p * max(1, len(frames)))(*frames)
+    sizes = (C.c_size_t * max(1, len(frames)))(*[len(f) for f in frames])
+    rc = lib().rsrt_avi_mjpeg_write(os.fsencode(path), ptrs, sizes, len(frames), width, height, fps[0], fps[1])
+    if rc == 1:
+        raise ValueError("rsrt_avi_mjpeg_write: want at least one frame, none of them empty, a size and a frame rate above 0, a file below 2 GiB")
+    if rc != 0:
+        raise OSError("rsrt_avi_mjpeg_write failed: " + str(path))
 
 
 def write_pfm(path, rgb):

@@ -46,7 +46,8 @@ _SYMBOLS = ["rsrt_context_create", "rsrt_context_destroy", "rsrt_last_error", "r
             "rsrt_environment_sky", "rsrt_environment_download",
             "rsrt_white_meter", "rsrt_white_download", "rsrt_white_reset", "rsrt_colour_lut_build", "rsrt_colour_lut_upload",
             "rsrt_colour_lut_download", "rsrt_colour_lut_reset", "rsrt_display_colour_srgb8", "rsrt_display_finished_srgb8",
-            "rsrt_display_hdr", "rsrt_display_video"]
+            "rsrt_display_hdr", "rsrt_display_video",
+            "rsrt_display_jpeg", "rsrt_display_jpeg_coefficients", "rsrt_jpeg_encode_coefficients"]
 
 
 class RsrtError(RuntimeError):
@@ -263,6 +264,39 @@ def video_planes(width, height, depth=8, layout=VIDEO_SEMIPLANAR):
         planes.append((at, w * b, w, h))
         at += w * b * h
     return at, planes
+
+
+# the JPEG pass (include/rsrt.h "JPEG output", include/rsrt_jpeg.h): its enumerators, its defaults, its parameters and its sizes
+JPEG_420, JPEG_444 = 0, 1
+JPEG_SUBSAMPLINGS = {"420": JPEG_420, "444": JPEG_444}
+JPEG_DEFAULTS = {"quality": 90, "subsampling": "420", "flags": 0, "reserved": 0}
+JPEG_HEADER_BYTES = 623  # SOI .. SOS
+JPEG_BLOCK_BITS = 1664   # a block's slot in the worst case
+
+
+class JpegParams(C.Structure):
+    _fields_ = [("quality", C.c_uint32), ("subsampling", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def jpeg_params(quality=None, subsampling=None):
+    """rsrt_jpeg_params of quality 1 .. 100 and subsampling "420", "444" or a JPEG_* enumerator; JPEG_DEFAULTS where None.  What is
+    out of range is the library's to refuse."""
+    d = JPEG_DEFAULTS
+    sub = d["subsampling"] if subsampling is None else subsampling
+    return JpegParams(d["quality"] if quality is None else quality, JPEG_SUBSAMPLINGS.get(sub, sub), d["flags"], d["reserved"])
+
+
+def jpeg_blocks(width, height, subsampling="420"):
+    """rsrt_jpeg_blocks: the 8 x 8 blocks of a width x height picture's scan, partial MCUs whole."""
+    side, per = (8, 3) if JPEG_SUBSAMPLINGS.get(subsampling, subsampling) == JPEG_444 else (16, 6)
+    return -(-width // side) * -(-height // side) * per
+
+
+def jpeg_max_bytes(width, height, subsampling="420"):
+    """rsrt_jpeg_max_bytes: the room that always suffices for a width x height file."""
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        return 0
+    return JPEG_HEADER_BYTES + 2 * (JPEG_BLOCK_BITS // 8) * jpeg_blocks(width, height, subsampling) + 2
 
 
 class VideoFrame:
@@ -517,6 +551,9 @@ def lib():
         L.rsrt_display_colour_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_finished_srgb8.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         L.rsrt_display_hdr.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_display_jpeg.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.rsrt_display_jpeg_coefficients.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        L.rsrt_jpeg_encode_coefficients.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
         L.rsrt_display_video.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                          C.c_void_p]
         _lib = L
@@ -1205,6 +1242,58 @@ class State:
                                                C.byref(v), _p(out), out.nbytes, C.byref(lv) if levels else None), "rsrt_display_video")
         frame = VideoFrame(out, width, height, v)
         return (frame, {"max_cll": lv.max_cll, "max_fall": lv.max_fall, "max_q": lv.max_q, "sum_q": lv.sum_q}) if levels else frame
+
+    # -- JPEG output (include/rsrt.h "JPEG output") ----------------------------------------------------------
+    def _jpeg_file(self, what, call, guess, limit):
+        """call(buffer, capacity, byref(n)) into a buffer of `guess` bytes, once more with the size the library asks for (at most
+        `limit`, which always suffices); the file's bytes."""
+        n = C.c_size_t(0)
+        out = np.empty(max(1, min(guess, limit)), np.uint8)
+        rc = call(_p(out), out.nbytes, C.byref(n))
+        if rc != 0 and out.nbytes < n.value <= limit:  # (refused for the room alone: n is the size needed)
+            out = np.empty(n.value, np.uint8)
+            rc = call(_p(out), out.nbytes, C.byref(n))
+        self._check(rc, what)
+        return out[:n.value].tobytes()
+
+    def display_jpeg(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
+                     quality=None, subsampling=None, sample_total=None, **params):
+        """rsrt_display_jpeg: `source` as a complete baseline JPEG / JFIF file, coded on the device: display_colour_srgb8's chain (whose
+        arguments `source` .. `bloom_intensity`, sample_total and params are) with the LUT, then JFIF's Y'CbCr at `subsampling` ("420":
+        4:2:0, centre-sited; "444") and `quality` 1 .. 100 on the IJG scale (JPEG_DEFAULTS where None).  The buffer is sized from a guess,
+        an eighth of the worst case, and the call is made once more with the size the library asks for.  bytes."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        c = self._colour_params(white, lut_strength)
+        j = jpeg_params(quality, subsampling)
+        height, width = self._source_shape(source)
+        limit = jpeg_max_bytes(width, height, j.subsampling) or 1
+        st = self._source_total(source, sample_total)
+        ex = self._exposure_or_one(exposure)
+        return self._jpeg_file("rsrt_display_jpeg", lambda out, cap, n: self._L.rsrt_display_jpeg(
+            self._ctx, *st, ex, C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(j), out, cap, n), JPEG_HEADER_BYTES + 2 + limit // 8, limit)
+
+    def jpeg_coefficients(self, source="mean", exposure=None, white=None, lut_strength=None, shadows=None, highlights=None, bloom_intensity=0.0,
+                          quality=None, subsampling=None, sample_total=None, **params):
+        """rsrt_display_jpeg_coefficients: display_jpeg's first stage alone, the quantised DCT coefficients: int16 [blocks, 64], zigzag
+        order, blocks in scan order (MCUs row by row; Y00 Y01 Y10 Y11 Cb Cr, or Y Cb Cr at "444"), the DC as it is."""
+        local = None if shadows is None and highlights is None else self._local_params(shadows, highlights, params)
+        c = self._colour_params(white, lut_strength)
+        j = jpeg_params(quality, subsampling)
+        height, width = self._source_shape(source)
+        out = np.empty((max(1, jpeg_blocks(width, height, j.subsampling)), 64), np.int16)
+        self._check(self._L.rsrt_display_jpeg_coefficients(self._ctx, *self._source_total(source, sample_total), self._exposure_or_one(exposure),
+                                                           C.byref(local) if local is not None else None, bloom_intensity, C.byref(c), C.byref(j), _p(out), out.size),
+                    "rsrt_display_jpeg_coefficients")
+        return out
+
+    def jpeg_encode(self, coefs, width, height, quality=None, subsampling=None):
+        """rsrt_jpeg_encode_coefficients: the file that `quality`'s tables and the coefficients `coefs` (jpeg_coefficients' layout, any
+        shape of 64 * blocks int16) of a width x height picture make: the scan and the packer on the device.  bytes."""
+        j = jpeg_params(quality, subsampling)
+        coefs = np.ascontiguousarray(coefs, np.int16)
+        limit = jpeg_max_bytes(width, height, j.subsampling) or 1
+        return self._jpeg_file("rsrt_jpeg_encode_coefficients", lambda out, cap, n: self._L.rsrt_jpeg_encode_coefficients(
+            self._ctx, width, height, C.byref(j), _p(coefs), coefs.size, out, cap, n), JPEG_HEADER_BYTES + 2 + limit // 8, limit)
 
     # -- depth of field (include/rsrt.h "depth of field") ---------------------------------------------------
     def depth_of_field(self, source="mean", focus_distance=None, aperture=None, max_radius=None, sample_total=None, stream=None, out_ptr=None):
